@@ -2,6 +2,7 @@
 """bench.py -- megapixels/s of the joint-bilateral hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config north_star|c2|c3|c4|c5]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -82,7 +83,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-extras", "--no-colour-src", dest="no_extras", action="store_true",
                     help="skip the secondary launches and the C2/C3/C5 lines (keeps a profile of "
                          "this command to the one timed kernel shape)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's "
+                         "shard) as DIR/<name>.npy in float32, at most 64 MB in all (a fixed seeded "
+                         "sample of images, or of rows of one image, beyond that), and "
+                         "DIR/manifest.json naming the part kept")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # --------------------------------------------------------------------------- self-launch
@@ -460,15 +469,18 @@ class Workload:
             self.name = ("1x1 CNN -> trunc(r*255) -> BF(CNN,CNN) c=%g s=%g, batch %d x %dx%d per GPU"
                          % (sc, ss, n, w, h))
         self.pixels = float(n) * h * w
+        self.last = None                 # what the last timed step returned
 
     def timed_steps(self, steps, world, sharding, stub=False):
         """barrier + sync | K steps with per-step events on the launch stream | sync + barrier."""
+        last = None
         if stub:
             sharding.barrier(world)
             t0 = time.perf_counter()
             for _ in range(steps):
-                self.step()
+                last = self.step()
             sharding.barrier(world)
+            self.last = last
             return time.perf_counter() - t0, None
         torch = self.torch
         torch.cuda.synchronize()
@@ -479,13 +491,23 @@ class Workload:
         t0 = time.perf_counter()
         for e0, e1 in evs:
             e0.record()
-            self.step()
+            last = self.step()
             e1.record()
         torch.cuda.synchronize()
         sharding.barrier(world)
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        self.last = last
         return elapsed, sum(e0.elapsed_time(e1) for e0, e1 in evs) / max(1, steps)
+
+    def outputs(self):
+        """What the last timed step handed its caller, by name (valid until the next launch)."""
+        if self.last is None:
+            return {}
+        if self.kind == "chain":
+            r8, filtered = self.last
+            return {"reflectance_u8": r8, "filtered": filtered}
+        return {"filtered": self.last}
 
 
 class StubWorkload(Workload):
@@ -498,6 +520,7 @@ class StubWorkload(Workload):
         self.bytes_per_px = JBF_BYTES_PER_PX
         self.name = "stub (no kernel), batch %d x %dx%d per rank" % (n, w, h)
         self.step = lambda: time.sleep(0.01)
+        self.last = None
 
 
 def one_shot(torch, fn, reps=1):
@@ -510,6 +533,60 @@ def one_shot(torch, fn, reps=1):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
+
+
+# --------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20251015
+
+
+def sample_outputs(arrays, limit_bytes=DUMP_LIMIT_BYTES, seed=DUMP_SEED):
+    """{name: tensor [N, ...]} -> {name: (float32 ndarray, description of the part kept)}.
+    Everything when it fits in `limit_bytes` as float32; else every array gets an equal share:
+    a seeded choice of whole images (axis 0, kept in order), or - one image alone over the share -
+    one seeded image and a seeded choice of its rows.  The choice depends on the shapes only."""
+    import numpy as np
+    total = sum(int(t.numel()) for t in arrays.values()) * 4
+    share = limit_bytes // max(1, len(arrays)) // 4             # float32 elements per array
+    out = {}
+    for name, t in arrays.items():
+        shape = [int(d) for d in t.shape]
+        rng = np.random.RandomState(seed)
+        if total <= limit_bytes:
+            part, kept = t, {"part": "all"}
+        else:
+            n = shape[0]
+            per_image = int(t[0].numel())
+            if per_image <= share:
+                idx = np.sort(rng.choice(n, min(n, share // per_image), replace=False))
+                part, kept = t[idx.tolist()], {"part": "images", "images": idx.tolist()}
+            else:
+                img = int(rng.randint(n))
+                per_row = per_image // shape[1]
+                if per_row > share:
+                    raise ValueError("--dump-outputs: one row of %r is over the %d-byte limit"
+                                     % (name, limit_bytes))
+                rows = np.sort(rng.choice(shape[1], share // per_row, replace=False))
+                part = t[img][rows.tolist()]
+                kept = {"part": "rows of one image", "image": img, "rows": rows.tolist()}
+        kept.update({"shape": shape, "dtype": str(t.dtype).replace("torch.", "")})
+        out[name] = (part.float().cpu().numpy(), kept)
+    return out
+
+
+def dump_outputs(path, wl, args, world):
+    """--dump-outputs: DIR/<name>.npy for every output of the last timed step, DIR/manifest.json."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    manifest = {"config": args.config, "batch_per_gpu": wl.n, "height": wl.h, "width": wl.w,
+                "steps": args.steps, "warmup": args.warmup, "rank": 0, "n_gpus": world,
+                "limit_bytes": DUMP_LIMIT_BYTES, "sample_seed": DUMP_SEED, "outputs": {}}
+    for name, (arr, kept) in sample_outputs(wl.outputs()).items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+        kept["file"] = name + ".npy"
+        manifest["outputs"][name] = kept
+    with open(os.path.join(path, "manifest.json"), "w") as fh:
+        json.dump(manifest, fh, indent=1)
 
 
 def committed_traffic(n, h, w):
@@ -768,6 +845,10 @@ def run_rank(args):
     # must not hide behind the max
     per_rank_ms = sharding.gather_scalars(kernel_ms if kernel_ms is not None
                                           else elapsed / args.steps * 1e3, world, device=device)
+    if rank == 0 and args.dump_outputs:
+        # before the secondary launches below, which reuse the step's output buffer
+        dump_outputs(args.dump_outputs, wl, args, world)
+    wl.last = None
 
     extras = {}
     clock_mhz = None

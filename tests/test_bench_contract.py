@@ -137,7 +137,9 @@ def test_scale_report_tabulates_the_curve(tmp_path, monkeypatch):
     for key in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         monkeypatch.delenv(key, raising=False)
     out = tmp_path / "scale.json"
-    doc = mod.main(["--gpus", "1,2", "--steps", "2", "--warmup", "0", "--batch", "2",
+    # ten 10 ms stub steps: the fixed cost of the two gloo barriers around the timed region stays
+    # small beside them on a loaded machine (two steps measured 1.35x)
+    doc = mod.main(["--gpus", "1,2", "--steps", "10", "--warmup", "0", "--batch", "2",
                     "--out", str(out)])
     assert [c["n_gpus"] for c in doc["curve"]] == [1, 2] and doc["skipped"] == []
     assert doc["curve"][0]["ratio_to_one_gpu"] == 1.0
@@ -191,3 +193,48 @@ def test_flat_guide_is_seeded_voronoi_cells():
     assert 2 <= runs <= 40
     coarse = len(np.unique((a // 8).reshape(-1, 3), axis=0))
     assert 50 <= coarse <= 2000 * 8                                    # hundreds of cells, not a posterised scene
+
+
+def test_output_sample_is_whole_or_seeded_and_capped():
+    """--dump-outputs: all of an output that fits, else a seeded choice of whole images (or rows of
+    one image) within the byte limit, as float32, the same choice every time for the same shapes."""
+    import torch
+    gen = torch.Generator().manual_seed(3)
+    a = torch.randint(0, 256, (6, 5, 4, 3), generator=gen, dtype=torch.uint8)
+    b = torch.randint(0, 256, (6, 5, 8), generator=gen, dtype=torch.uint8)
+    whole = bench.sample_outputs({"a": a, "b": b})
+    assert whole["a"][1]["part"] == "all" and whole["a"][0].dtype == np.float32
+    assert np.array_equal(whole["a"][0], a.numpy().astype(np.float32))
+    assert whole["b"][1] == {"part": "all", "shape": [6, 5, 8], "dtype": "uint8"}
+
+    limit = 2 * 4 * (2 * 60 + 1)          # two arrays: 2 images of `a` (60 values) fit each share
+    s1, s2 = bench.sample_outputs({"a": a, "b": b}, limit), bench.sample_outputs({"a": a, "b": b}, limit)
+    assert sum(v[0].nbytes for v in s1.values()) <= limit
+    ka = s1["a"][1]
+    assert ka["part"] == "images" and ka["shape"] == [6, 5, 4, 3] and len(ka["images"]) == 2
+    assert ka["images"] == sorted(ka["images"]) and ka == s2["a"][1]
+    assert np.array_equal(s1["a"][0], a.numpy()[ka["images"]].astype(np.float32))
+    kb = s1["b"][1]
+    assert kb["part"] == "images" and len(kb["images"]) == 3            # 40 values per image
+    assert np.array_equal(s1["b"][0], b.numpy()[kb["images"]].astype(np.float32))
+
+    rows = bench.sample_outputs({"a": a}, 4 * 12 * 3)      # 3 rows of 12 values, less than an image
+    kr = rows["a"][1]
+    assert kr["part"] == "rows of one image" and len(kr["rows"]) == 3
+    assert np.array_equal(rows["a"][0], a.numpy()[kr["image"]][kr["rows"]].astype(np.float32))
+    assert rows["a"][0].nbytes <= 4 * 12 * 3
+
+
+def test_bench_dump_outputs_flag_and_steps(tmp_path):
+    """The flag reaches rank 0 and leaves a manifest (the stub step returns nothing); --steps is the
+    number of timed steps and must be positive."""
+    import json
+    dump = tmp_path / "out"
+    rc, out, err = _run_bench(["--steps", "4", "--warmup", "0", "--batch", "2", "--height", "8",
+                               "--width", "16", "--cpu-seconds", "0", "--dump-outputs", str(dump)], {})
+    assert rc == 0, err[-2000:]
+    assert out["steps"] == 4 and out["ms_per_step"] >= 10.0
+    doc = json.loads((dump / "manifest.json").read_text())
+    assert doc["steps"] == 4 and doc["outputs"] == {} and doc["limit_bytes"] == 64 << 20
+    rc, out, err = _run_bench(["--steps", "0"], {})
+    assert rc != 0 and out is None and "--steps" in err

@@ -145,3 +145,48 @@ def test_c5_full_shard_128_images(env):
     del out, guide, src
     rf.ops.release_workspaces()
     torch.cuda.empty_cache()
+
+
+def _bench_dump(out_dir, *extra):
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for key in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "RF_BENCH_STUB"):
+        env.pop(key, None)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1",
+           "--cpu-seconds", "0", "--no-extras", "--traffic", "off",
+           "--dump-outputs", str(out_dir)] + list(extra)
+    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and json.loads(lines[0])["steps"] == 2
+    with open(os.path.join(str(out_dir), "manifest.json")) as fh:
+        return json.load(fh)
+
+
+def test_bench_dump_outputs_are_the_timed_results(env, tmp_path):
+    """bench.py --dump-outputs: the same arguments give the same inputs and so the same arrays, and
+    they are what the timed call returns for bench.py's seeded inputs (rank 0: seed 1234 + 2000)."""
+    rf, co, torch, bench = env
+    shape = ["--batch", "3", "--height", "72", "--width", "104"]
+    m1 = _bench_dump(tmp_path / "a", *shape)
+    m2 = _bench_dump(tmp_path / "b", *shape)
+    assert m1 == m2 and list(m1["outputs"]) == ["filtered"]
+    assert m1["outputs"]["filtered"] == {"part": "all", "shape": [3, 72, 104, 3], "dtype": "uint8",
+                                         "file": "filtered.npy"}
+    a = np.load(str(tmp_path / "a" / "filtered.npy"))
+    assert a.dtype == np.float32 and np.array_equal(a, np.load(str(tmp_path / "b" / "filtered.npy")))
+    dev = torch.device("cuda", 0)
+    joint, src = bench.synth_batch(torch, 3, 72, 104, 1234 + 2000, dev)
+    want = rf.ops.joint_bilateral_u8(joint, src, -1, 20.0, 22.0)
+    assert np.array_equal(a, want.cpu().numpy().astype(np.float32))
+    # the chain hands back two arrays
+    mc = _bench_dump(tmp_path / "c", "--config", "c3", "--batch", "2", "--height", "40", "--width", "56")
+    assert list(mc["outputs"]) == ["reflectance_u8", "filtered"]
+    r8, filt = rf.decompose_and_filter_batch(bench.synth_batch(torch, 2, 40, 56, 1234 + 2000, dev)[0])
+    for name, t in (("reflectance_u8", r8), ("filtered", filt)):
+        assert np.array_equal(np.load(str(tmp_path / "c" / (name + ".npy"))),
+                              t.cpu().numpy().astype(np.float32))

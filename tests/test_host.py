@@ -95,15 +95,66 @@ def test_caffe_blob_helpers():
         assert str(e.value) == str(msg)
 
 
-def test_caffemodel_decoder_and_shipped_weights():
+def _pb_varint(v):
+    out = bytearray()
+    while True:
+        b = v & 0x7F
+        v >>= 7
+        out.append(b | (0x80 if v else 0))
+        if not v:
+            return bytes(out)
+
+
+def _pb_field(field, wtype, payload):
+    key = _pb_varint(field << 3 | wtype)
+    if wtype == 2:
+        return key + _pb_varint(len(payload)) + payload
+    return key + payload
+
+
+def _pb_blob(arr, packed=True):
+    """BlobProto: shape = 7 {dim = 1, packed}, data = 5 (packed float, or repeated fixed32)."""
+    dims = b"".join(_pb_varint(d) for d in arr.shape)
+    body = _pb_field(7, 2, _pb_field(1, 2, dims))
+    flat = np.ascontiguousarray(arr, dtype="<f4").reshape(-1)
+    if packed:
+        body += _pb_field(5, 2, flat.tobytes())
+    else:
+        body += b"".join(_pb_field(5, 5, flat[i:i + 1].tobytes()) for i in range(flat.size))
+    return body
+
+
+def _caffemodel_bytes(flat):
+    """A NetParameter (layer = 100; name = 1, blobs = 7) holding `flat` in the decoder's layout,
+    with a blob-less input layer and an unrelated field in front, as Caffe writes them."""
+    msg = _pb_field(1, 2, b"ReflectanceNet")
+    msg += _pb_field(100, 2, _pb_field(1, 2, b"data") + _pb_field(2, 2, b"Input"))
+    pos = 0
+    for i, name in enumerate(rf.weights.CONV_LAYERS):
+        wshape, bshape = rf.weights._EXPECTED_SHAPES[name]
+        nw, nb = int(np.prod(wshape)), int(np.prod(bshape))
+        wgt = flat[pos:pos + nw].reshape(wshape)
+        bias = flat[pos + nw:pos + nw + nb].reshape(bshape)
+        pos += nw + nb
+        layer = _pb_field(1, 2, name.encode()) + _pb_field(2, 2, b"Convolution")
+        layer += _pb_field(7, 2, _pb_blob(wgt, packed=i != 1)) + _pb_field(7, 2, _pb_blob(bias))
+        msg += _pb_field(100, 2, layer)
+    assert pos == flat.size
+    return msg
+
+
+def test_caffemodel_decoder_and_shipped_weights(tmp_path):
     g = np.load(os.path.join(G, "cnn_forward.npz"))
     shipped = rf.weights.load_weights()
     assert shipped.dtype == np.float32 and np.array_equal(shipped, g["weights"])
-    ref_model = "/root/reference/learned_weights.caffemodel"
-    if os.path.exists(ref_model):  # only in the build container
-        assert np.array_equal(rf.weights.load_weights(ref_model), shipped)
-        layers = rf.weights.read_caffemodel(ref_model)
-        assert set(rf.weights.CONV_LAYERS) <= set(layers)
+    # the decoder on a NetParameter encoded here from the shipped weights (packed and unpacked
+    # float data, a layer without blobs, fields it must skip)
+    model = tmp_path / "learned_weights.caffemodel"
+    model.write_bytes(_caffemodel_bytes(shipped))
+    assert np.array_equal(rf.weights.load_weights(str(model)), shipped)
+    layers = rf.weights.read_caffemodel(str(model))
+    assert set(layers) == set(rf.weights.CONV_LAYERS)
+    assert layers["conv1"][0].shape == (32, 32, 1, 1) and layers["fuse_skip_layers"][1].shape == (1,)
 
 
 def test_reflectance_net_blob_to_bytes_roundtrip():
