@@ -100,6 +100,27 @@ int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, int n, int 
              size_t workspace_bytes, void *stream);
 
 /*
+ * Guided filter, 8-bit, with flags.  flags == 0 is rf_gf_u8 (the same results and the same
+ * refusals).
+ *   RF_GF_GREY_AS_BGR  guide is n*h*w*1 (guide_cn must be 1, src_cn 1 or 3): each guide byte stands
+ *     for three equal channels, i.e. what cv2.imread makes of a grey PNG such as the CNN's `-r.png`
+ *     - the reference tool's GF(CNN, CNN) recipe (its filter_reflectance.py:135-137).  The result is
+ *     byte for byte rf_gf_u8 on the guide replicated to 3 channels; the grey guide is read at one
+ *     byte per pixel and stage 1 box-sums 2 + 2 x src_cn quantities instead of 9 + 4 x src_cn.
+ *     This is NOT cv2.ximgproc.guidedFilter on a 1-channel guide: for one guide channel OpenCV
+ *     inverts var + eps as a scalar, whereas three equal channels with eps*I on the diagonal go
+ *     through the 3x3 inverse (and its small-eps determinant rule) - different floats.  Only the
+ *     second is implemented.
+ *   Refused: guide_cn == 3 with the flag and any unknown flag bit (RF_E_BADARG); guide_cn == 1
+ *   without the flag (RF_E_UNSUPPORTED, as rf_gf_u8).  The workspace is sized by
+ *   rf_gf_workspace_bytes as for a colour guide (a grey guide needs no more).
+ */
+#define RF_GF_GREY_AS_BGR 1
+int rf_gf_ex_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, int n, int h, int w,
+                int guide_cn, int src_cn, int radius, double eps, int iterations, int flags,
+                void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * 1x1 CNN reflectance predictor on uint8 BGR images.
  * Replaces  caffe.Net(network_definition.prototxt, TEST, weights=learned_weights.caffemodel),
  * blobs['images'] <- imgCV2_to_caffeBlob(image), forward(), blobs['reflectance_intensity']

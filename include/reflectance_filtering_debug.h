@@ -63,6 +63,10 @@
  *   "gf_cw_chan_run"     guided filter, colour src, passes of an iterated call that hand their result on as
  *                        planes: n + 1 = the column walk takes an XCD's (block, channel) items in runs of n
  *                        blocks per channel (0 = the library's choice, 64; 1 = channel fastest); identical bytes
+ *
+ * The grey-guide form of the guided filter (rf_gf_ex_u8 with RF_GF_GREY_AS_BGR) has no stage 1 for
+ * "gf_guide_cache" and "gf_exact": while either is set, such a call returns RF_E_UNSUPPORTED.  Every
+ * other switch above applies to it as to a colour guide.
  */
 #ifndef REFLECTANCE_FILTERING_DEBUG_H
 #define REFLECTANCE_FILTERING_DEBUG_H

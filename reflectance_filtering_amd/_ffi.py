@@ -21,11 +21,12 @@ BORDER_DEFAULT = BORDER_REFLECT_101
 JBF_TRUE_DIVISION = 1
 JBF_FORCE_GENERIC = 2
 JBF_GREY_AS_BGR = 4
+GF_GREY_AS_BGR = 1          # rf_gf_ex_u8: a 1-channel guide stands for three equal channels
 CNN_NPARAMS = 4513
 CNN_NPACKED = 4673          # RF_CNN_NPACKED: floats of rf_cnn_pack_weights' output
 
 EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_workspace_bytes",
-           "rf_gf_u8", "rf_cnn_reflectance_u8", "rf_cnn_pack_weights",
+           "rf_gf_u8", "rf_gf_ex_u8", "rf_cnn_reflectance_u8", "rf_cnn_pack_weights",
            "rf_cnn_reflectance_packed_u8", "rf_colorize_workspace_bytes",
            "rf_colorize_srgb_u8", "rf_whdr_f32", "rf_jbf_f32_workspace_bytes", "rf_jbf_f32",
            "rf_gf_f32_workspace_bytes", "rf_gf_f32")
@@ -71,6 +72,8 @@ def load_library():
         lib.rf_gf_workspace_bytes.restype = sz
         lib.rf_gf_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, vp, sz, vp]
         lib.rf_gf_u8.restype = ci
+        lib.rf_gf_ex_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, vp, sz, vp]
+        lib.rf_gf_ex_u8.restype = ci
         lib.rf_cnn_reflectance_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
         lib.rf_cnn_reflectance_u8.restype = ci
         lib.rf_cnn_pack_weights.argtypes = [vp, vp, vp]

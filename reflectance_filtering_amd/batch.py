@@ -161,6 +161,12 @@ def filter_files(filter_type, inputs, guidance_pattern, sigma_color, sigma_spati
                 for _ in range(iterations):
                     out = ops.joint_bilateral_u8(joints, out, -1, sigma_color, sigma_spatial,
                                                  grey_as_bgr=True)
+            elif filter_type == "guided" and _is_grey(guis):
+                # grey guidance (GF(CNN, CNN)): uploaded as one byte per pixel, read as three equal
+                # channels by the grey-guide kernels - identical bytes
+                joints = torch.from_numpy(np.ascontiguousarray(guis[..., :1])).cuda()
+                out = fr.apply_filter_batch(filter_type, images, joints, sigma_color,
+                                            sigma_spatial, iterations=iterations, grey_as_bgr=True)
             else:
                 joints = torch.from_numpy(guis).cuda()
                 out = fr.apply_filter_batch(filter_type, images, joints, sigma_color,

@@ -51,8 +51,23 @@ namespace {
 // strips cover 3840 columns exactly, but five waves per workgroup load the four SIMDs unevenly
 // between barriers) 5.04 ms against 4.95; 512 x 1 at 80 registers (24 waves per CU, a fifth
 // more scan work per pixel) 5.56 ms.
-constexpr int stage1_threads(int) { return 256; }
-constexpr int stage1_cols(int scn) { return scn == 1 ? 3 : 2; }
+// Grey guide (RF_GF_GREY_AS_BGR, QuantGrey): 2 + 2 x SCN quantities, so the prefix sums would leave
+// room for wider strips.  Measured (8 x 4K, radius 52 / 45): one src channel 3 / 6 / 8 columns per
+// thread 1.35 / 1.39 / 1.45 ms per pass, three src channels 3 / 4 mixed (+2 % / -7 %): the scan work
+// wide strips save does not pay for fewer, longer workgroups - 256 x 3 (profiles/r07_gf_grey_guide.md).
+// (-DRF_GF_GREY_S1_COLS1 / -DRF_GF_GREY_S1_COLS3: other widths for such A/B builds)
+#ifndef RF_GF_GREY_S1_COLS1
+#define RF_GF_GREY_S1_COLS1 3
+#endif
+#ifndef RF_GF_GREY_S1_COLS3
+#define RF_GF_GREY_S1_COLS3 3
+#endif
+constexpr int stage1_threads(int, bool = false) { return 256; }
+constexpr int stage1_cols(int scn, bool grey = false)
+{
+    return grey ? (scn == 1 ? RF_GF_GREY_S1_COLS1 : RF_GF_GREY_S1_COLS3) : (scn == 1 ? 3 : 2);
+}
+constexpr int stage1_nq(int scn, bool grey) { return grey ? 2 + 2 * scn : 9 + 4 * scn; }
 
 // Stage-1 quantities.  GUIDE = true: all of them, q: 0..2 I_g | 3..8 I_aI_b (00 01 02 11 12 22) |
 // 9.. p_s | then p_s*I_g (s major).  GUIDE = false (later passes of an iterated call, whose guide
@@ -87,6 +102,48 @@ struct Quant {
             acc[G0 + SCN + 3 * s + 0] += (uint32_t)(ps * g0);
             acc[G0 + SCN + 3 * s + 1] += (uint32_t)(ps * g1);
             acc[G0 + SCN + 3 * s + 2] += (uint32_t)(ps * g2);
+        }
+    }
+};
+
+// Grey guide (RF_GF_GREY_AS_BGR): one guide byte I per pixel stands for three equal channels
+// I_0 = I_1 = I_2 = I.  Of the quantities of Quant<SCN> only I, I*I, p_s and p_s*I are distinct, the
+// rest are copies: q: 0 I | 1 I*I | 2.. p_s | then p_s*I.  Their window sums are the integers the
+// 9 + 4*SCN sums of the replicated guide hold, so their means are the same floats; expand() lays
+// them out in the order of Quant<SCN> and the unchanged algebra runs on that - the same float
+// operations on the same operands, including the small-eps determinant branch, which a grey guide
+// takes often (det = eps^2 (3 var + eps)).
+template <int SCN>
+struct QuantGrey {
+    static constexpr int NQ = 2 + 2 * SCN;
+    static constexpr int NFULL = 9 + 4 * SCN;  // entries of the expanded mean vector
+    template <bool NEG>
+    __device__ static inline void accumulate(int g, const int *p, uint32_t *acc)
+    {
+        const int sg = NEG ? -g : g;
+        acc[0] += (uint32_t)sg;
+        acc[1] += (uint32_t)(sg * g);
+#pragma unroll
+        for (int s = 0; s < SCN; s++) {
+            const int ps = NEG ? -p[s] : p[s];
+            acc[2 + s] += (uint32_t)ps;
+            acc[2 + SCN + s] += (uint32_t)(ps * g);
+        }
+    }
+    __device__ static inline void expand(const float *m, float *full)
+    {
+#pragma unroll
+        for (int g = 0; g < 3; g++)
+            full[g] = m[0];
+#pragma unroll
+        for (int e = 3; e < 9; e++)
+            full[e] = m[1];
+#pragma unroll
+        for (int s = 0; s < SCN; s++) {
+            full[9 + s] = m[2 + s];
+#pragma unroll
+            for (int g = 0; g < 3; g++)
+                full[9 + SCN + 3 * s + g] = m[2 + SCN + s];
         }
     }
 };
@@ -380,8 +437,10 @@ __device__ unsigned long long g_s1_stamps[16];
 #endif
 // (waves per SIMD: the one-channel kernel is built for four - 128 registers -, which the exact-row
 //  additions would otherwise miss by one register; the three-channel kernel for three)
-template <int SCN, int SPX, int MODE, bool EXACT = false>
-__global__ __launch_bounds__(stage1_threads(SCN))
+// GREY: the guide is one byte per pixel standing for three equal channels (QuantGrey; plain stage 1
+// only, MODE = kS1Full and no exact rows).
+template <int SCN, int SPX, int MODE, bool EXACT = false, bool GREY = false>
+__global__ __launch_bounds__(stage1_threads(SCN, GREY))
     __attribute__((amdgpu_waves_per_eu(SCN == 1 ? 4 : 3))) void gf_stage1_kernel(
     const uint8_t *__restrict__ guide, const uint8_t *__restrict__ src, float *__restrict__ ab,
     int h, int w, int radius, float eps_f, int eps_small, int seg_rows,
@@ -391,6 +450,7 @@ __global__ __launch_bounds__(stage1_threads(SCN))
     // src_planar (three-channel kernel, later passes of an iterated call): the src channels as three
     // planes [img][3][h][w] - what the previous pass's column walk left - instead of interleaved
     static_assert(!EXACT || MODE == kS1Full, "exact rows: plain stage 1 only");
+    static_assert(!GREY || (MODE == kS1Full && !EXACT), "grey guide: plain stage 1 only");
     // hl, out_w: the strip's geometry - its kACW columns are image columns xs - hl .. xs - hl + kACW - 1
     // (xs = strip index x out_w), of which columns hl .. hl + out_w - 1 are its outputs; hl >= radius
     // and kACW - hl - out_w >= radius (rf_gf_u8 picks them, see gf_strip_geometry)
@@ -398,10 +458,11 @@ __global__ __launch_bounds__(stage1_threads(SCN))
     // image is read from its one-byte-per-pixel intermediate (SPX = 1, see rf_gf_u8)
     if (wrong_variant<SCN>(colour, blockIdx.z))
         return;
-    using Q = Quant<SCN, MODE != kS1Reuse>;
+    using Q = std::conditional_t<GREY, QuantGrey<SCN>, Quant<SCN, MODE != kS1Reuse>>;
     constexpr int NQ = Q::NQ;
-    constexpr int kAThreads = stage1_threads(SCN), kAWaves = kAThreads / 64;
-    constexpr int kACols = stage1_cols(SCN);
+    constexpr int kGCN = GREY ? 1 : 3;  // guide bytes per pixel
+    constexpr int kAThreads = stage1_threads(SCN, GREY), kAWaves = kAThreads / 64;
+    constexpr int kACols = stage1_cols(SCN, GREY);
     constexpr int kACW = kAThreads * kACols;
     __shared__ uint32_t pfx[NQ][kACW + 1];
     __shared__ uint32_t wave_acc[NQ][kAWaves];
@@ -412,7 +473,7 @@ __global__ __launch_bounds__(stage1_threads(SCN))
     const int ys = blockIdx.y * seg_rows;
     const int ye = min(ys + seg_rows, h);
     const size_t npx = (size_t)h * w;
-    const uint8_t *gimg = guide + (size_t)blockIdx.z * npx * 3;
+    const uint8_t *gimg = guide + (size_t)blockIdx.z * npx * kGCN;
     const uint8_t *simg = src + (size_t)blockIdx.z * npx * SPX;
     float *abimg = ab + (size_t)blockIdx.z * npx * (ab_groups * 4);
     float *gsimg = MODE == kS1Full ? nullptr : gs + (size_t)blockIdx.z * npx * kGsFloats;
@@ -420,7 +481,7 @@ __global__ __launch_bounds__(stage1_threads(SCN))
     const double scale = 1.0 / (double)(ks * ks);
     const double nbias = -(4503599627370496.0 * scale);
 
-    // byte offsets of the thread's columns within an image row (guide: 3 bytes per pixel, src: SPX);
+    // byte offsets of the thread's columns within an image row (guide: kGCN bytes per pixel, src: SPX);
     // a row's bytes are then (wave-uniform row pointer) + (32-bit lane offset): no 64-bit vector
     // arithmetic per load
     const bool planar = SCN == 3 && src_planar != nullptr;
@@ -429,7 +490,7 @@ __global__ __launch_bounds__(stage1_threads(SCN))
 #pragma unroll
     for (int k = 0; k < kACols; k++) {
         const int gx = border_interpolate(xs - hl + tid * kACols + k, w, RF_BORDER_REFLECT);
-        gx3[k] = (uint32_t)gx * 3u;
+        gx3[k] = (uint32_t)gx * (uint32_t)kGCN;
         gxs[k] = planar ? (uint32_t)gx : (uint32_t)gx * (uint32_t)SPX;
     }
 
@@ -450,7 +511,7 @@ __global__ __launch_bounds__(stage1_threads(SCN))
         constexpr bool NEG = decltype(neg_c)::value;
         const int gy = border_interpolate(yy, h, RF_BORDER_REFLECT);
         const auto rg = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t *>(gimg + (size_t)gy * w * 3), 0, w * 3, 0x00020000);
+            const_cast<uint8_t *>(gimg + (size_t)gy * w * kGCN), 0, w * kGCN, 0x00020000);
         // (planar: one descriptor over the three planes' common row offset .. the last plane's row,
         //  channel sc at byte sc * npx + column; interleaved: the row's w * SPX bytes)
         const auto rp = __builtin_amdgcn_make_buffer_rsrc(
@@ -459,13 +520,21 @@ __global__ __launch_bounds__(stage1_threads(SCN))
         const int pstep = planar ? (int)npx : 1;
 #pragma unroll
         for (int k = 0; k < kACols; k++) {
-            const uint32_t g01 = __builtin_amdgcn_raw_buffer_load_b16(rg, (int)gx3[k], 0, 0);
-            const int g2 = __builtin_amdgcn_raw_buffer_load_b8(rg, (int)gx3[k] + 2, 0, 0);
             int p[SCN];
+            if constexpr (GREY) {
+                const int g = __builtin_amdgcn_raw_buffer_load_b8(rg, (int)gx3[k], 0, 0);
 #pragma unroll
-            for (int sc = 0; sc < SCN; sc++)
-                p[sc] = __builtin_amdgcn_raw_buffer_load_b8(rp, (int)gxs[k], sc * pstep, 0);
-            Q::template accumulate<NEG>((int)(g01 & 0xffu), (int)(g01 >> 8), g2, p, V[k]);
+                for (int sc = 0; sc < SCN; sc++)
+                    p[sc] = __builtin_amdgcn_raw_buffer_load_b8(rp, (int)gxs[k], sc * pstep, 0);
+                Q::template accumulate<NEG>(g, p, V[k]);
+            } else {
+                const uint32_t g01 = __builtin_amdgcn_raw_buffer_load_b16(rg, (int)gx3[k], 0, 0);
+                const int g2 = __builtin_amdgcn_raw_buffer_load_b8(rg, (int)gx3[k] + 2, 0, 0);
+#pragma unroll
+                for (int sc = 0; sc < SCN; sc++)
+                    p[sc] = __builtin_amdgcn_raw_buffer_load_b8(rp, (int)gxs[k], sc * pstep, 0);
+                Q::template accumulate<NEG>((int)(g01 & 0xffu), (int)(g01 >> 8), g2, p, V[k]);
+            }
         }
     };
     using RowIn = std::integral_constant<bool, false>;
@@ -620,7 +689,13 @@ __global__ __launch_bounds__(stage1_threads(SCN))
             for (int q = 0; q < NQ; q++)
                 m[q] = mean_of(pfx[q][c + radius + 1] - pfx[q][c - radius], scale, nbias);
             float ab_px[4 * SCN];
-            if (MODE == kS1Reuse) {
+            if constexpr (GREY) {
+                float mf[QuantGrey<SCN>::NFULL];
+                QuantGrey<SCN>::expand(m, mf);
+                float gsn[kGsFloats];
+                gf_guide_algebra(mf, eps_f, eps_small, gsn);
+                gf_src_algebra<SCN>(gsn, mf + 9, ab_px);
+            } else if (MODE == kS1Reuse) {
                 gf_src_algebra<SCN>(gsr[k], m, ab_px);
             } else {
                 float gsn[kGsFloats];
@@ -800,10 +875,11 @@ __global__ __launch_bounds__(64) void gf_rowsum_kernel(const float *__restrict__
 // thread of that channel forms q = beta + a0*I0 + a1*I1 + a2*I2 and stores the byte.
 // ------------------------------------------------------------------------------------------
 // T = uint8_t (result rounded and saturated) or float (the CV_32F variant: result stored as is)
+// gcn: guide values per pixel, 3, or 1 for a grey guide standing for three equal channels
 template <int SCN, int SPX, typename T = uint8_t>
 __global__ __launch_bounds__(64 * 4 * SCN) void gf_colsum_apply_kernel(
     const double *__restrict__ rowsums, const T *__restrict__ guide, T *__restrict__ dst, int h,
-    int w, int radius, const int *__restrict__ colour)
+    int w, int radius, const int *__restrict__ colour, int gcn)
 {
     if (wrong_variant<SCN>(colour, blockIdx.z))
         return;
@@ -817,8 +893,9 @@ __global__ __launch_bounds__(64 * 4 * SCN) void gf_colsum_apply_kernel(
     const int xc = min(x, w - 1);
     const size_t npx = (size_t)h * w;
     const double *R = rowsums + ((size_t)blockIdx.z * (4 * SPX) + plane) * npx + xc;
-    const T *gimg = guide + (size_t)blockIdx.z * npx * 3;
+    const T *gimg = guide + (size_t)blockIdx.z * npx * gcn;
     T *dimg = dst + (size_t)blockIdx.z * npx * SPX;
+    const int gstep = gcn == 3 ? 1 : 0;  // a grey guide's one value serves all three channels
     const int ks = 2 * radius + 1;
     const double scale = 1.0 / (double)(ks * ks);
 
@@ -850,7 +927,7 @@ __global__ __launch_bounds__(64 * 4 * SCN) void gf_colsum_apply_kernel(
 #pragma unroll
                 for (int g = 0; g < 3; g++)
                     q = __fadd_rn(q, __fmul_rn(means[y & 1][s * 4 + g][lane],
-                                               (float)gimg[pix * 3 + g]));
+                                               (float)gimg[pix * gcn + g * gstep]));
                 T o;
                 if constexpr (sizeof(T) == 1)
                     o = saturate_u8(q);
@@ -976,7 +1053,7 @@ int gf_f32_chunk(const float *guide, const float *src, float *dst, int m, int h,
                            (const int *)nullptr, NQ);
         hipLaunchKernelGGL((gf_colsum_apply_kernel<SCN, SCN, float>), dim3(ceil_div(w, 64), 1, m),
                            dim3(64, 4 * SCN), 0, stream, rows, guide, dst, h, w, radius,
-                           (const int *)nullptr);
+                           (const int *)nullptr, 3);
     }
     return RF_OK;
 }
@@ -988,6 +1065,18 @@ __global__ __launch_bounds__(256) void gf_u8_to_f32_kernel(const uint8_t *__rest
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
          i += (size_t)gridDim.x * blockDim.x)
         out[i] = (float)in[i];
+}
+// ... and a grey guide (one byte per pixel) into the three equal float channels the float kernels take
+__global__ __launch_bounds__(256) void gf_u8_grey_to_f32x3_kernel(const uint8_t *__restrict__ in,
+                                                                  float *__restrict__ out, size_t count)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
+         i += (size_t)gridDim.x * blockDim.x) {
+        const float v = (float)in[i];
+        out[3 * i + 0] = v;
+        out[3 * i + 1] = v;
+        out[3 * i + 2] = v;
+    }
 }
 __global__ __launch_bounds__(256) void gf_f32_to_u8_kernel(const float *__restrict__ in,
                                                            uint8_t *__restrict__ out, size_t count)
@@ -1222,33 +1311,49 @@ extern "C" int rf_gf_f32(const float *guide, const float *src, float *dst, int n
                          int guide_cn, int src_cn, int radius, double eps, int iterations,
                          void *workspace, size_t workspace_bytes, void *stream_);
 
-extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, int n, int h,
-                        int w, int guide_cn, int src_cn, int radius, double eps, int iterations,
-                        void *workspace, size_t workspace_bytes, void *stream_)
+namespace {
+// rf_gf_u8 and rf_gf_ex_u8 (`fn`: the entry point named in error messages)
+int gf_u8_entry(const char *fn, const uint8_t *guide, const uint8_t *src, uint8_t *dst, int n, int h,
+                int w, int guide_cn, int src_cn, int radius, double eps, int iterations, int flags,
+                void *workspace, size_t workspace_bytes, void *stream_)
 {
     using namespace rf;
+    if (flags & ~RF_GF_GREY_AS_BGR)
+        return fail(RF_E_BADARG, "%s: unknown flag bits 0x%x", fn, (unsigned)(flags & ~RF_GF_GREY_AS_BGR));
     if (n == 0)  // an empty batch is valid whatever the (possibly NULL) pointers are
         return RF_OK;
     if (!guide || !src || !dst || !workspace)
-        return fail(RF_E_BADARG, "rf_gf_u8: NULL pointer");
+        return fail(RF_E_BADARG, "%s: NULL pointer", fn);
     if (n < 0 || h <= 0 || w <= 0 || iterations < 1)
-        return fail(RF_E_BADARG, "rf_gf_u8: bad size n=%d h=%d w=%d iterations=%d", n, h, w,
+        return fail(RF_E_BADARG, "%s: bad size n=%d h=%d w=%d iterations=%d", fn, n, h, w,
                     iterations);
-    if (guide_cn != 3)
-        return fail(RF_E_UNSUPPORTED, "rf_gf_u8: guide must have 3 channels (got %d)", guide_cn);
+    // a grey guide (RF_GF_GREY_AS_BGR): one byte per pixel that stands for three equal channels
+    const bool grey = (flags & RF_GF_GREY_AS_BGR) != 0;
+    if (grey && guide_cn == 3)
+        return fail(RF_E_BADARG, "%s: RF_GF_GREY_AS_BGR takes a 1-channel guide (got 3 channels)", fn);
+    if (grey && guide_cn != 1)
+        return fail(RF_E_UNSUPPORTED, "%s: RF_GF_GREY_AS_BGR takes a 1-channel guide (got %d)", fn,
+                    guide_cn);
+    if (!grey && guide_cn != 3)
+        return fail(RF_E_UNSUPPORTED, "%s: guide must have 3 channels (got %d)", fn, guide_cn);
+    const int gcn = grey ? 1 : 3;  // guide bytes per pixel
     if (src_cn != 1 && src_cn != 3)
-        return fail(RF_E_UNSUPPORTED, "rf_gf_u8: src channels must be 1 or 3 (got %d)", src_cn);
+        return fail(RF_E_UNSUPPORTED, "%s: src channels must be 1 or 3 (got %d)", fn, src_cn);
     if (radius < 0 || radius > 4096)
-        return fail(RF_E_UNSUPPORTED, "rf_gf_u8: radius %d outside 0..4096", radius);
+        return fail(RF_E_UNSUPPORTED, "%s: radius %d outside 0..4096", fn, radius);
     if (w >= (1 << 27))  // the kernels address a row's alpha/beta (16 B per pixel) with 32-bit offsets
-        return fail(RF_E_UNSUPPORTED, "rf_gf_u8: width %d beyond 2^27 - 1", w);
+        return fail(RF_E_UNSUPPORTED, "%s: width %d beyond 2^27 - 1", fn, w);
     {
         const size_t px = (size_t)n * h * w;
-        if (ranges_overlap(dst, px * src_cn, guide, px * 3))
-            return fail(RF_E_BADARG, "rf_gf_u8: dst must not overlap guide");
+        if (ranges_overlap(dst, px * src_cn, guide, px * gcn))
+            return fail(RF_E_BADARG, "%s: dst must not overlap guide", fn);
         if (dst != src && ranges_overlap(dst, px * src_cn, src, px * src_cn))
-            return fail(RF_E_BADARG, "rf_gf_u8: dst may equal src but not partially overlap it");
+            return fail(RF_E_BADARG, "%s: dst may equal src but not partially overlap it", fn);
     }
+    // experiments without a grey-guide form (reflectance_filtering_debug.h)
+    if (grey && (debug_get(kDbgGfGuideCache) || debug_get(kDbgGfExact)))
+        return fail(RF_E_UNSUPPORTED, "%s: RF_GF_GREY_AS_BGR has no form for the debug options "
+                    "gf_guide_cache / gf_exact", fn);
     if (n == 0)
         return RF_OK;
     const int np = 4 * src_cn;
@@ -1264,8 +1369,8 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
         // forms, so the bytes are what the 8-bit kernels would give (tested on either side of 128).
         const size_t per_img_f = gf_per_img_via_f32(npx, src_cn);
         if (workspace_bytes < header + per_img_f + kGfF32Slack)
-            return fail(RF_E_WORKSPACE, "rf_gf_u8: workspace %zu B < %zu B needed for one image at "
-                        "radius %d", workspace_bytes, header + per_img_f + kGfF32Slack, radius);
+            return fail(RF_E_WORKSPACE, "%s: workspace %zu B < %zu B needed for one image at "
+                        "radius %d", fn, workspace_bytes, header + per_img_f + kGfF32Slack, radius);
         const size_t f32_ws = npx * (9 + 4 * (size_t)src_cn) * (sizeof(float) + sizeof(double));
         // (kGfF32Slack: the float kernels' scratch starts with double row sums, so the float copies
         //  in front of it are rounded up to 16 bytes - an odd pixel count would leave it 4-aligned)
@@ -1278,11 +1383,15 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
             float *dF = sF + (size_t)m * npx * src_cn;
             const size_t copies = ((size_t)m * npx * (3 + 2 * (size_t)src_cn) * sizeof(float) + 15) & ~(size_t)15;
             void *fw = ws0 + copies;
-            const size_t cg = (size_t)m * npx * 3, cs = (size_t)m * npx * src_cn;
+            const size_t cg = (size_t)m * npx * gcn, cs = (size_t)m * npx * src_cn;
             const unsigned bg = (unsigned)std::min<size_t>((cg + 255) / 256, 65535);
             const unsigned bs = (unsigned)std::min<size_t>((cs + 255) / 256, 65535);
-            hipLaunchKernelGGL(gf_u8_to_f32_kernel, dim3(bg), dim3(256), 0, stream,
-                               guide + (size_t)i0 * npx * 3, gF, cg);
+            if (grey)  // expanded to the three equal channels while copying
+                hipLaunchKernelGGL(gf_u8_grey_to_f32x3_kernel, dim3(bg), dim3(256), 0, stream,
+                                   guide + (size_t)i0 * npx, gF, cg);
+            else
+                hipLaunchKernelGGL(gf_u8_to_f32_kernel, dim3(bg), dim3(256), 0, stream,
+                                   guide + (size_t)i0 * npx * 3, gF, cg);
             uint8_t *d0 = dst + (size_t)i0 * npx * src_cn;
             for (int it = 0; it < iterations; it++) {
                 const uint8_t *s0 = it == 0 ? src + (size_t)i0 * npx * src_cn : d0;
@@ -1315,7 +1424,7 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
     const bool fused = chained || (can_fuse && workspace_bytes >= header + per_img_rw);
     const size_t per_img_fused = chained ? per_img_chained : per_img_rw;
     if (!fused && workspace_bytes < header + per_img)
-        return fail(RF_E_WORKSPACE, "rf_gf_u8: workspace %zu B < %zu B needed for one image",
+        return fail(RF_E_WORKSPACE, "%s: workspace %zu B < %zu B needed for one image", fn,
                     workspace_bytes, header + per_img);
     // EXPERIMENT, off by default (debug option "gf_guide_cache"): iterated calls keep the guide half
     // of the per-pixel algebra (kGsFloats floats per pixel) from the first pass for the later ones,
@@ -1382,7 +1491,7 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
         int hl, out_w, strips;
     };
     auto strip_geometry = [&](int scn) {
-        const int acw = stage1_threads(scn) * stage1_cols(scn);
+        const int acw = stage1_threads(scn, grey) * stage1_cols(scn, grey);
         StripGeom g;
         if (debug_get(kDbgGfS1LegacyStrips)) {
             g.hl = radius;
@@ -1443,8 +1552,11 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
         const size_t want = (size_t)163840 / (s1_cap + 1) + 1536;
         return want > static_lds ? (unsigned)(want - static_lds) : 0u;
     };
-    const unsigned pad1 = s1_pad(sizeof(uint32_t) * (13 * (stage1_threads(1) * stage1_cols(1) + 1) + 13 * 4));
-    const unsigned pad3 = s1_pad(sizeof(uint32_t) * (21 * (stage1_threads(3) * stage1_cols(3) + 1) + 21 * 4));
+    const int nq1 = stage1_nq(1, grey), nq3 = stage1_nq(3, grey);
+    const unsigned pad1 =
+        s1_pad(sizeof(uint32_t) * (nq1 * (stage1_threads(1, grey) * stage1_cols(1, grey) + 1) + nq1 * 4));
+    const unsigned pad3 =
+        s1_pad(sizeof(uint32_t) * (nq3 * (stage1_threads(3, grey) * stage1_cols(3, grey) + 1) + nq3 * 4));
     auto part_setup = [&](Part &P, int m_fill) {
         const int i0 = P.i0, m = P.m;
         char *ws = P.ws;
@@ -1483,7 +1595,7 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
             P.xcount = P.xlist + rows_all;  // [m x groups] lengths, then [m x groups][mask_words] flags
             P.rowmask = reinterpret_cast<unsigned *>(P.xcount + (size_t)m * src_cn);
         }
-        P.g0 = guide + (size_t)i0 * npx * 3;
+        P.g0 = guide + (size_t)i0 * npx * gcn;
         P.d0 = dst + (size_t)i0 * npx * src_cn;
         // Rows per stage-1 segment (m_fill: the images whose stage 1 is in flight on the device
         // together - both halves of a chunk in the aligned schedule, the part alone otherwise).  A
@@ -1574,39 +1686,41 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
             (void)hipFuncSetAttribute((const void *)(K), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                       (int)(PAD));                                                 \
     } while (0)
-#define RF_GF_STAGE1(MODE, EX)                                                                     \
+#define RF_GF_STAGE1(MODE, EX, GR)                                                                     \
     do {                                                                                           \
-        RF_GF_S1_ATTR((gf_stage1_kernel<3, 3, MODE, EX>), pad3);                                   \
-        RF_GF_S1_ATTR((gf_stage1_kernel<1, 1, MODE, EX>), pad1);                                   \
-        RF_GF_S1_ATTR((gf_stage1_kernel<1, 3, MODE, EX>), pad1);                                   \
+        RF_GF_S1_ATTR((gf_stage1_kernel<3, 3, MODE, EX, GR>), pad3);                                   \
+        RF_GF_S1_ATTR((gf_stage1_kernel<1, 1, MODE, EX, GR>), pad1);                                   \
+        RF_GF_S1_ATTR((gf_stage1_kernel<1, 3, MODE, EX, GR>), pad1);                                   \
         if (src_cn == 3) {                                                                         \
-            hipLaunchKernelGGL((gf_stage1_kernel<3, 3, MODE, EX>), ga3, dim3(stage1_threads(3)), pad3, \
+            hipLaunchKernelGGL((gf_stage1_kernel<3, 3, MODE, EX, GR>), ga3, dim3(stage1_threads(3, GR)), pad3, \
                                st, g0, s0, ab, h, w, radius, eps_f, eps_small, seg_rows3, colour,  \
                                gs, 3, geo3.hl, geo3.out_w, xo, it > 0 ? P.cmp3 : nullptr);         \
             if (cmp != nullptr)                                                                    \
-                hipLaunchKernelGGL((gf_stage1_kernel<1, 1, MODE, EX>), ga1, dim3(stage1_threads(1)), \
+                hipLaunchKernelGGL((gf_stage1_kernel<1, 1, MODE, EX, GR>), ga1, dim3(stage1_threads(1, GR)), \
                                    pad1, st, g0, cmp, ab, h, w, radius, eps_f, eps_small,          \
                                    seg_rows1, colour, gs, 3, geo1.hl, geo1.out_w, xo, nullptr);    \
             else                                                                                   \
-                hipLaunchKernelGGL((gf_stage1_kernel<1, 3, MODE, EX>), ga1, dim3(stage1_threads(1)), \
+                hipLaunchKernelGGL((gf_stage1_kernel<1, 3, MODE, EX, GR>), ga1, dim3(stage1_threads(1, GR)), \
                                    pad1, st, g0, s0, ab, h, w, radius, eps_f, eps_small,           \
                                    seg_rows1, colour, gs, 3, geo1.hl, geo1.out_w, xo, nullptr);    \
         } else {                                                                                   \
-            hipLaunchKernelGGL((gf_stage1_kernel<1, 1, MODE, EX>), ga1, dim3(stage1_threads(1)), pad1, \
+            hipLaunchKernelGGL((gf_stage1_kernel<1, 1, MODE, EX, GR>), ga1, dim3(stage1_threads(1, GR)), pad1, \
                                st, g0, s0, ab, h, w, radius, eps_f, eps_small, seg_rows1, colour,  \
                                gs, 1, geo1.hl, geo1.out_w, xo, nullptr);                           \
         }                                                                                          \
     } while (0)
         if (debug_get(kDbgGfExpSkip) & 1)
             ;  // timing experiment: no stage 1 (results wrong)
+        else if (grey)  // (no exact rows, no guide cache: refused above)
+            RF_GF_STAGE1(kS1Full, false, true);
         else if (exact)
-            RF_GF_STAGE1(kS1Full, true);
+            RF_GF_STAGE1(kS1Full, true, false);
         else if (!keep_gs)
-            RF_GF_STAGE1(kS1Full, false);
+            RF_GF_STAGE1(kS1Full, false, false);
         else if (it == 0)
-            RF_GF_STAGE1(kS1Keep, false);
+            RF_GF_STAGE1(kS1Keep, false, false);
         else
-            RF_GF_STAGE1(kS1Reuse, false);
+            RF_GF_STAGE1(kS1Reuse, false, false);
 #undef RF_GF_STAGE1
 #undef RF_GF_S1_ATTR
     };
@@ -1637,7 +1751,8 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
                                     // Debug option "gf_cw_chan_run": n + 1 forces runs of n (1: channel fastest)
                                     P.cmp3 != nullptr
                                         ? (debug_get(kDbgGfCwChanRun) ? debug_get(kDbgGfCwChanRun) - 1 : 64)
-                                        : 0};
+                                        : 0,
+                                    gcn};
             fused_launch(fa);
             if (P.cmp3 != nullptr && it + 1 == iterations && !(debug_get(kDbgGfExpSkip) & 4))
                 hipLaunchKernelGGL(gf_interleave3_kernel, dim3(probe_blocks, m), dim3(256), 0, st, P.cmp3,
@@ -1650,12 +1765,12 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
         dim3 gc(ceil_div(w, 64), 1, m);
         if (src_cn == 3) {
             hipLaunchKernelGGL((gf_colsum_apply_kernel<3, 3>), gc, dim3(64, 12), 0, st, P.rows,
-                               P.g0, P.d0, h, w, radius, P.colour);
+                               P.g0, P.d0, h, w, radius, P.colour, gcn);
             hipLaunchKernelGGL((gf_colsum_apply_kernel<1, 3>), gc, dim3(64, 4), 0, st, P.rows,
-                               P.g0, P.d0, h, w, radius, P.colour);
+                               P.g0, P.d0, h, w, radius, P.colour, gcn);
         } else {
             hipLaunchKernelGGL((gf_colsum_apply_kernel<1, 1>), gc, dim3(64, 4), 0, st, P.rows,
-                               P.g0, P.d0, h, w, radius, P.colour);
+                               P.g0, P.d0, h, w, radius, P.colour, gcn);
         }
     };
     auto run_part = [&](int i0, int m, int m_fill, char *ws, hipStream_t st) {
@@ -1721,7 +1836,7 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
         Events evs;
         hipEvent_t fork = evs.make(), join = evs.make();
         if (!fork || !join)
-            return fail(RF_E_HIP, "rf_gf_u8: hipEventCreate failed");
+            return fail(RF_E_HIP, "%s: hipEventCreate failed", fn);
         RF_HIP_CHECK(hipEventRecord(fork, stream));
         RF_HIP_CHECK(hipStreamWaitEvent(side, fork, 0));
         if (!stagger) {
@@ -1755,7 +1870,7 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
                     part_stage1(P, it);
                     prev = evs.make();
                     if (!prev)
-                        return fail(RF_E_HIP, "rf_gf_u8: hipEventCreate failed");
+                        return fail(RF_E_HIP, "%s: hipEventCreate failed", fn);
                     RF_HIP_CHECK(hipEventRecord(prev, P.st));
                     part_stage2(P, it);
                 }
@@ -1765,6 +1880,23 @@ extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, 
     }
     RF_HIP_CHECK(hipGetLastError());
     return RF_OK;
+}
+}  // namespace
+
+extern "C" int rf_gf_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, int n, int h,
+                        int w, int guide_cn, int src_cn, int radius, double eps, int iterations,
+                        void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return gf_u8_entry("rf_gf_u8", guide, src, dst, n, h, w, guide_cn, src_cn, radius, eps, iterations,
+                       0, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int rf_gf_ex_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, int n, int h,
+                           int w, int guide_cn, int src_cn, int radius, double eps, int iterations,
+                           int flags, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return gf_u8_entry("rf_gf_ex_u8", guide, src, dst, n, h, w, guide_cn, src_cn, radius, eps,
+                       iterations, flags, workspace, workspace_bytes, stream_);
 }
 
 extern "C" size_t rf_gf_f32_workspace_bytes(int n, int h, int w, int guide_cn, int src_cn,

@@ -516,8 +516,10 @@ __global__ __launch_bounds__(128, (R <= 64 ? 2 : 1)) void gf_colwalk_kernel(
     const uint8_t *__restrict__ guide, uint8_t *__restrict__ dst, int h, int w, int nb,
     int n_pairs, int spx, const int *__restrict__ colour, const GfChain xc,
     uint8_t *__restrict__ compact, const GfStateLayout lay, const GfExact xr,
-    uint8_t *__restrict__ compact3, int chan_group)
+    uint8_t *__restrict__ compact3, int chan_group, int gcn)
 {
+    // gcn: guide bytes per pixel - 3, or 1 for a grey guide that stands for three equal channels
+    // (a run-time value, uniform over the launch: one instantiation per radius serves both)
     using G = WalkGeom<R>;
     constexpr int M = G::M, T = G::T;
     constexpr int KS = 2 * R + 1;
@@ -602,7 +604,7 @@ __global__ __launch_bounds__(128, (R <= 64 ? 2 : 1)) void gf_colwalk_kernel(
     const int np = 4 * spx;
     const float *abg = ab + ((size_t)img * np + 4 * s_ch) * npx;          // planes 4s .. 4s+3
     const double *stg = states + ((size_t)img * np + 4 * s_ch) * nb * h;  // their states
-    const uint8_t *gimg = guide + (size_t)img * npx * 3;
+    const uint8_t *gimg = guide + (size_t)img * npx * gcn;
     uint8_t *dimg = dst + (size_t)img * npx * spx;
     // a grey 3-channel image of an iterated call hands its result on as one byte per pixel
     uint8_t *cimg = (grey3 && compact != nullptr) ? compact + (size_t)img * npx : nullptr;
@@ -643,7 +645,7 @@ __global__ __launch_bounds__(128, (R <= 64 ? 2 : 1)) void gf_colwalk_kernel(
             cnt += G::start(c) < rem ? 1 : 0;
         nsub = full * 2 * M + cnt;
     }
-    const uint32_t gbytes = (uint32_t)(npx * 3);
+    const uint32_t gbytes = (uint32_t)(npx * gcn);
     // chained hand-off: sums in from block b - 1, out to block b + 1; nsub_all = sub-tile slots per block
     const int nsub_all = gf_chain_nsub(h, R);
     const size_t item_blk = ((size_t)img * spx + s_ch) * nb + b;
@@ -679,7 +681,7 @@ __global__ __launch_bounds__(128, (R <= 64 ? 2 : 1)) void gf_colwalk_kernel(
         for (int i = 0; i < NF; i++)
             pxf[i] = 0.0;
     }
-    uint32_t gpre[3];  // guide bytes of the lane's four output pixels
+    uint32_t gpre[3];  // guide bytes of the lane's four output pixels (grey guide: gpre[0] only)
     double SUM = 0.0;
     double fifo[FL];
 
@@ -757,10 +759,12 @@ __global__ __launch_bounds__(128, (R <= 64 ? 2 : 1)) void gf_colwalk_kernel(
                             (unsigned)(bits >> 32), gf_chain_tag1(sb_out, (unsigned)jj, (unsigned)lane)};
         __builtin_amdgcn_raw_buffer_store_b128(o, rs_out, (jj * 64 + lane) * 16, 0, 16);
     };
-    // guide bytes of the lane's output pixels: row y0 + fr, columns 16 b + 4 qd .. + 3 (12 bytes)
+    // guide bytes of the lane's output pixels: row y0 + fr, columns 16 b + 4 qd .. + 3 (12 bytes; a grey
+    // guide needs the first 4 of them - the same 12-byte load either way keeps the colour guide's code
+    // as it was, and the lanes' windows still lie in the same cache lines of the one-byte row)
     auto guide_fetch = [&](int y0) __attribute__((always_inline)) {
         const int gy = min(y0 + fr, h - 1);
-        const uint32_t off = ((uint32_t)gy * w + b * kSB + 4 * qd) * 3;
+        const uint32_t off = ((uint32_t)gy * w + b * kSB + 4 * qd) * (uint32_t)gcn;
         gpre[0] = gpre[1] = gpre[2] = 0;
         if (off + 12 <= gbytes) {
             __builtin_memcpy(gpre, gimg + off, 12);
@@ -968,6 +972,13 @@ __global__ __launch_bounds__(128, (R <= 64 ? 2 : 1)) void gf_colwalk_kernel(
             const float4 bt = *reinterpret_cast<const float4 *>(&L.u.xch[frc][48 + 4 * qd]);
             const float A0[4] = {a0.x, a0.y, a0.z, a0.w}, A1[4] = {a1.x, a1.y, a1.z, a1.w};
             const float A2[4] = {a2.x, a2.y, a2.z, a2.w}, BT[4] = {bt.x, bt.y, bt.z, bt.w};
+            if (gcn == 1) {  // grey guide: its four bytes as the twelve of three equal channels
+                const uint32_t g4 = gpre[0], b0 = g4 & 0xff, b1 = (g4 >> 8) & 0xff, b2 = (g4 >> 16) & 0xff,
+                               b3 = g4 >> 24;
+                gpre[0] = b0 * 0x010101u | (b1 << 24);
+                gpre[1] = b1 * 0x0101u | (b2 * 0x0101u << 16);
+                gpre[2] = b2 | (b3 * 0x010101u << 8);
+            }
             o4 = 0;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -1061,6 +1072,7 @@ struct GfFusedArgs {
     GfExact xr;         // exact rows: flags and list of the rows that take the row walk (on = 0: all do)
     uint8_t *compact3;  // not the last pass of an iterated call: colour images go here as three planes
     int chan_group;     // column walk: pairs per channel run in an XCD's item order (0: channel fastest)
+    int guide_cn;       // guide bytes per pixel: 3, or 1 (RF_GF_GREY_AS_BGR: three equal channels)
 };
 typedef void (*GfFusedLaunch)(const GfFusedArgs &);
 GfFusedLaunch gf_fused_launcher(int radius);  // nullptr outside 1 .. kGfFusedMaxRadius
@@ -1084,7 +1096,7 @@ void gf_fused_launch(const GfFusedArgs &a)
                                    dim3(8u * (unsigned)((a.m + 7) / 8) * a.src_cn * a.nb), dim3(128),
                                    0, a.stream, a.ab, a.states, a.guide, a.dst, a.h, a.w, a.nb, pairs,
                                    a.src_cn, a.colour, a.chain, a.compact, a.lay, GfExact{nullptr, nullptr, nullptr, 0, 0},
-                                   a.compact3, 0);
+                                   a.compact3, 0, a.guide_cn);
         }
         return;
     }
@@ -1105,14 +1117,15 @@ void gf_fused_launch(const GfFusedArgs &a)
             hipLaunchKernelGGL((gf_colwalk_kernel<R, false, true>),
                                dim3(cw_grid), dim3(128), 0, a.stream,
                                a.ab, a.states, a.guide, a.dst, a.h, a.w, a.nb, pairs, a.src_cn, a.colour,
-                               GfChain{nullptr, nullptr, nullptr}, a.compact, a.lay, a.xr, a.compact3, cgrp);
+                               GfChain{nullptr, nullptr, nullptr}, a.compact, a.lay, a.xr, a.compact3, cgrp,
+                               a.guide_cn);
             return;
         }
     }
     hipLaunchKernelGGL((gf_colwalk_kernel<R>), dim3(cw_grid),
                        dim3(128), 0, a.stream, a.ab, a.states, a.guide, a.dst, a.h, a.w, a.nb, pairs,
                        a.src_cn, a.colour, GfChain{nullptr, nullptr, nullptr}, a.compact, a.lay, a.xr,
-                       a.compact3, cgrp);
+                       a.compact3, cgrp, a.guide_cn);
 }
 
 }  // namespace rf

@@ -98,14 +98,23 @@ def get_reflectance_batch(images, weights=None):
     return ops.cnn_reflectance_u8(images, weights=weights)
 
 
-def decompose_and_filter_batch(images, sigma_color=20.0, sigma_spatial=22.0, weights=None):
-    """BF(CNN, CNN) on the device, the paper's headline pipeline (README.md:56 of the reference):
-    CUDA uint8 BGR [N,H,W,3] -> (r_u8 [N,H,W], filtered [N,H,W]) with `filtered` bit-identical to
-    what the two CLIs produce through `<base>-r.png` (grey PNG re-read as 3 equal channels,
-    filtered with itself as guidance, any channel of the result)."""
+def decompose_and_filter_batch(images, sigma_color=20.0, sigma_spatial=22.0, weights=None,
+                               filter_type="bilateral"):
+    """CNN -> filter(CNN, CNN) on the device, the reference tool's two self-guided recipes:
+    'bilateral' BF(CNN, CNN) (the paper's headline pipeline, README.md:56 of the reference;
+    jointBilateralFilter with d = -1) or 'guided' GF(CNN, CNN) (guidedFilter with
+    radius = int(sigma_spatial), eps = sigma_color; the tool suggests sigma_color=7,
+    sigma_spatial=52).  CUDA uint8 BGR [N,H,W,3] -> (r_u8 [N,H,W], filtered [N,H,W]) with
+    `filtered` bit-identical to what the two CLIs produce through `<base>-r.png` (grey PNG re-read
+    as 3 equal channels, filtered with itself as guidance, any channel of the result)."""
+    if filter_type not in ("bilateral", "guided"):
+        raise ValueError("filter_type must be 'bilateral' or 'guided'.")
     _, r8 = ops.cnn_reflectance_u8(images, weights=weights, want_float=False)
     r1 = r8.unsqueeze(-1)
-    out = ops.joint_bilateral_u8(r1, r1, -1, sigma_color, sigma_spatial, grey_as_bgr=True)
+    if filter_type == "guided":
+        out = ops.guided_filter_u8(r1, r1, int(sigma_spatial), sigma_color, grey_as_bgr=True)
+    else:
+        out = ops.joint_bilateral_u8(r1, r1, -1, sigma_color, sigma_spatial, grey_as_bgr=True)
     return r8, out.squeeze(-1)
 
 

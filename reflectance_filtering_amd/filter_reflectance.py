@@ -52,19 +52,23 @@ def apply_filter(filter_type, image, joint, sigma_color, sigma_spatial):
                                  eps=sigma_color)
 
 
-def apply_filter_batch(filter_type, images, joints, sigma_color, sigma_spatial, iterations=1):
+def apply_filter_batch(filter_type, images, joints, sigma_color, sigma_spatial, iterations=1,
+                       grey_as_bgr=False):
     """Device-resident batch form: ``images``/``joints`` are CUDA uint8 tensors [N,H,W,C];
     returns a CUDA uint8 tensor.  ``iterations`` > 1 chains the filter with the same guidance
-    (the uint8 result of one pass is the input of the next), e.g. the reference's 3x GF."""
+    (the uint8 result of one pass is the input of the next), e.g. the reference's 3x GF.
+    ``grey_as_bgr``: ``joints`` is [N,H,W,1] and counts as three equal channels (a grey PNG as
+    cv2.imread reads it), in either filter."""
     _check_params(filter_type, sigma_color, sigma_spatial)
     if iterations < 1:
         raise ValueError("iterations must be >= 1")
     if filter_type == "guided":
         return ops.guided_filter_u8(joints, images, int(sigma_spatial), sigma_color,
-                                    iterations=iterations)
+                                    iterations=iterations, grey_as_bgr=grey_as_bgr)
     out = images
     for _ in range(iterations):
-        out = ops.joint_bilateral_u8(joints, out, -1, sigma_color, sigma_spatial)
+        out = ops.joint_bilateral_u8(joints, out, -1, sigma_color, sigma_spatial,
+                                     grey_as_bgr=grey_as_bgr)
     return out
 
 

@@ -76,9 +76,13 @@ def gf_workspace(n, h, w, scn, radius, device, torch):
     return ws
 
 
-def guided_filter_u8(guide, src, radius, eps, iterations=1, out=None, workspace=None):
+def guided_filter_u8(guide, src, radius, eps, iterations=1, out=None, workspace=None,
+                     grey_as_bgr=False):
     """Batched cv2.ximgproc.guidedFilter(guide, src, radius, eps), applied `iterations` times
-    with the uint8 result fed back as src (the reference's chained CLI runs)."""
+    with the uint8 result fed back as src (the reference's chained CLI runs).
+    grey_as_bgr: the guide is [N,H,W,1] and is filtered as the 3-equal-channel image cv2.imread
+    would have produced from it (rf_gf_ex_u8 with RF_GF_GREY_AS_BGR; no replicated copy is made) -
+    the same bytes as the replicated guide, not OpenCV's 1-channel-guide arithmetic."""
     torch = _ffi.require_gpu()
     lib = _ffi.load_library()
     _chk_images(guide, "guide", torch)
@@ -90,6 +94,13 @@ def guided_filter_u8(guide, src, radius, eps, iterations=1, out=None, workspace=
     n, h, w, scn = src.shape
     if workspace is None:
         workspace = gf_workspace(n, h, w, scn, int(radius), src.device, torch)
+    if grey_as_bgr:
+        rc = lib.rf_gf_ex_u8(guide.data_ptr(), src.data_ptr(), out.data_ptr(), n, h, w,
+                             guide.shape[3], scn, int(radius), float(eps), int(iterations),
+                             _ffi.GF_GREY_AS_BGR, workspace.data_ptr(), workspace.numel(),
+                             _ffi.current_stream_ptr(torch))
+        _ffi.check(rc, "rf_gf_ex_u8")
+        return out
     rc = lib.rf_gf_u8(guide.data_ptr(), src.data_ptr(), out.data_ptr(), n, h, w, guide.shape[3],
                       scn, int(radius), float(eps), int(iterations), workspace.data_ptr(),
                       workspace.numel(), _ffi.current_stream_ptr(torch))

@@ -85,7 +85,9 @@ def guidedFilter(guide, src, radius, eps, dst=None, dDepth=-1):
     (/root/reference/filter_reflectance.py:67-70) and runs the 8-bit kernels; every other
     combination runs the float kernels on the values as they are (OpenCV converts without
     scaling) and, for an 8-bit result, rounds like saturate_cast<uchar> - on 8-bit inputs the
-    same bytes as the 8-bit kernels, whose float core it is."""
+    same bytes as the 8-bit kernels, whose float core it is.  A 1-channel (or 2-D) guide is
+    refused: OpenCV inverts var + eps as a scalar for it, which is not what the grey-guide kernels
+    compute (they treat it as three equal channels, ops.guided_filter_u8(grey_as_bgr=True))."""
     torch = _ffi.require_gpu()
     g_np, s_np = np.asarray(guide), np.asarray(src)
     if g_np.shape[:2] != s_np.shape[:2]:
