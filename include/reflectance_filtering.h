@@ -162,13 +162,20 @@ int rf_cnn_reflectance_packed_u8(const uint8_t *bgr, float *r_out, uint8_t *r_u8
  * /root/reference/image_utils.py:42-49, 60-92) for a batch that is already on the device:
  *   shading = mean_c(bgr) / r ; reflectance = bgr / max(shading, 1e-3)          (float64)
  *   each: if max > 1: clip(x / percentile(x, 99.9, 'lower'), 0, 1); rgb_to_srgb; trunc(x * 255)
+ *   r must be >= +0.  r == 0 makes the shading +inf (a black pixel: 0/0 = NaN, and NaN
+ *   reflectance).  As in numpy, max is NaN for a result that holds a NaN, `max > 1` fails and that
+ *   result is written WITHOUT normalisation: NaN -> byte 0, values above 1 keep counting
+ *   srgb_steps up to byte 255.  Where numpy's trunc(x * 255) would be >= 256 (x above ~1.087)
+ *   its uint8 cast overflows and the reference's byte depends on the platform: unspecified
+ *   (this library writes 255).
  *   bgr          n*h*w*3 uint8 device        r   n*h*w float32 device (the CNN output)
  *   refl_out     n*h*w*3 uint8 device or NULL (bytes of `<base>-r_colorized.png`, BGR order)
  *   shading_out  n*h*w   uint8 device or NULL (bytes of `<base>-s_colorized.png`)
  *   k_refl, k_shading  0-based rank of the 99.9-percentile ('lower') among the 3*h*w resp. h*w
  *                values of one image, computed by the caller with numpy's own index rule
- *   srgb_steps   255 float64 on the device: srgb_steps[k-1] = smallest x in (0.0031308, 1] with
- *                trunc(((1.055*x)^(1/2.4) - 0.055) * 255) >= k under the HOST's pow (+inf if none);
+ *   srgb_steps   255 float64 on the device: srgb_steps[k-1] = smallest x > 0.0031308 with
+ *                trunc(((1.055*x)^(1/2.4) - 0.055) * 255) >= k under the HOST's pow (all finite;
+ *                k >= 247 lie above 1);
  *                this makes the bytes exact for the libm the reference would have used
  *   workspace    device scratch, rf_colorize_workspace_bytes(n) bytes
  */

@@ -139,8 +139,9 @@ __global__ __launch_bounds__(256) void colorize_pick_kernel(SelState *st, int pa
     }
 }
 
-// rgb_to_srgb + (x*255).astype(uint8) of a value in [0,1] (NaN -> 0 like the zero-initialised
-// result array of the reference)
+// rgb_to_srgb + (x*255).astype(uint8) of a value in [0, steps[254]] (NaN -> 0 like the
+// zero-initialised result array of the reference); above steps[254], where only a target holding
+// a NaN goes unnormalised, 255 (numpy's cast overflows from byte 256 on)
 __device__ inline uint8_t srgb_byte(double v, const double *__restrict__ steps)
 {
     if (v <= 0.0031308)
@@ -182,8 +183,12 @@ __global__ __launch_bounds__(256) void colorize_write_kernel(
     const int img = blockIdx.y;
     const SelState &s0 = st[img * kTargets + 0];
     const SelState &s1 = st[img * kTargets + 1];
-    const unsigned long long one = key_of(1.0);
-    const bool n0 = s0.maxkey > one, n1 = s1.maxkey > one;  // np.max(img) > 1
+    // np.max(img) > 1.  The values are non-negative, so the key of a NaN (exponent field all
+    // ones, non-zero fraction) lies above that of +inf: np.max is NaN then, `NaN > 1` is false,
+    // and the target is written without normalisation.
+    const unsigned long long one = key_of(1.0), inf = key_of(__longlong_as_double(0x7ff0000000000000LL));
+    const bool n0 = s0.maxkey > one && s0.maxkey <= inf;
+    const bool n1 = s1.maxkey > one && s1.maxkey <= inf;
     const double p0 = __longlong_as_double((long long)s0.prefix);
     const double p1 = __longlong_as_double((long long)s1.prefix);
     const uint8_t *b = bgr + (size_t)img * npx * 3;

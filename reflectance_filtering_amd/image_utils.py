@@ -66,31 +66,36 @@ _steps_cache = None
 
 
 def srgb_write_steps():
-    """float64[255] for the device colourise path: entry k-1 is the smallest x in (0.0031308, 1]
-    for which imwrite(..., sRGB=True) stores a byte >= k, i.e.
+    """float64[255] for the device colourise path: entry k-1 is the smallest x > 0.0031308 for
+    which imwrite(..., sRGB=True) stores a byte >= k, i.e.
     ((rgb_to_srgb(x)) * 255).astype(uint8) >= k, evaluated with THIS host's numpy (np.power is
     libm's pow, which a GPU cannot reproduce bit for bit; a table of the <= 255 steps of the
-    monotone byte curve can).  +inf where no x <= 1 reaches the byte (rgb_to_srgb(1) = 0.9676)."""
+    monotone byte curve can).  Every step is finite: bytes 247..255 lie above x = 1
+    (rgb_to_srgb(1) = 0.9676), where an image that holds a NaN is written without normalisation
+    (np.max is NaN, so `max > 1` fails); byte 255 starts near x = 1.078.  From
+    rgb_to_srgb(x) * 255 >= 256 on (x ~ 1.087) the cast to uint8 overflows and numpy's bytes
+    depend on the platform: the table does not describe them."""
     global _steps_cache
     if _steps_cache is not None:
         return _steps_cache
 
-    def byte_of(x):
-        return (rgb_to_srgb(x) * 255).astype(np.uint8).astype(np.int64)
+    def at_least(x, ks):
+        # (v * 255).astype(uint8) >= k for every v * 255 below 256 (truncation of a non-negative
+        # value), without the cast that overflows above it
+        return np.floor(rgb_to_srgb(x) * 255) >= ks
 
     ks = np.arange(1, 256, dtype=np.int64)
     first = np.nextafter(np.float64(0.0031308), np.float64(1.0))
     lo = np.full(255, first.view(np.int64), dtype=np.int64)       # candidates as bit patterns
-    hi = np.full(255, np.float64(1.0).view(np.int64), dtype=np.int64)
-    reach = byte_of(np.full(255, 1.0)) >= ks                       # byte(1.0) >= k ?
-    # invariant: byte(hi) >= k (where reachable); find the smallest such bit pattern in [lo, hi]
+    hi = np.full(255, np.float64(1.125).view(np.int64), dtype=np.int64)
+    assert at_least(hi.view(np.float64), ks).all()
+    # invariant: byte(hi) >= k; find the smallest such bit pattern in [lo, hi]
     while np.any(lo < hi):
         mid = lo + (hi - lo) // 2
-        ok = byte_of(mid.view(np.float64)) >= ks
+        ok = at_least(mid.view(np.float64), ks)
         hi = np.where(ok, mid, hi)
         lo = np.where(ok, lo, np.minimum(mid + 1, hi))
     steps = hi.view(np.float64).copy()
-    steps[~reach] = np.inf
     _steps_cache = steps
     return steps
 

@@ -31,28 +31,38 @@ def _byte_of(x):
     return (iu.rgb_to_srgb(np.asarray(x, dtype=np.float64)) * 255).astype(np.uint8).astype(int)
 
 
-def test_srgb_write_steps_are_the_steps_of_the_byte_curve():
+def _below_byte_256(x):
+    """x whose byte numpy computes without overflowing the uint8 cast (x below ~1.087)."""
+    return iu.rgb_to_srgb(np.asarray(x, dtype=np.float64)) * 255 < 256
+
+
+def test_srgb_write_steps_reach_byte_255_above_one():
+    """Every byte 1..255 has a finite step, those above 246 beyond x = 1: an image holding a NaN
+    is written without normalisation, so its values above 1 reach the byte curve as they are."""
     steps = iu.srgb_write_steps()
     assert steps.shape == (255,) and steps.dtype == np.float64
-    fin = np.isfinite(steps)
+    assert np.isfinite(steps).all() and np.all(np.diff(steps) >= 0)
     k = np.arange(1, 256)
-    assert np.all(np.diff(steps[fin]) >= 0) and not fin[246:].any() and fin[:246].all()
+    assert steps[245] <= 1.0 < steps[246] and _below_byte_256(steps).all()
     first = np.nextafter(0.0031308, 1.0)
-    assert np.all(_byte_of(steps[fin]) >= k[fin])
-    below = np.nextafter(steps[fin], 0.0)
+    assert np.all(_byte_of(steps) >= k)
+    below = np.nextafter(steps, 0.0)
     inside = below >= first
-    assert np.all(_byte_of(below[inside]) < k[fin][inside])
-    assert np.all(steps[fin][~inside] == first)
-    # counting steps <= x is the byte, on random values and right around every step
+    assert np.all(_byte_of(below[inside]) < k[inside])
+    assert np.all(steps[~inside] == first)
+    # counting steps <= x is the byte, on random values and right around every step, on
+    # (0.0031308, 1] and above 1 up to where the byte would reach 256
     rng = np.random.default_rng(3)
-    xs = [rng.uniform(first, 1.0, 200000), 10.0 ** rng.uniform(-2.5, 0.0, 100000), np.array([first, 1.0])]
+    xs = [rng.uniform(first, 1.0, 200000), 10.0 ** rng.uniform(-2.5, 0.0, 100000),
+          rng.uniform(1.0, 1.09, 100000), np.array([first, 1.0, np.nextafter(1.0, 2.0)])]
     for d in range(-3, 4):
-        x = steps[fin].copy()
+        x = steps.copy()
         for _ in range(abs(d)):
             x = np.nextafter(x, 2.0 if d > 0 else 0.0)
-        xs.append(x[(x >= first) & (x <= 1.0)])
+        xs.append(x)
     x = np.concatenate(xs)
-    x = x[(x >= first) & (x <= 1.0)]
+    x = x[(x >= first) & _below_byte_256(x)]
+    assert (x > 1.0).sum() > 50000 and (x > steps[-1]).sum() > 5000
     assert np.array_equal(np.searchsorted(steps, x, side="right"), _byte_of(x))
 
 

@@ -356,7 +356,8 @@ def test_jbf_randomised_sweep(env):
 def test_jbf_row_pipeline(env, sc, ss):
     """The grey tap loop carries its software pipeline from one tap row into the next (the last
     group of a row prefetches the next row); against the compiler-scheduled loop (debug option), the
-    64x64-only launch and the oracle, for several radii (different row shapes)."""
+    64x64-only launch, the one-step-lookahead gathers and the oracle, for several radii (different
+    row shapes)."""
     from tests import synth
     rf, co, torch = env
     h, w = 150, 200
@@ -365,7 +366,7 @@ def test_jbf_row_pipeline(env, sc, ss):
     jd, sd = _dev(torch, joint, grey)
     got = rf.ops.joint_bilateral_u8(jd, sd, -1, sc, ss)
     assert np.array_equal(got.cpu().numpy()[0], co.joint_bilateral_filter(joint, grey, -1, sc, ss))
-    for opt in ("jbf_compiler_loop", "jbf_tile64_only"):
+    for opt in ("jbf_compiler_loop", "jbf_tile64_only", "jbf_lookahead1"):
         with rf._ffi.debug_options(**{opt: 1}):
             assert torch.equal(rf.ops.joint_bilateral_u8(jd, sd, -1, sc, ss), got), opt
     # colour src: the hand-scheduled 6-byte-texel loop against the oracle and the compiler's loop

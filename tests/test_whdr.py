@@ -114,6 +114,58 @@ def test_device_batch_matches_reference_and_host(built):
         W.whdr_batch(torch.zeros((1, 1, 4, 4), device="cuda"), [np.array([[4, 0, 1, 1, 1, 1.0]])])
 
 
+def _edge_case_batch(rng, c, n, h, w):
+    """The generator of test_host_whdr_edge_cases_match_the_definition as a batch (0 and NaN
+    lightness floored at EPS, 0 / 1 / 50 / 300 comparisons, all-zero weights), plus pairs whose
+    float32 ratio is exactly float32(1 + delta) for delta 0.1 and 0 - "about equal", not darker."""
+    refl = (rng.random((n, c, h, w)) ** 3).astype(np.float32)
+    refl[:, :, 2, 3] = 0
+    refl[:, :, 4, 5] = np.nan
+    # row 6: (6, 0) lightness 0.5, (6, 1) its float32(1.1) multiple, (6, 2) equal to (6, 0)
+    refl[:, :, 6, 0] = 0.5
+    refl[:, :, 6, 1] = np.float32(0.5) * np.float32(1.1)
+    refl[:, :, 6, 2] = 0.5
+    comps = []
+    for i in range(n):
+        k = (0, 1, 50, 300)[i % 4]
+        comp = np.zeros((k, 6))
+        comp[:, :4] = rng.random((k, 4)) * 0.999
+        comp[:, 4] = rng.integers(0, 3, k)
+        comp[:, 5] = rng.random(k) if i % 5 else 0.0
+        px = W.to_pixels(comp, h, w)
+        if k:
+            px[0, :4] = (3, 2, 5, 4)
+        if k >= 50:
+            exact = np.array([(0, 6, 1, 6), (1, 6, 0, 6), (0, 6, 2, 6), (2, 6, 0, 6), (0, 6, 0, 6)])
+            px[1:6, :4] = exact
+            px[6:11, :4] = exact
+            px[1:11, 4] = rng.integers(0, 3, 10)
+        comps.append(px)
+    return refl, comps
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", [1, 3])
+def test_device_batch_edge_cases_match_host_and_definition(built, c):
+    """Device WHDR on the edge cases the host mirror is held to, with more than 64 comparisons per
+    image (the wave loop runs several times): the same float64 value as W.whdr and as the
+    definition spelled out, bit for bit, for delta 0.1 and 0."""
+    import torch
+    rng = np.random.default_rng(17 + c)
+    n, h, w = 12, 9, 13
+    refl, comps = _edge_case_batch(rng, c, n, h, w)
+    light = refl[0, :, 6, :3].mean(axis=0) if c == 3 else refl[0, 0, 6, :3]
+    assert light[1] / light[0] == np.float32(1 + 0.1) and light[2] / light[0] == np.float32(1 + 0.0)
+    for dl in (0.1, 0.0):
+        got = W.whdr_batch(torch.from_numpy(refl).cuda(), comps, dl)
+        assert got.shape == (n,)
+        for i in range(n):
+            with np.errstate(all="ignore"):
+                host = W.whdr(refl[i], comps[i], dl)
+                spelled = _whdr_by_definition(refl[i], comps[i], dl)
+            assert got[i] == host == spelled, (c, dl, i, got[i], host, spelled)
+
+
 def test_to_pixels_keeps_float32_products():
     """Coordinates of a float32 blob are multiplied in float32 (whdr_layer.py:248-249 multiplies
     the array by a Python int): k / w as float32 times w rounds back to k, where the float64
