@@ -1,5 +1,5 @@
 # Convenience targets; the driver uses __graft_entry__.build(), pytest and bench.py directly.
-.PHONY: build test test-gpu bench clean golden
+.PHONY: build test test-gpu bench bench-full clean golden
 
 build:
 	python -c "import __graft_entry__ as g; g.build()"
@@ -12,6 +12,9 @@ test-gpu: build
 
 bench: build
 	python bench.py
+
+bench-full: build
+	python bench.py --full
 
 golden:            # needs /root/reference (build container only)
 	python tests/golden/make_golden.py

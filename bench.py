@@ -2,7 +2,7 @@
 """bench.py -- megapixels/s of the joint-bilateral hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config north_star|c2|c3|c4|c5]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,9 +14,15 @@ sigma_spatial=22 -> radius 33, 3,409 taps per pixel) over one batch of 256 synth
 images per GPU, inputs already resident in HBM.  Image batches shard across GPUs with no
 collective (weak scaling: the per-GPU batch is fixed); torch.distributed only carries the
 barrier and the max-over-ranks of the timed region.  Rank 0 prints ONE JSON line with the
-contract fields plus `roofline` and `cpu_baseline`, and (N = 1, default config) driver-timed lines
-for the other BASELINE configurations: `c2_single_image`, `c3_chain` (CNN -> BF(CNN,CNN), 256 IIW
-images) and `c5_gf` (3x guided filter r=45 eps=3 at 3840x2160).
+contract fields plus `roofline`, `valu` and `lds` (figures derived from the timed steps; the
+traffic is the committed profile's, the clock the 2.4 GHz peak).
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints that line; it
+launches nothing else.  `--full` adds what takes runs of its own: the shader clock probed beside
+the launch, `roofline.traffic` measured by rocprofv3 --pmc child passes (one GPU), `cpu_baseline`,
+and (N = 1, default config) the secondary launches `colour_src`, `grey_joint`, `c2_single_image`
+and driver-timed lines for the other BASELINE configurations: `c3_chain` (CNN -> BF(CNN,CNN),
+256 IIW images), `c5_gf` and `c5_gf_colour` (3x guided filter r=45 eps=3 at 3840x2160).
 
 Other workloads, same contract (`--config`):
     c2  one 1920x1080 image per step (BASELINE configs[1] as written)
@@ -72,17 +78,22 @@ def parse_args(argv=None):
                     help="joint-bilateral workloads: the src image - the grey CNN-style map the "
                          "reference filters (default, the metric's input) or a 3-channel colour "
                          "image (profiling the colour tap loop; named in config.workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the clock probe, the live "
+                         "traffic passes, the CPU baseline, the secondary launches and the "
+                         "C2/C3/C5 lines (off: the timed steps and the headline line only)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="target CPU time of the cpu_baseline sample (0 disables it)")
+                    help="with --full: target CPU time of the cpu_baseline sample (0 disables it)")
     ap.add_argument("--traffic", choices=("auto", "live", "profile", "off"), default="auto",
                     help="roofline.traffic of the metric launch: 'live' measures it now (two child "
                          "runs of this script under rocprofv3 --pmc, FETCH_SIZE and WRITE_SIZE "
-                         "in separate passes), 'profile' takes the committed summary of the same "
-                         "launch shape, 'auto' = live on one GPU when rocprofv3 is there and this "
-                         "process is not itself being profiled, else profile; 'off' = null")
+                         "in separate passes; needs --full), 'profile' takes the committed summary "
+                         "of the same launch shape, 'auto' = live with --full on one GPU when "
+                         "rocprofv3 is there and this process is not itself being profiled, else "
+                         "profile; 'off' = null")
     ap.add_argument("--no-extras", "--no-colour-src", dest="no_extras", action="store_true",
-                    help="skip the secondary launches and the C2/C3/C5 lines (keeps a profile of "
-                         "this command to the one timed kernel shape)")
+                    help="with --full: skip the secondary launches and the C2/C3/C5 lines (keeps a "
+                         "profile of this command to the one timed kernel shape)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0's "
                          "shard) as DIR/<name>.npy in float32, at most 64 MB in all (a fixed seeded "
@@ -91,6 +102,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.traffic == "live" and not args.full:
+        ap.error("--traffic live measures in child runs of its own: add --full")
     return args
 
 
@@ -850,14 +863,15 @@ def run_rank(args):
         dump_outputs(args.dump_outputs, wl, args, world)
     wl.last = None
 
+    # everything below that launches or measures anything is --full's: a plain run is done
     extras = {}
     clock_mhz = None
-    if rank == 0 and not stub and kind == "jbf" and kernel_ms and kernel_ms > 2.0:
+    if args.full and rank == 0 and not stub and kind == "jbf" and kernel_ms and kernel_ms > 2.0:
         try:
             clock_mhz = measured_clock_mhz(torch, rf, wl.step, kernel_ms)
         except Exception as exc:                  # noqa: BLE001 - a measurement aid, never fatal
             sys.stderr.write("bench.py: clock probe failed: %r\n" % (exc,))
-    if rank == 0 and not stub and not args.no_extras and kind == "jbf" and n > 1:
+    if args.full and rank == 0 and not stub and not args.no_extras and kind == "jbf" and n > 1:
         sc, ss = args.sigma_color, args.sigma_spatial
         joint, src, dst = wl.joint, wl.src, wl.dst
         # the same launch with a 3-channel colour src (3-channel accumulation; the headline src is
@@ -890,7 +904,7 @@ def run_rank(args):
         traffic, source = None, None
         mode = args.traffic
         if kind == "jbf" and mode != "off":
-            if mode == "live" or (mode == "auto" and world == 1 and not being_profiled()
+            if mode == "live" or (mode == "auto" and args.full and world == 1 and not being_profiled()
                                   and os.environ.get("RF_BENCH_CHILD") != "1"):
                 try:
                     traffic, source = live_traffic(args, n, h, w)
@@ -904,10 +918,10 @@ def run_rank(args):
                     source += (" (rocprofv3 --pmc passes of this launch shape; not measured by "
                                "this run)")
         headline_traffic = (traffic, source)
-    # the CPU baseline runs on rank 0 at ANY N ("next to the reference CPU filter ... in the same
-    # run", BASELINE.json): after the final barrier, when the other ranks have left the node's cores
+    # with --full the CPU baseline runs on rank 0 at ANY N ("next to the reference CPU filter ... in
+    # the same run", BASELINE.json): after the final barrier, when the other ranks have left the cores
     image0 = None
-    if rank == 0 and kind == "jbf" and args.cpu_seconds > 0:
+    if args.full and rank == 0 and kind == "jbf" and args.cpu_seconds > 0:
         if stub:
             import numpy as np
             rng = np.random.default_rng(5)
@@ -915,7 +929,7 @@ def run_rank(args):
                       rng.integers(0, 256, (h, w, 3), dtype=np.uint8))
         else:
             image0 = (wl.joint[0].cpu().numpy(), wl.src[0].cpu().numpy())
-    if (rank == 0 and not stub and world == 1 and not args.no_extras
+    if (args.full and rank == 0 and not stub and world == 1 and not args.no_extras
             and args.config == "north_star"):
         # driver-timed lines for the other BASELINE configurations (one GPU; not `value`)
         del wl.joint, wl.src, wl.dst

@@ -66,10 +66,10 @@ def _run_bench(extra_args, env_extra, timeout=300):
 
 
 def test_bench_launches_its_own_ranks_and_sums_their_pixels():
-    """`python bench.py --gpus 2` starts two ranks itself (gloo here, kernel call stubbed): one
-    JSON line from rank 0 with n_gpus = 2 and the pixels of both ranks in `value`."""
+    """`python bench.py --gpus 2 --full` starts two ranks itself (gloo here, kernel call stubbed):
+    one JSON line from rank 0 with n_gpus = 2 and the pixels of both ranks in `value`."""
     rc, out, err = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4",
-                               "--height", "8", "--width", "16"], {})
+                               "--height", "8", "--width", "16", "--full"], {})
     assert rc == 0, err[-2000:]
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1
     assert out["scaling"] == "weak" and out["higher_is_better"] is True
@@ -86,6 +86,23 @@ def test_bench_launches_its_own_ranks_and_sums_their_pixels():
     base = out["cpu_baseline"]
     assert base["kind"] in ("port", "reference") and base["value"] > 0 and base["cores"] >= 1
     assert base["unit"] == "MP/s" and "sample" in base
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """Without --full a run times its steps and prints the line: no CPU baseline (nor anything else
+    that takes runs of its own), the same contract fields; --traffic live asks for --full."""
+    rc, out, err = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
+                               "--height", "8", "--width", "16"], {})
+    assert rc == 0, err[-2000:]
+    assert "cpu_baseline" not in out
+    assert out["n_gpus"] == 2 and out["steps"] == 2 and out["warmup"] == 1
+    assert out["unit"] == "MP/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert np.isclose(out["value"] * 1e6 * out["ms_per_step"] * 1e-3 * 2, 2 * 4 * 8 * 16 * 2,
+                      rtol=1e-6)
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+    assert bench.parse_args(["--full", "--traffic", "live"]).traffic == "live"
+    rc, out, err = _run_bench(["--steps", "1", "--traffic", "live"], {})
+    assert rc != 0 and out is None and "--full" in err
 
 
 def test_bench_has_the_colour_chain_configuration():

@@ -132,15 +132,15 @@ print("ok", n)
 
 
 def test_bench_measures_its_traffic_live(gpu):
-    """`bench.py --traffic live`: the two rocprofv3 --pmc child passes run, the kernel is found in
-    their counter files and `roofline.traffic` is of the order of the algorithmic bytes (at this
-    small batch the counters read about 3x - 1.07x at the metric's 256 images, where the 128-byte
-    requests FETCH_SIZE is corrected for dominate)."""
+    """`bench.py --full --traffic live`: the two rocprofv3 --pmc child passes run, the kernel is
+    found in their counter files and `roofline.traffic` is of the order of the algorithmic bytes (at
+    this small batch the counters read about 3x - 1.07x at the metric's 256 images, where the
+    128-byte requests FETCH_SIZE is corrected for dominate)."""
     import shutil
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("no rocprofv3 on this machine")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "8", "--steps", "1", "--warmup",
-           "1", "--cpu-seconds", "0", "--no-extras", "--traffic", "live"]
+           "1", "--cpu-seconds", "0", "--no-extras", "--traffic", "live", "--full"]
     p = subprocess.run(cmd, env=_clean_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
