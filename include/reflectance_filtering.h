@@ -220,6 +220,56 @@ int rf_gf_f32(const float *guide, const float *src, float *dst, int n, int h, in
 int rf_whdr_f32(const float *refl, int n, int c, int h, int w, const int *points,
                 const double *weights, const int *offsets, double delta, double *out, void *stream);
 
+/*
+ * Joint bilateral filter, 8-bit, evaluated at listed pixels only, for many parameter sets in one
+ * call: the bilateral half of a WHDR parameter sweep (the reference's filter_reflectance.py:1
+ * "Go through color and spatial parameters and evaluate filter").
+ *   joint, src, n, h, w, joint_cn, src_cn, d, border  as for rf_jbf_u8
+ *   points         total_points*2 int32 device: x, y of each point (inside its image)
+ *   point_offsets  n+1 int32 device: the points of image i are [point_offsets[i], point_offsets[i+1])
+ *   sigma_color, sigma_space  n_params doubles each, HOST memory: parameter set p is
+ *                  (sigma_color[p], sigma_space[p]); sets may differ in sigma_space, i.e. in radius
+ *   out            n_params*total_points*src_cn uint8 device, must not overlap an input
+ *   workspace      device scratch of at least rf_jbf_points_workspace_bytes(n_params, sigma_space,
+ *                  d, joint_cn, flags) bytes (0 there = arguments the call refuses)
+ * out[p][k][c] is, byte for byte, what rf_jbf_u8(joint, src, ..., d, sigma_color[p],
+ * sigma_space[p], border, flags) writes at pixel points[k] of its image: the same radius rule,
+ * sigma <= 0 rule and refusals, the same per-pixel arithmetic (taps in row-major disk order,
+ * w = sw * lut[sad], separately rounded multiply and add, sum * (1/wsum) or, with
+ * RF_JBF_TRUE_DIVISION, sum / wsum) and the same RF_JBF_GREY_AS_BGR rule; RF_JBF_FORCE_GENERIC is
+ * accepted and changes nothing, any other flag bit is refused (RF_E_BADARG).  Points are not
+ * read on the host, so they cannot be checked: a point outside its image gives unspecified bytes
+ * (the kernel clamps it and never reads outside the images).  The parameter tables are built on
+ * the host by the code rf_jbf_u8 uses and staged in the workspace; rf_jbf_u8's table cache is
+ * left alone.  THIS ENTRY POINT SYNCHRONISES THE STREAM (before its launch, to upload the tables)
+ * and is refused (RF_E_UNSUPPORTED) on a stream that is being captured into a graph.
+ */
+size_t rf_jbf_points_workspace_bytes(int n_params, const double *sigma_space, int d, int joint_cn,
+                                     int flags);
+int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n, int h, int w, int joint_cn,
+                     int src_cn, const int *points, const int *point_offsets, int total_points,
+                     int n_params, const double *sigma_color, const double *sigma_space, int d,
+                     int border, int flags, uint8_t *out, void *workspace, size_t workspace_bytes,
+                     void *stream);
+
+/*
+ * WHDR of uint8 predictions sampled at judgement points (rf_jbf_points_u8's output, or whole
+ * images taken as point lists).
+ *   samples        n_sets*set_stride*c uint8 device: pixel q of set s is at (s*set_stride + q)*c
+ *   point_offsets  n int32 device (the n+1 array of rf_jbf_points_u8 serves): the points of image i
+ *                  are the pixels point_offsets[i] + index of each set
+ *   comps          total*3 int32 device: index of point 1, index of point 2 (into image i's
+ *                  points), darker (0 'E', 1, 2)
+ *   weights        total float64 device; comp_offsets n+1 int32 device (as in rf_whdr_f32)
+ *   out            n_sets*n float64 device: out[s*n + i] = WHDR of image i in set s
+ * Each byte becomes (float)byte / 255.0f (correctly rounded), and from there on the lightness,
+ * decision and float64 sums are rf_whdr_f32's: the result equals rf_whdr_f32 on the planar float
+ * images bytes / 255.0f.  Indices are not checked (device data); a read never leaves the set.
+ */
+int rf_whdr_points_u8(const uint8_t *samples, int n_sets, long long set_stride, int c, int n,
+                      const int *point_offsets, const int *comps, const double *weights,
+                      const int *comp_offsets, double delta, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,9 +31,45 @@
 #include <type_traits>
 #include <vector>
 
-#include "rf_common.hpp"
+#include "rf_jbf_common.hpp"
 
 namespace rf {
+
+int jbf_colour_lut(int joint_cn, double sigma_color, std::vector<float> &lut)
+{
+    const double gauss_color_coeff = -0.5 / (sigma_color * sigma_color);
+    const int nlut = 256 * joint_cn;
+    lut.assign(nlut, 0.0f);
+    for (int i = 0; i < nlut; i++)
+        lut[i] = (float)std::exp(i * i * gauss_color_coeff);
+    for (int i = 0; i < nlut; i++)
+        if (lut[i] == 0.0f)
+            return i + 1;
+    return nlut;
+}
+
+void jbf_space_taps(int radius, double sigma_space, std::vector<int> &di, std::vector<int> &dj,
+                    std::vector<float> &sw, std::vector<int> &hw)
+{
+    const double gauss_space_coeff = -0.5 / (sigma_space * sigma_space);
+    di.clear();
+    dj.clear();
+    sw.clear();
+    hw.assign(2 * radius + 1, -1);
+    for (int i = -radius; i <= radius; i++)
+        for (int j = -radius; j <= radius; j++) {
+            double r = std::sqrt((double)i * i + (double)j * j);
+            if (r > radius)
+                continue;
+            float wgt = (float)std::exp(r * r * gauss_space_coeff);
+            di.push_back(i);
+            dj.push_back(j);
+            sw.push_back(wgt);
+            if (j >= 0 && j > hw[i + radius])
+                hw[i + radius] = j;
+        }
+}
+
 namespace {
 
 constexpr int kTileW = 64;
@@ -189,34 +225,14 @@ int get_tables(int radius, int joint_cn, double sigma_color, double sigma_space,
     t.joint_cn = joint_cn;
     t.sigma_color = sigma_color;
     t.sigma_space = sigma_space;
-    const double gauss_color_coeff = -0.5 / (sigma_color * sigma_color);
-    const double gauss_space_coeff = -0.5 / (sigma_space * sigma_space);
     const int nlut = 256 * joint_cn;
-    std::vector<float> lut(nlut);
-    for (int i = 0; i < nlut; i++)
-        lut[i] = (float)std::exp(i * i * gauss_color_coeff);
+    std::vector<float> lut;
     // keep entries up to and including the first exact zero (the LUT is non-increasing)
-    t.lut_len = nlut;
-    for (int i = 0; i < nlut; i++)
-        if (lut[i] == 0.0f) {
-            t.lut_len = i + 1;
-            break;
-        }
+    t.lut_len = jbf_colour_lut(joint_cn, sigma_color, lut);
     const int d = 2 * radius + 1;
-    std::vector<int> di, dj, hw(d, -1);
+    std::vector<int> di, dj, hw;
     std::vector<float> sw;
-    for (int i = -radius; i <= radius; i++)
-        for (int j = -radius; j <= radius; j++) {
-            double r = std::sqrt((double)i * i + (double)j * j);
-            if (r > radius)
-                continue;
-            float wgt = (float)std::exp(r * r * gauss_space_coeff);
-            di.push_back(i);
-            dj.push_back(j);
-            sw.push_back(wgt);
-            if (j >= 0 && j > hw[i + radius])
-                hw[i + radius] = j;
-        }
+    jbf_space_taps(radius, sigma_space, di, dj, sw, hw);
     t.maxk = (int)di.size();
     t.r4 = (radius + 3) & ~3;
     t.sw_len = 2 * (t.r4 + 8);
@@ -306,20 +322,6 @@ int get_tables(int radius, int joint_cn, double sigma_color, double sigma_space,
     return RF_OK;
 }
 
-// Packs up to 3 interleaved bytes into the low bytes of a dword (byte 3 = 0), so that
-// v_sad_u8 on two such dwords is the L1 colour distance.
-// cn = -1: single-channel image treated as three equal channels (RF_JBF_GREY_AS_BGR).
-__device__ inline uint32_t load_packed(const uint8_t *img, size_t pix, int cn)
-{
-    if (cn < 0)
-        return (uint32_t)img[pix] * 0x010101u;
-    const uint8_t *p = img + pix * cn;
-    uint32_t v = p[0];
-    if (cn == 3)
-        v |= ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-    return v;
-}
-
 // Four consecutive pixels (cn interleaved bytes each, any alignment) -> four packed dwords.
 __device__ inline void load_packed4(const uint8_t *img, size_t pix, int cn, uint32_t (&out)[4])
 {
@@ -378,18 +380,6 @@ __device__ inline int xcd_contiguous_tile(int b, int nblocks)
 {
     const int per = nblocks >> 3;
     return b < (per << 3) ? (b & 7) * per + (b >> 3) : b;
-}
-
-__device__ inline void finish_pixel(uint8_t *o, const float *sum, float wsum, int scn, int flags)
-{
-    if (flags & RF_JBF_TRUE_DIVISION) {
-        for (int c = 0; c < scn; c++)
-            o[c] = saturate_u8(__fdiv_rn(sum[c], wsum));
-    } else {
-        const float inv = __fdiv_rn(1.0f, wsum);
-        for (int c = 0; c < scn; c++)
-            o[c] = saturate_u8(__fmul_rn(sum[c], inv));
-    }
 }
 
 __device__ inline float finish_value(float sum, float wsum_or_inv, int flags)

@@ -1,0 +1,350 @@
+// rf_jbf_points.hip -- the joint bilateral filter evaluated at listed pixels only, for many
+// parameter sets in one launch (rf_jbf_points_u8): the bilateral half of a WHDR parameter sweep.
+//
+// An output pixel of rf_jbf_u8 depends only on its own disk, so the bytes at a few hundred
+// judgement points per image can be computed directly, with the per-pixel arithmetic of
+// jbf_generic_kernel (rf_jbf.hip): taps in the d_di / d_dj order, w = sw[k] * lut[sad],
+// separately rounded multiply and add, sum * (1 / wsum) unless true division is asked for.
+//
+// Mapping: the parameter sets are grouped by sigma_space (one tap table, one radius per group)
+// and each group is cut into chunks of at most 64 sets.  A wave works on one chunk: its lanes are
+// (point, set) pairs, up to 64 / nsets points per wave (fewer while the launch would have under
+// 4096 waves), so every lane of a point reads the same texel
+// per tap (a broadcast) and the tap offsets and spatial weights are wave-uniform (scalar loads);
+// only the colour-table read differs per lane.  The tables are interleaved [sad][set] per chunk, so
+// the lanes of one point read neighbouring words.  Every output is one sequential chain over its
+// disk (no reduction across lanes: the summation order is the contract).  Chunks are issued in
+// order of decreasing radius, so the long chains start first.
+//
+// Tables: built on the host by the functions rf_jbf_u8's own cache uses (rf_jbf_common.hpp),
+// staged into the caller's workspace with one copy per call; the library's table cache
+// (g_tables in rf_jbf.hip) is not touched.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "rf_jbf_common.hpp"
+
+namespace rf {
+namespace {
+
+constexpr int kPtsMaxSets = 64;  // sets per chunk = lanes of a wave
+constexpr int kPtsWaves = 4;     // waves per workgroup
+constexpr int kPtsUnroll = 8;    // taps whose loads are issued before the first of them is added
+constexpr int kPtsMinWaves = 4096;  // waves a launch should have before lanes take several points
+
+struct PtsChunk {
+    int tap_off;     // first tap of the chunk's group in the tap table
+    int maxk;        // taps of the disk
+    int lut_off;     // first float of the chunk's interleaved colour tables
+    int nsets;       // parameter sets of the chunk (1..64)
+    int ppw;         // points per wave, 1 .. 64 / nsets
+    int item_begin;  // first work item (wave) of the chunk
+    int param[kPtsMaxSets];  // global index of each set
+};
+
+struct PtsGroup {
+    double sigma_space;
+    int radius;
+    int maxk;
+    std::vector<int> params;
+};
+
+// Radius rule and sigma rule of rf_jbf_u8.
+int points_radius(int d, double sigma_space)
+{
+    int radius = d <= 0 ? (int)std::lrint(sigma_space * 1.5) : d / 2;
+    return radius < 1 ? 1 : radius;
+}
+
+// Taps of the radius-r disk: the predicate of jbf_space_taps, without the weights.
+int disk_taps(int radius)
+{
+    long long count = 0;
+    for (int i = -radius; i <= radius; i++)
+        for (int j = -radius; j <= radius; j++)
+            if (!(std::sqrt((double)i * i + (double)j * j) > radius))
+                count++;
+    return (int)count;
+}
+
+struct PtsPlan {
+    std::vector<PtsGroup> groups;  // in launch order: decreasing radius
+    int nchunks = 0;
+    size_t taps = 0;               // entries of the tap table
+    size_t lut_floats = 0;
+    size_t off_chunks = 0, off_taps = 0, off_luts = 0, bytes = 0;
+};
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Groups, sizes and the workspace layout [chunks][taps][luts] of one call.  Fails on a radius
+// rf_jbf_u8 refuses.
+int plan_points(int n_params, const double *sigma_space, int d, int nlut, PtsPlan *plan)
+{
+    for (int p = 0; p < n_params; p++) {
+        const double ss = sigma_space[p] <= 0 ? 1 : sigma_space[p];
+        PtsGroup *g = nullptr;
+        for (PtsGroup &e : plan->groups)
+            if (e.sigma_space == ss)
+                g = &e;
+        if (!g) {
+            const int radius = points_radius(d, ss);
+            if (radius > 4096)
+                return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: radius %d too large", radius);
+            plan->groups.push_back(PtsGroup{ss, radius, 0, {}});
+            g = &plan->groups.back();
+        }
+        g->params.push_back(p);
+    }
+    std::stable_sort(plan->groups.begin(), plan->groups.end(),
+                     [](const PtsGroup &a, const PtsGroup &b) { return a.radius > b.radius; });
+    for (PtsGroup &g : plan->groups) {
+        g.maxk = disk_taps(g.radius);
+        plan->taps += (size_t)g.maxk;
+        plan->nchunks += ((int)g.params.size() + kPtsMaxSets - 1) / kPtsMaxSets;
+        plan->lut_floats += (size_t)nlut * g.params.size();
+    }
+    if (plan->taps > (size_t)0x7fffffff || plan->lut_floats > (size_t)0x7fffffff)
+        return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: tables too large for one call");
+    plan->off_chunks = 0;
+    plan->off_taps = align256(sizeof(PtsChunk) * plan->nchunks);
+    plan->off_luts = plan->off_taps + align256(sizeof(uint2) * plan->taps);
+    plan->bytes = plan->off_luts + align256(sizeof(float) * plan->lut_floats);
+    return RF_OK;
+}
+
+// One wave = one work item = up to 64 (point, set) lanes of one chunk.
+__global__ __launch_bounds__(64 * kPtsWaves) void jbf_points_kernel(
+    const uint8_t *__restrict__ joint, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+    int n, int h, int w, int jcn, int scn, int border, int flags, const int *__restrict__ points,
+    const int *__restrict__ point_offsets, int total, const PtsChunk *__restrict__ chunks,
+    int nchunks, const uint2 *__restrict__ taps, const float *__restrict__ luts, int items)
+{
+    const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * kPtsWaves + (threadIdx.x >> 6));
+    if (item >= items)
+        return;
+    // the chunk: last one with item_begin <= item (wave-uniform)
+    int lo = 0, hi = nchunks - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (chunks[mid].item_begin <= item)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    const PtsChunk *ch = chunks + lo;
+    const int nsets = ch->nsets;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane / nsets, s = lane - sub * nsets;
+    const int k = (item - ch->item_begin) * ch->ppw + sub;
+    const bool active = sub < ch->ppw && k < total;
+    // idle lanes follow point 0 through the loop (no divergence there) and write nothing.
+    // Points are validated by the caller; clamping keeps every read inside the images anyway.
+    const int kk = active ? k : 0;
+    const int px = min(max(points[2 * kk], 0), w - 1);
+    const int py = min(max(points[2 * kk + 1], 0), h - 1);
+    int ilo = 0, ihi = n - 1;  // the image: last i with point_offsets[i] <= kk
+    while (ilo < ihi) {
+        const int mid = (ilo + ihi + 1) >> 1;
+        if (point_offsets[mid] <= kk)
+            ilo = mid;
+        else
+            ihi = mid - 1;
+    }
+    const size_t img = (size_t)ilo * h * w;
+    const uint32_t j0 = load_packed(joint, img + (size_t)py * w + px, jcn);
+    const float *__restrict__ lut = luts + ch->lut_off + s;  // entry a of this set: lut[a * nsets]
+    const uint2 *__restrict__ tp = taps + ch->tap_off;
+    const int maxk = ch->maxk;
+    float sum[3] = {0.f, 0.f, 0.f};
+    float wsum = 0.f;
+    for (int t0 = 0; t0 < maxk; t0 += kPtsUnroll) {
+        const int cnt = min(kPtsUnroll, maxk - t0);
+        uint32_t jt[kPtsUnroll], st[kPtsUnroll];
+        float sw[kPtsUnroll], lw[kPtsUnroll];
+#pragma unroll
+        for (int u = 0; u < kPtsUnroll; u++) {
+            jt[u] = st[u] = 0u;
+            sw[u] = 0.f;
+            if (u < cnt) {
+                const uint2 tap = tp[t0 + u];
+                const int di = (int)tap.x >> 16;
+                const int dj = (int)(int16_t)(tap.x & 0xffffu);
+                sw[u] = __uint_as_float(tap.y);
+                const int yy = border_interpolate(py + di, h, border);
+                const int xx = border_interpolate(px + dj, w, border);
+                if (yy >= 0 && xx >= 0) {
+                    const size_t q = img + (size_t)yy * w + xx;
+                    jt[u] = load_packed(joint, q, jcn);
+                    st[u] = load_packed(src, q, scn);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kPtsUnroll; u++)
+            lw[u] = u < cnt ? lut[__builtin_amdgcn_sad_u8(j0, jt[u], 0u) * nsets] : 0.f;
+#pragma unroll
+        for (int u = 0; u < kPtsUnroll; u++) {
+            if (u < cnt) {
+                const float wgt = __fmul_rn(sw[u], lw[u]);
+                sum[0] = __fadd_rn(sum[0], __fmul_rn(wgt, (float)(st[u] & 0xff)));
+                if (scn == 3) {
+                    sum[1] = __fadd_rn(sum[1], __fmul_rn(wgt, (float)((st[u] >> 8) & 0xff)));
+                    sum[2] = __fadd_rn(sum[2], __fmul_rn(wgt, (float)((st[u] >> 16) & 0xff)));
+                }
+                wsum = __fadd_rn(wsum, wgt);
+            }
+        }
+    }
+    if (active)
+        finish_pixel(out + ((size_t)ch->param[s] * total + k) * scn, sum, wsum, scn, flags);
+}
+
+bool stream_capturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// The colour-table length (entries per set) of a call: 256 per joint channel, 768 for a grey
+// joint read as three equal channels.  0 = bad channel count.
+int points_nlut(int joint_cn, int flags)
+{
+    if (joint_cn != 1 && joint_cn != 3)
+        return 0;
+    return 256 * ((flags & RF_JBF_GREY_AS_BGR) ? 3 : joint_cn);
+}
+
+}  // namespace
+}  // namespace rf
+
+extern "C" size_t rf_jbf_points_workspace_bytes(int n_params, const double *sigma_space, int d,
+                                                int joint_cn, int flags)
+{
+    using namespace rf;
+    const int nlut = points_nlut(joint_cn, flags);
+    if (n_params <= 0 || !sigma_space || nlut == 0)
+        return 0;
+    PtsPlan plan;
+    if (plan_points(n_params, sigma_space, d, nlut, &plan) != RF_OK)
+        return 0;
+    return plan.bytes;
+}
+
+extern "C" int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n, int h, int w,
+                                int joint_cn, int src_cn, const int *points,
+                                const int *point_offsets, int total_points, int n_params,
+                                const double *sigma_color, const double *sigma_space, int d,
+                                int border, int flags, uint8_t *out, void *workspace,
+                                size_t workspace_bytes, void *stream_)
+{
+    using namespace rf;
+    if (n == 0)
+        return RF_OK;
+    if (!joint || !src || !points || !point_offsets || !out)
+        return fail(RF_E_BADARG, "rf_jbf_points_u8: NULL pointer");
+    if (n < 0 || h <= 0 || w <= 0 || total_points < 0)
+        return fail(RF_E_BADARG, "rf_jbf_points_u8: bad size n=%d h=%d w=%d total_points=%d", n,
+                    h, w, total_points);
+    if (n_params <= 0 || !sigma_color || !sigma_space)
+        return fail(RF_E_BADARG, "rf_jbf_points_u8: no parameter sets (n_params=%d)", n_params);
+    if ((joint_cn != 1 && joint_cn != 3) || (src_cn != 1 && src_cn != 3))
+        return fail(RF_E_UNSUPPORTED,
+                    "rf_jbf_points_u8: channels must be 1 or 3 (joint %d, src %d)", joint_cn,
+                    src_cn);
+    if (border < 0 || border > 4)
+        return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: border type %d", border);
+    if (flags & ~(RF_JBF_TRUE_DIVISION | RF_JBF_FORCE_GENERIC | RF_JBF_GREY_AS_BGR))
+        return fail(RF_E_BADARG, "rf_jbf_points_u8: unknown flag bits 0x%x", flags);
+    {
+        const size_t px = (size_t)n * h * w;
+        const size_t nout = (size_t)n_params * total_points * src_cn;
+        if (ranges_overlap(out, nout, joint, px * joint_cn) ||
+            ranges_overlap(out, nout, src, px * src_cn))
+            return fail(RF_E_BADARG, "rf_jbf_points_u8: out must not overlap an input");
+    }
+    // RF_JBF_GREY_AS_BGR as in rf_jbf_u8: only a 1-channel joint is affected
+    const int flags_eff = joint_cn == 1 ? flags : (flags & ~RF_JBF_GREY_AS_BGR);
+    const int nlut = points_nlut(joint_cn, flags_eff);
+    const int jcn_kernel = (flags_eff & RF_JBF_GREY_AS_BGR) ? -1 : joint_cn;
+    PtsPlan plan;
+    int rc = plan_points(n_params, sigma_space, d, nlut, &plan);
+    if (rc != RF_OK)
+        return rc;
+    if (!workspace || workspace_bytes < plan.bytes)
+        return fail(RF_E_WORKSPACE, "rf_jbf_points_u8: workspace of %zu bytes, %zu needed",
+                    workspace ? workspace_bytes : (size_t)0, plan.bytes);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (stream_capturing(stream))
+        return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: synchronises its stream and cannot be "
+                                      "captured into a graph");
+    if (total_points == 0)
+        return RF_OK;
+
+    // ---- tables: one host image of the workspace, copied with one call --------------------
+    std::vector<char> image(plan.bytes, 0);
+    PtsChunk *chunks = reinterpret_cast<PtsChunk *>(image.data() + plan.off_chunks);
+    uint2 *taps = reinterpret_cast<uint2 *>(image.data() + plan.off_taps);
+    float *luts = reinterpret_cast<float *>(image.data() + plan.off_luts);
+    int tap_off = 0, lut_off = 0, item = 0, c = 0;
+    std::vector<int> di, dj, hw;
+    std::vector<float> sw, lut;
+    for (const PtsGroup &g : plan.groups) {
+        jbf_space_taps(g.radius, g.sigma_space, di, dj, sw, hw);
+        if ((int)di.size() != g.maxk)
+            return fail(RF_E_HIP, "rf_jbf_points_u8: tap count mismatch (internal)");
+        for (int t = 0; t < g.maxk; t++) {
+            taps[tap_off + t].x = ((uint32_t)di[t] << 16) | ((uint32_t)dj[t] & 0xffffu);
+            uint32_t bits;
+            std::memcpy(&bits, &sw[t], 4);
+            taps[tap_off + t].y = bits;
+        }
+        for (size_t first = 0; first < g.params.size(); first += kPtsMaxSets) {
+            PtsChunk &ch = chunks[c++];
+            ch.tap_off = tap_off;
+            ch.maxk = g.maxk;
+            ch.lut_off = lut_off;
+            ch.nsets = (int)std::min(g.params.size() - first, (size_t)kPtsMaxSets);
+            // points per wave: as many as the lanes hold once the launch has enough waves to
+            // fill the chip; below that, fewer (down to one), so that short lists still spread
+            // their chains over many waves (a chain is latency-bound, lanes are not the limit)
+            ch.ppw = std::max(1, std::min(kPtsMaxSets / ch.nsets,
+                                          (int)(((long long)total_points * plan.nchunks) /
+                                                kPtsMinWaves)));
+            ch.item_begin = item;
+            for (int s = 0; s < ch.nsets; s++) {
+                const int p = g.params[first + s];
+                ch.param[s] = p;
+                const double sc = sigma_color[p] <= 0 ? 1 : sigma_color[p];
+                jbf_colour_lut(nlut / 256, sc, lut);
+                for (int a = 0; a < nlut; a++)
+                    luts[lut_off + (size_t)a * ch.nsets + s] = lut[a];
+            }
+            lut_off += nlut * ch.nsets;
+            const long long next = item + ((long long)total_points + ch.ppw - 1) / ch.ppw;
+            if (next > 0x7fffffffLL - kPtsWaves)
+                return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: too many points for one launch");
+            item = (int)next;
+        }
+        tap_off += g.maxk;
+    }
+    // the host image must outlive the copy: the copy is waited for before the launch (this is
+    // the call's one synchronisation of `stream`)
+    RF_HIP_CHECK(hipMemcpyAsync(workspace, image.data(), plan.bytes, hipMemcpyHostToDevice, stream));
+    RF_HIP_CHECK(hipStreamSynchronize(stream));
+    char *ws = static_cast<char *>(workspace);
+    const int blocks = (item + kPtsWaves - 1) / kPtsWaves;
+    hipLaunchKernelGGL(jbf_points_kernel, dim3(blocks), dim3(64 * kPtsWaves), 0, stream, joint, src,
+                       out, n, h, w, jcn_kernel, src_cn, border, flags_eff, points, point_offsets,
+                       total_points, reinterpret_cast<const PtsChunk *>(ws + plan.off_chunks),
+                       plan.nchunks, reinterpret_cast<const uint2 *>(ws + plan.off_taps),
+                       reinterpret_cast<const float *>(ws + plan.off_luts), item);
+    RF_HIP_CHECK(hipGetLastError());
+    return RF_OK;
+}

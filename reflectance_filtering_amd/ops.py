@@ -49,6 +49,69 @@ def joint_bilateral_u8(joint, src, d, sigma_color, sigma_space, border=_ffi.BORD
     return out
 
 
+def check_points(points, point_offsets, n, h, w):
+    """Host copies of a point list for images of h x w: int32 [total,2] (x, y) and int32 [n+1]
+    offsets, checked (the C entry cannot read device points to check them)."""
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.int64).reshape(-1, 2))
+    off = np.asarray(point_offsets, dtype=np.int64).ravel()
+    if off.shape[0] != n + 1 or off[0] != 0 or off[-1] != pts.shape[0] or np.any(np.diff(off) < 0):
+        raise ValueError("point_offsets must be %d non-decreasing values from 0 to the number of "
+                         "points" % (n + 1))
+    if pts.shape[0] and (pts.min() < 0 or pts[:, 0].max() >= w or pts[:, 1].max() >= h):
+        raise IndexError("point outside the %dx%d images" % (w, h))
+    if pts.shape[0] >= 2 ** 31:
+        raise ValueError("too many points")
+    return pts.astype(np.int32), off.astype(np.int32)
+
+
+def joint_bilateral_points_u8(joint, src, points, point_offsets, sigma_pairs, d=-1,
+                              border=_ffi.BORDER_DEFAULT, flags=0, grey_as_bgr=False):
+    """joint_bilateral_u8 evaluated at listed pixels only, for many (sigma_color, sigma_space)
+    pairs in one launch (rf_jbf_points_u8): returns CUDA uint8 [P, total, src_cn] with
+    out[p, k] = joint_bilateral_u8(joint, src, d, *sigma_pairs[p], border, flags)[i, y_k, x_k],
+    byte for byte, where point k = (x_k, y_k) = points[k] belongs to image i
+    (point_offsets[i] <= k < point_offsets[i+1]).  points / point_offsets are host arrays (or
+    tensors, copied to the host) and are checked there.  Synchronises the current stream."""
+    if grey_as_bgr:
+        flags |= _ffi.JBF_GREY_AS_BGR
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    _chk_images(joint, "joint", torch)
+    _chk_images(src, "src", torch)
+    if joint.shape[:3] != src.shape[:3]:
+        raise ValueError("joint and src must have the same N,H,W")
+    n, h, w, scn = src.shape
+    if torch.is_tensor(points):
+        points = points.cpu().numpy()
+    if torch.is_tensor(point_offsets):
+        point_offsets = point_offsets.cpu().numpy()
+    pts, off = check_points(points, point_offsets, n, h, w)
+    pairs = np.asarray(sigma_pairs, dtype=np.float64).reshape(-1, 2)
+    if pairs.shape[0] == 0:
+        raise ValueError("sigma_pairs is empty")
+    sc = np.ascontiguousarray(pairs[:, 0])
+    ss = np.ascontiguousarray(pairs[:, 1])
+    total = pts.shape[0]
+    dev = src.device
+    out = torch.empty((pairs.shape[0], total, scn), dtype=torch.uint8, device=dev)
+    need = lib.rf_jbf_points_workspace_bytes(pairs.shape[0], ss.ctypes.data, int(d),
+                                             joint.shape[3], int(flags))
+    if n == 0 or total == 0:
+        return out
+    if need == 0:   # arguments the entry refuses: let it say why
+        need = 1
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    d_pts = torch.from_numpy(pts).to(dev)
+    d_off = torch.from_numpy(off).to(dev)
+    rc = lib.rf_jbf_points_u8(joint.data_ptr(), src.data_ptr(), n, h, w, joint.shape[3], scn,
+                              d_pts.data_ptr(), d_off.data_ptr(), total, pairs.shape[0],
+                              sc.ctypes.data, ss.ctypes.data, int(d), int(border), int(flags),
+                              out.data_ptr(), ws.data_ptr(), ws.numel(),
+                              _ffi.current_stream_ptr(torch))
+    _ffi.check(rc, "rf_jbf_points_u8")
+    return out
+
+
 def gf_workspace(n, h, w, scn, radius, device, torch):
     """Guided-filter scratch for the CURRENT stream of `device`, cached per (device, stream):
     two streams (or threads with their own streams) never share planes.  The cache keeps one

@@ -144,3 +144,177 @@ def whdr_batch(reflectances, comparisons_px, delta=0.1):
                              _ffi.current_stream_ptr(torch))
         _ffi.check(rc, "rf_whdr_f32")
     return out.cpu().numpy()
+
+
+def dedup_points(comparisons_px, height, width):
+    """The point lists of rf_jbf_points_u8 / rf_whdr_points_u8 for judgements in pixel
+    coordinates (IIW comparisons share points): per image the distinct (x, y) of its comparisons,
+    sorted by (x, y), and each comparison re-indexed into them.  Coordinates are truncated to int
+    like whdr_batch does, and checked against the image size.
+    Returns (points int32 [total,2] (x, y), point_offsets int32 [n+1], comps int32 [m,3]
+    (index 1, index 2, darker), weights float64 [m], comp_offsets int32 [n+1])."""
+    n = len(comparisons_px)
+    point_offsets = np.zeros(n + 1, dtype=np.int64)
+    comp_offsets = np.zeros(n + 1, dtype=np.int64)
+    pts, comps, wts = [], [], []
+    for i, comp in enumerate(comparisons_px):
+        comp = np.asarray(comp, dtype=np.float64).reshape(-1, 6)
+        xy = comp[:, :4].astype(np.int64)
+        if comp.shape[0] and (xy.min() < 0 or xy[:, [0, 2]].max() >= width
+                              or xy[:, [1, 3]].max() >= height):
+            raise IndexError("comparison point outside the %dx%d image %d" % (width, height, i))
+        both = np.concatenate([xy[:, 0:2], xy[:, 2:4]], axis=0)
+        uniq, inverse = np.unique(both, axis=0, return_inverse=True)
+        inverse = inverse.reshape(-1)
+        m = comp.shape[0]
+        pts.append(uniq.reshape(-1, 2))
+        comps.append(np.stack([inverse[:m], inverse[m:], comp[:, 4].astype(np.int64)], axis=1))
+        wts.append(comp[:, 5])
+        point_offsets[i + 1] = point_offsets[i] + uniq.shape[0]
+        comp_offsets[i + 1] = comp_offsets[i] + m
+    cat = (lambda parts, shape: np.concatenate(parts, axis=0) if parts else np.zeros(shape))
+    if comp_offsets[-1] >= 2 ** 31 or point_offsets[-1] >= 2 ** 31:
+        raise ValueError("too many comparisons")
+    return (cat(pts, (0, 2)).astype(np.int32), point_offsets.astype(np.int32),
+            cat(comps, (0, 3)).astype(np.int32), cat(wts, (0,)).astype(np.float64),
+            comp_offsets.astype(np.int32))
+
+
+def whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta=0.1):
+    """WHDR of uint8 predictions sampled at points (rf_whdr_points_u8): samples is CUDA uint8
+    [S, total, C] (C = 1 or 3; e.g. ops.joint_bilateral_points_u8's output), the other arrays as
+    dedup_points returns them.  Each byte counts as float32(byte) / 255; returns float64 [S, n]
+    (host), equal bit for bit to whdr_batch on the float32 images bytes / 255."""
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    if not (torch.is_tensor(samples) and samples.is_cuda and samples.dtype == torch.uint8
+            and samples.is_contiguous() and samples.dim() == 3):
+        raise ValueError("samples must be a contiguous CUDA uint8 tensor [S, total, C]")
+    n_sets, total, c = samples.shape
+    if c not in (1, 3):
+        raise Exception("Expecting 1 or 3 channels to compute lightness!")
+    point_offsets = np.asarray(point_offsets, dtype=np.int64).ravel()
+    comp_offsets = np.asarray(comp_offsets, dtype=np.int64).ravel()
+    comps = np.asarray(comps, dtype=np.int64).reshape(-1, 3)
+    weights = np.asarray(weights, dtype=np.float64).ravel()
+    n = comp_offsets.shape[0] - 1
+    if n < 0 or point_offsets.shape[0] < n or comps.shape[0] != weights.shape[0] \
+            or comp_offsets[-1] != comps.shape[0]:
+        raise ValueError("inconsistent point / comparison arrays")
+    # indices must stay inside their image's points (the device entry cannot check them)
+    for i in range(n):
+        k0, k1 = comp_offsets[i], comp_offsets[i + 1]
+        size = (point_offsets[i + 1] if i + 1 < point_offsets.shape[0] else total) - point_offsets[i]
+        if k1 > k0 and (comps[k0:k1, :2].min() < 0 or comps[k0:k1, :2].max() >= size):
+            raise IndexError("comparison index outside the points of image %d" % i)
+    out = np.zeros((n_sets, n), dtype=np.float64)
+    if n == 0 or n_sets == 0 or total == 0 or comps.shape[0] == 0:
+        return out
+    dev = samples.device
+    up = (lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev))
+    d_po, d_co = up(point_offsets[:n], np.int32), up(comp_offsets, np.int32)
+    d_comps, d_wts = up(comps, np.int32), up(weights, np.float64)
+    d_out = torch.empty(n_sets * n, dtype=torch.float64, device=dev)
+    rc = lib.rf_whdr_points_u8(samples.data_ptr(), n_sets, total, c, n, d_po.data_ptr(),
+                               d_comps.data_ptr(), d_wts.data_ptr(), d_co.data_ptr(), float(delta),
+                               d_out.data_ptr(), _ffi.current_stream_ptr(torch))
+    _ffi.check(rc, "rf_whdr_points_u8")
+    return d_out.cpu().numpy().reshape(n_sets, n)
+
+
+# bytes of filtered images held at once by the guided half of a sweep (one group of pairs)
+SWEEP_GUIDED_BYTES = 1 << 30
+
+
+def _sweep_batch(filter_type, src, joint, comparisons_px, pairs, delta, grey_as_bgr):
+    """sweep() on one device batch of equal-size images: float64 [P, N]."""
+    import torch
+    from . import ops
+    n, h, w, c = src.shape
+    pts, point_offsets, comps, weights, comp_offsets = dedup_points(comparisons_px, h, w)
+    out = np.zeros((pairs.shape[0], n), dtype=np.float64)
+    if comps.shape[0] == 0:
+        return out
+    if filter_type == "bilateral":
+        samples = ops.joint_bilateral_points_u8(joint, src, pts, point_offsets, pairs, d=-1,
+                                                grey_as_bgr=grey_as_bgr)
+        return whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta)
+    # guided: full passes (its window sums are sequential chains by contract, a point cannot be
+    # evaluated on its own); the whole images are the point lists: pixel index y * w + x
+    npx = h * w
+    image_offsets = np.arange(n + 1, dtype=np.int64) * npx
+    px_comps = comps.copy()
+    for i in range(n):
+        k0, k1 = comp_offsets[i], comp_offsets[i + 1]
+        own = pts[point_offsets[i]:point_offsets[i + 1]].astype(np.int64)
+        for col in (0, 1):
+            q = own[comps[k0:k1, col]]
+            px_comps[k0:k1, col] = q[:, 1] * w + q[:, 0]
+    per = max(1, SWEEP_GUIDED_BYTES // max(1, n * npx * c))
+    for p0 in range(0, pairs.shape[0], per):
+        chunk = pairs[p0:p0 + per]
+        filtered = torch.empty((chunk.shape[0], n, h, w, c), dtype=torch.uint8, device=src.device)
+        for j, (sc, ss) in enumerate(chunk):
+            ops.guided_filter_u8(joint, src, int(ss), float(sc), out=filtered[j],
+                                 grey_as_bgr=grey_as_bgr)
+        out[p0:p0 + chunk.shape[0]] = whdr_points_u8(
+            filtered.view(chunk.shape[0], n * npx, c), image_offsets, px_comps, weights,
+            comp_offsets, delta)
+    return out
+
+
+def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_as_bgr=False):
+    """WHDR of filter(joint, src) for every (sigma_color, sigma_space) pair: float64 [P, N] on the
+    host, row p = pair p, column i = image i in the caller's order.
+
+    src / joint: CUDA uint8 batches [N,H,W,C], or lists of N images (CUDA tensors or numpy
+    arrays [H,W,C]) that may differ in size: equal-size runs are batched (batch.group_by_shape).
+    comparisons_px: N arrays [n_i,6] in pixel coordinates (to_pixels).  grey_as_bgr: the joint
+    has one channel and counts as three equal ones (as in ops.joint_bilateral_u8).
+      'bilateral'  joint_bilateral_u8(joint, src, -1, sigma_color, sigma_space) evaluated at the
+                   judgement points only (ops.joint_bilateral_points_u8: the same bytes), points
+                   deduplicated per image;
+      'guided'     guided_filter_u8(joint, src, int(sigma_space), sigma_color), full passes.
+    Each result equals whdr_batch on the filtered bytes as float32 / 255 (planar), bit for bit."""
+    from . import filter_reflectance as fr
+    from .batch import group_by_shape
+    import torch
+    pairs = np.asarray(sigma_pairs, dtype=np.float64).reshape(-1, 2)
+    if pairs.shape[0] == 0:
+        raise ValueError("sigma_pairs is empty")
+    for sc, ss in pairs:
+        fr._check_params(filter_type, sc, ss)
+    if torch.is_tensor(src):
+        if not torch.is_tensor(joint) or src.dim() != 4:
+            raise ValueError("src and joint must both be CUDA batches [N,H,W,C] or both lists")
+        if len(comparisons_px) != src.shape[0]:
+            raise ValueError("one comparison array per image")
+        _ffi.require_gpu()
+        return _sweep_batch(filter_type, src, joint, comparisons_px, pairs, delta, grey_as_bgr)
+    src, joint = list(src), list(joint)
+    if len(src) != len(joint) or len(src) != len(comparisons_px):
+        raise ValueError("src, joint and comparisons_px must have one entry per image")
+    for img, comp in zip(src, comparisons_px):   # points are checked before any device work
+        dedup_points([comp], img.shape[0], img.shape[1])
+    _ffi.require_gpu()
+
+    out = np.zeros((pairs.shape[0], len(src)), dtype=np.float64)
+    order = list(range(len(src)))
+    # (1 GiB runs: the guided half addresses a run's pixels with int32 offsets)
+    def key(i):   # (H, W, src channels, joint channels): equal keys batch together
+        s_shape, j_shape = tuple(src[i].shape), tuple(joint[i].shape)
+        return s_shape[:2] + ((s_shape + (1,))[2], (j_shape + (1,))[2])
+
+    for run in group_by_shape(order, key, max_bytes=1 << 30):
+        def stack(images):
+            parts = [torch.as_tensor(np.asarray(im)) if not torch.is_tensor(im) else im
+                     for im in images]
+            parts = [p.unsqueeze(-1) if p.dim() == 2 else p for p in parts]
+            return torch.stack([p.cuda() for p in parts]).contiguous()
+        s_b = stack([src[i] for i in run])
+        j_b = stack([joint[i] for i in run])
+        if s_b.shape[:3] != j_b.shape[:3]:
+            raise ValueError("src and joint images must have the same size")
+        out[:, run] = _sweep_batch(filter_type, s_b, j_b, [comparisons_px[i] for i in run], pairs,
+                                   delta, grey_as_bgr)
+    return out
