@@ -67,6 +67,10 @@
  * The grey-guide form of the guided filter (rf_gf_ex_u8 with RF_GF_GREY_AS_BGR) has no stage 1 for
  * "gf_guide_cache" and "gf_exact": while either is set, such a call returns RF_E_UNSUPPORTED.  Every
  * other switch above applies to it as to a colour guide.
+ *
+ * Besides the switches, rf_debug_jbf_points_plan reports the launch plan of rf_jbf_points_u8 (how
+ * its parameter sets are cut into chunks and how many points a wave of each chunk takes) without
+ * touching a device, so that tests can assert which lane mapping a call runs at.
  */
 #ifndef REFLECTANCE_FILTERING_DEBUG_H
 #define REFLECTANCE_FILTERING_DEBUG_H
@@ -89,6 +93,16 @@ int rf_debug_clock_probe(unsigned long long *out2, int micros, void *stream);
 /* The toolchain this library was compiled with (`hipcc --version`, first two lines): the inline-asm
  * hazard audit of tests/test_cabi.py holds for the machine code of that compiler. */
 const char *rf_debug_build_info(void);
+
+/* The launch plan of rf_jbf_points_u8(n_params sets with these sigma_space, d, joint_cn, flags) for
+ * a call of total_points points: per chunk, in launch order (decreasing radius; the sets of one
+ * sigma_space, after the `<= 0 -> 1` rule, in chunks of at most 64), the four ints
+ * {radius, nsets, ppw, waves} - ppw = points a wave takes, waves = ceil(total_points / ppw) - for the
+ * first max_chunks chunks at out[4 * chunk].  Decided by the code the entry launches from.  Returns
+ * the number of chunks of the call (it may exceed max_chunks; out may be NULL when max_chunks is 0),
+ * or a negative RF_E* for arguments the entry refuses.  Host only: needs no device. */
+int rf_debug_jbf_points_plan(int n_params, const double *sigma_space, int d, int joint_cn, int flags,
+                             int total_points, int *out, int max_chunks);
 
 #ifdef __cplusplus
 }

@@ -33,7 +33,8 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
            "rf_jbf_points_u8", "rf_whdr_points_u8")
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
-DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info")
+DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
+                 "rf_debug_jbf_points_plan")
 # switches that leave work out (wrong results, timing experiments only); all others keep the bytes
 RESULT_CHANGING_OPTIONS = ("jbf_stage_only", "gf_exp_skip")
 
@@ -110,6 +111,8 @@ def load_library():
         lib.rf_debug_clock_probe.restype = ci
         lib.rf_debug_build_info.argtypes = []
         lib.rf_debug_build_info.restype = ctypes.c_char_p
+        lib.rf_debug_jbf_points_plan.argtypes = [ci, vp, ci, ci, ci, ci, vp, ci]
+        lib.rf_debug_jbf_points_plan.restype = ci
         # RF_DEBUG_OPTIONS="name=value,...": preset the test / benchmark switches of
         # include/reflectance_filtering_debug.h for a whole process (timing experiments only).
         # Every preset is announced on stderr - loudly for the switches that change results.
@@ -166,6 +169,22 @@ def check(rc, what):
     if rc in (RF_E_BADARG, RF_E_UNSUPPORTED):
         raise ValueError("%s: %s" % (what, msg))
     raise RFError("%s failed (%d): %s" % (what, rc, msg))
+
+
+def jbf_points_plan(sigma_space, d, joint_cn, flags, total_points):
+    """The launch plan of rf_jbf_points_u8 for these arguments (rf_debug_jbf_points_plan, host
+    only): one (radius, nsets, ppw, waves) tuple per chunk, in launch order."""
+    import numpy as np
+    lib = load_library()
+    ss = np.ascontiguousarray(sigma_space, dtype=np.float64).ravel()
+    args = (ss.shape[0], ss.ctypes.data, int(d), int(joint_cn), int(flags), int(total_points))
+    nchunks = lib.rf_debug_jbf_points_plan(*(args + (None, 0)))
+    if nchunks < 0:
+        check(nchunks, "rf_debug_jbf_points_plan")
+    out = np.zeros((max(nchunks, 1), 4), dtype=np.int32)
+    if lib.rf_debug_jbf_points_plan(*(args + (out.ctypes.data, nchunks))) != nchunks:
+        raise RFError("rf_debug_jbf_points_plan: the chunk count changed between two calls")
+    return [tuple(int(v) for v in row) for row in out[:nchunks]]
 
 
 def require_gpu():

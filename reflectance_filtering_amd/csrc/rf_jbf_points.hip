@@ -24,6 +24,7 @@
 #include <cstring>
 #include <vector>
 
+#include "reflectance_filtering_debug.h"
 #include "rf_jbf_common.hpp"
 
 namespace rf {
@@ -69,9 +70,20 @@ int disk_taps(int radius)
     return (int)count;
 }
 
+// One chunk of the launch plan: sets [first, first + nsets) of a group, in launch order.
+struct PtsPlanChunk {
+    int group;        // index into PtsPlan::groups
+    int first;        // first set of the chunk within the group's params
+    int nsets;        // parameter sets of the chunk (1..64)
+    int ppw;          // points per wave, 1 .. 64 / nsets
+    long long waves;  // work items of the chunk: ceil(total_points / ppw)
+};
+
 struct PtsPlan {
     std::vector<PtsGroup> groups;  // in launch order: decreasing radius
+    std::vector<PtsPlanChunk> chunks;  // in launch order
     int nchunks = 0;
+    long long items = 0;           // waves of the launch (the sum over the chunks)
     size_t taps = 0;               // entries of the tap table
     size_t lut_floats = 0;
     size_t off_chunks = 0, off_taps = 0, off_luts = 0, bytes = 0;
@@ -79,9 +91,11 @@ struct PtsPlan {
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// Groups, sizes and the workspace layout [chunks][taps][luts] of one call.  Fails on a radius
-// rf_jbf_u8 refuses.
-int plan_points(int n_params, const double *sigma_space, int d, int nlut, PtsPlan *plan)
+// Groups, chunks with their points per wave, sizes and the workspace layout [chunks][taps][luts]
+// of one call of total_points points: the one place that decides what rf_jbf_points_u8 launches
+// (rf_debug_jbf_points_plan reports it).  Host only.  Fails on a radius rf_jbf_u8 refuses.
+int plan_points(int n_params, const double *sigma_space, int d, int nlut, int total_points,
+                PtsPlan *plan)
 {
     for (int p = 0; p < n_params; p++) {
         const double ss = sigma_space[p] <= 0 ? 1 : sigma_space[p];
@@ -112,8 +126,29 @@ int plan_points(int n_params, const double *sigma_space, int d, int nlut, PtsPla
     plan->off_taps = align256(sizeof(PtsChunk) * plan->nchunks);
     plan->off_luts = plan->off_taps + align256(sizeof(uint2) * plan->taps);
     plan->bytes = plan->off_luts + align256(sizeof(float) * plan->lut_floats);
+    for (size_t gi = 0; gi < plan->groups.size(); gi++) {
+        const size_t gsets = plan->groups[gi].params.size();
+        for (size_t first = 0; first < gsets; first += kPtsMaxSets) {
+            PtsPlanChunk pc;
+            pc.group = (int)gi;
+            pc.first = (int)first;
+            pc.nsets = (int)std::min(gsets - first, (size_t)kPtsMaxSets);
+            // points per wave: as many as the lanes hold once the launch has enough waves to
+            // fill the chip; below that, fewer (down to one), so that short lists still spread
+            // their chains over many waves (a chain is latency-bound, lanes are not the limit)
+            pc.ppw = std::max(1, std::min(kPtsMaxSets / pc.nsets,
+                                          (int)(((long long)total_points * plan->nchunks) /
+                                                kPtsMinWaves)));
+            pc.waves = ((long long)total_points + pc.ppw - 1) / pc.ppw;
+            plan->items += pc.waves;
+            plan->chunks.push_back(pc);
+        }
+    }
     return RF_OK;
 }
+
+// The launch addresses its waves with an int.
+bool plan_fits_one_launch(const PtsPlan &plan) { return plan.items <= 0x7fffffffLL - kPtsWaves; }
 
 // One wave = one work item = up to 64 (point, set) lanes of one chunk.
 __global__ __launch_bounds__(64 * kPtsWaves) void jbf_points_kernel(
@@ -232,9 +267,43 @@ extern "C" size_t rf_jbf_points_workspace_bytes(int n_params, const double *sigm
     if (n_params <= 0 || !sigma_space || nlut == 0)
         return 0;
     PtsPlan plan;
-    if (plan_points(n_params, sigma_space, d, nlut, &plan) != RF_OK)
+    if (plan_points(n_params, sigma_space, d, nlut, 0, &plan) != RF_OK)
         return 0;
     return plan.bytes;
+}
+
+extern "C" int rf_debug_jbf_points_plan(int n_params, const double *sigma_space, int d,
+                                        int joint_cn, int flags, int total_points, int *out,
+                                        int max_chunks)
+{
+    using namespace rf;
+    if (n_params <= 0 || !sigma_space)
+        return fail(RF_E_BADARG, "rf_debug_jbf_points_plan: no parameter sets (n_params=%d)",
+                    n_params);
+    if (total_points < 0 || max_chunks < 0 || (max_chunks > 0 && !out))
+        return fail(RF_E_BADARG, "rf_debug_jbf_points_plan: bad size total_points=%d max_chunks=%d",
+                    total_points, max_chunks);
+    if (joint_cn != 1 && joint_cn != 3)
+        return fail(RF_E_UNSUPPORTED, "rf_debug_jbf_points_plan: joint channels must be 1 or 3 (%d)",
+                    joint_cn);
+    if (flags & ~(RF_JBF_TRUE_DIVISION | RF_JBF_FORCE_GENERIC | RF_JBF_GREY_AS_BGR))
+        return fail(RF_E_BADARG, "rf_debug_jbf_points_plan: unknown flag bits 0x%x", flags);
+    const int flags_eff = joint_cn == 1 ? flags : (flags & ~RF_JBF_GREY_AS_BGR);
+    PtsPlan plan;
+    const int rc = plan_points(n_params, sigma_space, d, points_nlut(joint_cn, flags_eff),
+                               total_points, &plan);
+    if (rc != RF_OK)
+        return rc;
+    if (!plan_fits_one_launch(plan))
+        return fail(RF_E_UNSUPPORTED, "rf_debug_jbf_points_plan: too many points for one launch");
+    for (int c = 0; c < plan.nchunks && c < max_chunks; c++) {
+        const PtsPlanChunk &pc = plan.chunks[c];
+        out[4 * c + 0] = plan.groups[pc.group].radius;
+        out[4 * c + 1] = pc.nsets;
+        out[4 * c + 2] = pc.ppw;
+        out[4 * c + 3] = (int)pc.waves;
+    }
+    return plan.nchunks;
 }
 
 extern "C" int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n, int h, int w,
@@ -274,7 +343,7 @@ extern "C" int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n,
     const int nlut = points_nlut(joint_cn, flags_eff);
     const int jcn_kernel = (flags_eff & RF_JBF_GREY_AS_BGR) ? -1 : joint_cn;
     PtsPlan plan;
-    int rc = plan_points(n_params, sigma_space, d, nlut, &plan);
+    int rc = plan_points(n_params, sigma_space, d, nlut, total_points, &plan);
     if (rc != RF_OK)
         return rc;
     if (!workspace || workspace_bytes < plan.bytes)
@@ -286,16 +355,20 @@ extern "C" int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n,
                                       "captured into a graph");
     if (total_points == 0)
         return RF_OK;
+    if (!plan_fits_one_launch(plan))
+        return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: too many points for one launch");
 
     // ---- tables: one host image of the workspace, copied with one call --------------------
     std::vector<char> image(plan.bytes, 0);
     PtsChunk *chunks = reinterpret_cast<PtsChunk *>(image.data() + plan.off_chunks);
     uint2 *taps = reinterpret_cast<uint2 *>(image.data() + plan.off_taps);
     float *luts = reinterpret_cast<float *>(image.data() + plan.off_luts);
-    int tap_off = 0, lut_off = 0, item = 0, c = 0;
+    int tap_off = 0, lut_off = 0, item = 0;
+    size_t c = 0;
     std::vector<int> di, dj, hw;
     std::vector<float> sw, lut;
-    for (const PtsGroup &g : plan.groups) {
+    for (size_t gi = 0; gi < plan.groups.size(); gi++) {
+        const PtsGroup &g = plan.groups[gi];
         jbf_space_taps(g.radius, g.sigma_space, di, dj, sw, hw);
         if ((int)di.size() != g.maxk)
             return fail(RF_E_HIP, "rf_jbf_points_u8: tap count mismatch (internal)");
@@ -305,21 +378,17 @@ extern "C" int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n,
             std::memcpy(&bits, &sw[t], 4);
             taps[tap_off + t].y = bits;
         }
-        for (size_t first = 0; first < g.params.size(); first += kPtsMaxSets) {
-            PtsChunk &ch = chunks[c++];
+        for (; c < plan.chunks.size() && plan.chunks[c].group == (int)gi; c++) {
+            const PtsPlanChunk &pc = plan.chunks[c];
+            PtsChunk &ch = chunks[c];
             ch.tap_off = tap_off;
             ch.maxk = g.maxk;
             ch.lut_off = lut_off;
-            ch.nsets = (int)std::min(g.params.size() - first, (size_t)kPtsMaxSets);
-            // points per wave: as many as the lanes hold once the launch has enough waves to
-            // fill the chip; below that, fewer (down to one), so that short lists still spread
-            // their chains over many waves (a chain is latency-bound, lanes are not the limit)
-            ch.ppw = std::max(1, std::min(kPtsMaxSets / ch.nsets,
-                                          (int)(((long long)total_points * plan.nchunks) /
-                                                kPtsMinWaves)));
+            ch.nsets = pc.nsets;
+            ch.ppw = pc.ppw;
             ch.item_begin = item;
             for (int s = 0; s < ch.nsets; s++) {
-                const int p = g.params[first + s];
+                const int p = g.params[pc.first + s];
                 ch.param[s] = p;
                 const double sc = sigma_color[p] <= 0 ? 1 : sigma_color[p];
                 jbf_colour_lut(nlut / 256, sc, lut);
@@ -327,10 +396,7 @@ extern "C" int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n,
                     luts[lut_off + (size_t)a * ch.nsets + s] = lut[a];
             }
             lut_off += nlut * ch.nsets;
-            const long long next = item + ((long long)total_points + ch.ppw - 1) / ch.ppw;
-            if (next > 0x7fffffffLL - kPtsWaves)
-                return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: too many points for one launch");
-            item = (int)next;
+            item += (int)pc.waves;
         }
         tap_off += g.maxk;
     }

@@ -1,6 +1,7 @@
 """CPU suite: the point-evaluated joint bilateral (rf_jbf_points_u8), the sampled-byte WHDR
-(rf_whdr_points_u8) and the WHDR sweep's host side - refusals before any GPU work, the point
-deduplication, and the command line's grid parsing.  No compute calls."""
+(rf_whdr_points_u8) and the WHDR sweep's host side - refusals before any GPU work, the launch
+plan (rf_debug_jbf_points_plan: chunks and points per wave), the point deduplication, and the
+command line's grid parsing.  No compute calls."""
 import ctypes
 
 import numpy as np
@@ -72,6 +73,167 @@ def test_jbf_points_workspace_bytes(built):
     assert three > one
     # d > 0 fixes the radius whatever sigma_space is
     assert lib.rf_jbf_points_workspace_bytes(1, p_small, 3, 1, 0) < one
+
+
+# ---- the launch plan (rf_debug_jbf_points_plan) --------------------------------------------------
+# ppw = max(1, min(64 // nsets, total_points * nchunks // 4096)); every expected value below is
+# worked out by hand from that rule, none by a restatement of it in code.
+
+def _plan(ss, total, d=-1, jcn=3, flags=0):
+    return _ffi.jbf_points_plan(ss, d, jcn, flags, total)
+
+
+def test_points_plan_groups_sets_by_sigma_space(built):
+    # sigma_space <= 0 counts as 1, so -3, 0 and 1 are one group; radius = max(1, lrint(1.5 ss))
+    plan = _plan([22.0, 0.0, 4.0, 22.0, -3.0, 1.0, 4.0, 22.0], 10)
+    assert plan == [(33, 3, 1, 10), (6, 2, 1, 10), (2, 3, 1, 10)]
+    # groups are by sigma_space, not by radius: 3.9 and 4.1 both round to radius 6 and stay apart,
+    # in the caller's order (the sort by radius is stable)
+    assert _plan([4.1, 3.9, 4.1], 10) == [(6, 2, 1, 10), (6, 1, 1, 10)]
+    # d > 0 fixes the radius (d // 2) of every group; the groups remain
+    assert _plan([22.0, 4.0, 22.0], 10, d=9) == [(4, 2, 1, 10), (4, 1, 1, 10)]
+    assert _plan([0.2], 7) == [(1, 1, 1, 7)]                  # radius floor 1
+    # the channel count and the flags of the tables do not enter the plan
+    ss = [5.0] * 3 + [2.0] * 70
+    for jcn, flags in ((1, 0), (1, _ffi.JBF_GREY_AS_BGR), (3, _ffi.JBF_GREY_AS_BGR),
+                       (3, _ffi.JBF_TRUE_DIVISION | _ffi.JBF_FORCE_GENERIC)):
+        assert _plan(ss, 5000, jcn=jcn, flags=flags) == _plan(ss, 5000)
+
+
+def test_points_plan_chunks_hold_at_most_64_sets_by_decreasing_radius(built):
+    # 65 sets of one sigma: chunks of 64 and 1; 200 of another: 64, 64, 64, 8
+    ss = [2.0] * 30 + [6.0] * 65 + [2.0] * 170 + [4.0] * 64
+    plan = _plan(ss, 100)
+    assert [(r, n) for r, n, _, _ in plan] == [(9, 64), (9, 1), (6, 64), (3, 64), (3, 64), (3, 64),
+                                               (3, 8)]
+    assert all(ppw == 1 and waves == 100 for _, _, ppw, waves in plan)   # 100 * 7 < 8192
+    assert sum(n for _, n, _, _ in plan) == len(ss)
+
+
+def test_points_plan_points_per_wave_follow_the_rule(built):
+    # one chunk: total * 1 // 4096 is 1 at 8191, 2 at 8192
+    assert _plan([3.0], 8191) == [(4, 1, 1, 8191)]
+    assert _plan([3.0], 8192) == [(4, 1, 2, 4096)]
+    assert _plan([3.0], 4095) == [(4, 1, 1, 4095)]             # 0 -> the floor of 1
+    assert _plan([3.0], 0) == [(4, 1, 1, 0)]
+    # two chunks: 4095 * 2 = 8190 -> 1; 4096 * 2 = 8192 -> 2
+    assert _plan([3.0, 5.0], 4095) == [(8, 1, 1, 4095), (4, 1, 1, 4095)]
+    assert _plan([3.0, 5.0], 4096) == [(8, 1, 2, 2048), (4, 1, 2, 2048)]
+    # 65 sets = chunks of 64 and 1: 64 // 64 = 1 for the first whatever the cap; the second
+    # takes the cap 100000 * 2 // 4096 = 48, in ceil(100000 / 48) = 2084 waves
+    assert _plan([3.0] * 65, 100000) == [(4, 64, 1, 100000), (4, 1, 48, 2084)]
+    # nsets 1, 3, 5, 33, 64 in five chunks, cap 60000 * 5 // 4096 = 73: 64 // nsets decides;
+    # waves = ceil(60000 / ppw): 938 (64), 2858 (21), 5000 (12)
+    ss = [1.0] * 1 + [2.0] * 3 + [3.0] * 5 + [4.0] * 33 + [5.0] * 64
+    assert _plan(ss, 60000) == [(8, 64, 1, 60000), (6, 33, 1, 60000), (4, 5, 12, 5000),
+                                (3, 3, 21, 2858), (2, 1, 64, 938)]
+    # the same grid, cap 9000 * 5 // 4096 = 10: limits the chunks of 1, 3 and 5 sets alike
+    assert _plan(ss, 9000) == [(8, 64, 1, 9000), (6, 33, 1, 9000), (4, 5, 10, 900),
+                               (3, 3, 10, 900), (2, 1, 10, 900)]
+    # a last wave that is partly filled still counts: ceil(8193 / 2) = 4097
+    assert _plan([3.0], 8193) == [(4, 1, 2, 4097)]
+
+
+def test_points_plan_agrees_with_the_workspace_size(built):
+    """The workspace starts with one chunk record per planned chunk: with the tables unchanged
+    (same groups, same number of sets), 64 sets in one chunk or in two differ by the records
+    alone, and the chunk count the plan reports is the one the layout was sized for."""
+    lib = _ffi.load_library()
+
+    def bytes_of(ss, jcn=3, flags=0):
+        a, p = _dbl(ss)
+        return lib.rf_jbf_points_workspace_bytes(len(ss), p, -1, jcn, flags)
+
+    def layout(ss, jcn, flags):
+        """Restated layout: 256-aligned [chunk records][8-byte taps][float tables]."""
+        plan = _plan(ss, 0, jcn=jcn, flags=flags)
+        align = lambda b: (b + 255) & ~255
+        record = 4 * (6 + 64)
+        taps = 0
+        groups = {}
+        for v in ss:
+            groups.setdefault(1.0 if v <= 0 else v, 0)
+        for v in groups:
+            r = max(1, int(np.rint(v * 1.5)))
+            taps += sum(1 for i in range(-r, r + 1) for j in range(-r, r + 1)
+                        if not np.sqrt(float(i * i + j * j)) > r)
+        nlut = 256 * (3 if (flags & _ffi.JBF_GREY_AS_BGR and jcn == 1) else jcn)
+        return align(record * len(plan)) + align(8 * taps) + align(4 * nlut * len(ss))
+
+    for ss in ([22.0], [3.0] * 64, [3.0] * 65, [2.0] * 30 + [6.0] * 65 + [2.0] * 170,
+               [1.0, 0.0, -1.0, 5.0]):
+        for jcn, flags in ((3, 0), (1, 0), (1, _ffi.JBF_GREY_AS_BGR)):
+            assert bytes_of(ss, jcn, flags) == layout(ss, jcn, flags), (len(ss), jcn, flags)
+    # one more chunk record (a multiple of 256 once aligned) is the whole difference
+    assert len(_plan([3.0] * 64 + [3.0], 0)) == len(_plan([3.0] * 64, 0)) + 1
+
+
+def test_points_plan_refuses_what_the_entry_refuses(built):
+    lib = _ffi.load_library()
+    ss, p_ss = _dbl([22.0, 28.0])
+    out = (ctypes.c_int * 8)()
+
+    def call(n_params=2, p=p_ss, d=-1, jcn=1, flags=0, total=100, o=out, room=2):
+        return lib.rf_debug_jbf_points_plan(n_params, p, d, jcn, flags, total, o, room)
+
+    assert call() == 2
+    assert list(out) == [42, 1, 1, 100, 33, 1, 1, 100]
+    assert call(o=None, room=0) == 2                          # the count alone
+    out[4] = -7
+    assert call(room=1) == 2 and out[4] == -7                 # writes no more than max_chunks
+    assert call(n_params=0) == _ffi.RF_E_BADARG
+    assert call(p=None) == _ffi.RF_E_BADARG
+    assert call(total=-1) == _ffi.RF_E_BADARG
+    assert call(o=None) == _ffi.RF_E_BADARG
+    assert call(room=-1) == _ffi.RF_E_BADARG
+    assert call(jcn=2) == _ffi.RF_E_UNSUPPORTED
+    assert call(flags=8) == _ffi.RF_E_BADARG
+    assert b"flag" in lib.rf_last_error()
+    big, p_big = _dbl([20.0, 3000.0])                          # radius 4500 > 4096
+    assert call(p=p_big) == _ffi.RF_E_UNSUPPORTED
+    assert b"radius" in lib.rf_last_error()
+    # 2^31 - 1 points in two chunks of 64 sets: more waves than one launch addresses
+    many, p_many = _dbl([3.0] * 128)
+    assert call(n_params=128, p=p_many, total=2 ** 31 - 1, o=None, room=0) == _ffi.RF_E_UNSUPPORTED
+    with pytest.raises(ValueError):
+        _ffi.jbf_points_plan([22.0], -1, 2, 0, 10)
+
+
+def test_gpu_point_cases_run_at_many_points_per_wave(built):
+    """The coverage claim of tests/test_gpu_points_fuzz.py, checked without a GPU on the inputs
+    those tests build: cases a, b and d have chunks with ppw > 1, case a the nine hand-computed
+    values, and the first 16 fuzz cases alone meet every mapping class three times."""
+    from tests import test_gpu_points_fuzz as pf
+    pairs = pf.case_a_pairs()
+    pts, off = pf.case_a_points(4, 100, 130)
+    assert len(pairs) == 146 and pts.shape == (52000, 2) and off.tolist() == [0, 13000, 26000, 39000, 52000]
+    assert len(np.unique(pts[:13000], axis=0)) == 13000        # every pixel once
+    assert not np.array_equal(pts[:13000], pts[13000:26000])   # each image in an order of its own
+    plan = _plan([ss for _, ss in pairs], 52000)
+    assert [c[:3] for c in plan] == pf.A_PLAN_52000
+    assert [c[2] for c in plan] == [1, 4, 1, 4, 9, 12, 21, 32, 64]
+    for shape in pf.B_SHAPES:
+        for pool, ppw in zip(pf.B_POOLS, (2, 4)):
+            pts, off = pf.case_b_points(shape, pool)
+            per_image = np.diff(off)
+            assert per_image[list(pf.B_EMPTY)].tolist() == [0, 0]
+            assert np.all(np.abs(np.delete(per_image, pf.B_EMPTY) - pool) < 0.05 * pool)
+            plan = _plan([ss for _, ss in pf.B_PAIRS], int(off[-1]), jcn=1, flags=_ffi.JBF_GREY_AS_BGR)
+            assert [c[:3] for c in plan] == [(99, 1, ppw), (33, 2, ppw)], (shape, pool, plan)
+    total = whdr.dedup_points(pf.case_d_comparisons(), *pf.D_SHAPE)[0].shape[0]
+    plan = _plan([ss for _, ss in pf.D_PAIRS["bilateral"]], total, jcn=1, flags=_ffi.JBF_GREY_AS_BGR)
+    assert min(c[2] for c in plan) > 1, (total, plan)
+    rng = np.random.default_rng(65536)
+    seen = dict.fromkeys(pf.C_CLASSES, 0)
+    slabs = 0
+    for index in range(16):
+        case = pf.draw_fuzz_case(rng, index)
+        assert case["total"] == case["off"][-1] == case["pts"].shape[0] >= 1
+        assert case["pts"][:, 0].max() < case["w"] and case["pts"][:, 1].max() < case["h"]
+        for name in case["classes"]:
+            seen[name] += 1
+        slabs += case["slab"]
+    assert min(seen.values()) >= 3, seen
 
 
 def test_whdr_points_refusals_need_no_gpu(built):
