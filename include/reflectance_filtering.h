@@ -253,6 +253,35 @@ int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n, int h, int
                      void *stream);
 
 /*
+ * rf_jbf_points_u8 over images of different sizes (IIW photos come in many shapes): one call, one
+ * launch, whatever the sizes are.
+ *   joint, src     the n images tightly packed one after another: image i starts at pixel
+ *                  sum over j < i of heights[j] * widths[j] (offsets are formed in 64 bits) and is
+ *                  heights[i] rows of widths[i] pixels
+ *   heights, widths  n ints each, HOST memory (like the sigmas): every entry must be > 0
+ *   workspace      device scratch of at least rf_jbf_points_ragged_workspace_bytes(n, n_params,
+ *                  sigma_space, d, joint_cn, flags) bytes: rf_jbf_points_workspace_bytes of the same
+ *                  arguments plus one 256-byte-aligned block of 16 * n bytes (a record of first
+ *                  pixel, height and width per image, staged with the tables in the call's one copy);
+ *                  0 = arguments the call refuses
+ * Everything else is rf_jbf_points_u8's contract: out[p][k][c] is, byte for byte, what rf_jbf_u8 on
+ * image i alone (n = 1, heights[i], widths[i]) writes at pixel points[k]; the same radius, sigma,
+ * flag and border rules and refusals; out must not overlap an input (judged on the summed pixel
+ * count); n == 0 is RF_OK, total_points == 0 is RF_OK after the checks.  A point outside its image
+ * is clamped to that image's own size (unspecified bytes, never a read outside the buffers).
+ * The lanes run the code of rf_jbf_points_u8's kernel and the launch plan is the same function of
+ * total_points.  SYNCHRONISES THE STREAM once, and is refused on a capturing stream.
+ */
+size_t rf_jbf_points_ragged_workspace_bytes(int n, int n_params, const double *sigma_space, int d,
+                                            int joint_cn, int flags);
+int rf_jbf_points_ragged_u8(const uint8_t *joint, const uint8_t *src, int n, const int *heights,
+                            const int *widths, int joint_cn, int src_cn, const int *points,
+                            const int *point_offsets, int total_points, int n_params,
+                            const double *sigma_color, const double *sigma_space, int d, int border,
+                            int flags, uint8_t *out, void *workspace, size_t workspace_bytes,
+                            void *stream);
+
+/*
  * WHDR of uint8 predictions sampled at judgement points (rf_jbf_points_u8's output, or whole
  * images taken as point lists).
  *   samples        n_sets*set_stride*c uint8 device: pixel q of set s is at (s*set_stride + q)*c

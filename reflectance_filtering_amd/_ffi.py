@@ -30,7 +30,8 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
            "rf_cnn_reflectance_packed_u8", "rf_colorize_workspace_bytes",
            "rf_colorize_srgb_u8", "rf_whdr_f32", "rf_jbf_f32_workspace_bytes", "rf_jbf_f32",
            "rf_gf_f32_workspace_bytes", "rf_gf_f32", "rf_jbf_points_workspace_bytes",
-           "rf_jbf_points_u8", "rf_whdr_points_u8")
+           "rf_jbf_points_u8", "rf_jbf_points_ragged_workspace_bytes", "rf_jbf_points_ragged_u8",
+           "rf_whdr_points_u8")
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
@@ -102,6 +103,11 @@ def load_library():
         lib.rf_jbf_points_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, ci, ci,
                                          ci, vp, vp, sz, vp]
         lib.rf_jbf_points_u8.restype = ci
+        lib.rf_jbf_points_ragged_workspace_bytes.argtypes = [ci, ci, vp, ci, ci, ci]
+        lib.rf_jbf_points_ragged_workspace_bytes.restype = sz
+        lib.rf_jbf_points_ragged_u8.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, ci, ci, vp, vp, ci,
+                                                ci, ci, vp, vp, sz, vp]
+        lib.rf_jbf_points_ragged_u8.restype = ci
         lib.rf_whdr_points_u8.argtypes = [vp, ci, ctypes.c_longlong, ci, ci, vp, vp, vp, vp, cd, vp,
                                           vp]
         lib.rf_whdr_points_u8.restype = ci

@@ -19,6 +19,13 @@
 // Tables: built on the host by the functions rf_jbf_u8's own cache uses (rf_jbf_common.hpp),
 // staged into the caller's workspace with one copy per call; the library's table cache
 // (g_tables in rf_jbf.hip) is not touched.
+//
+// Ragged form (rf_jbf_points_ragged_u8): the images of a call may differ in size and lie packed one
+// after another.  Every lane already finds its image by a binary search over point_offsets and
+// reads single texels, so the only difference is where the image's first pixel, height and width
+// come from: a 16-byte record per image (staged behind the tables, in the same copy) instead of
+// i * h * w and the launch's h, w.  Both kernels are one lane body (jbf_points_lane<kRagged>);
+// the plan, the checks and the staging are shared (points_call).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -94,8 +101,8 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // Groups, chunks with their points per wave, sizes and the workspace layout [chunks][taps][luts]
 // of one call of total_points points: the one place that decides what rf_jbf_points_u8 launches
 // (rf_debug_jbf_points_plan reports it).  Host only.  Fails on a radius rf_jbf_u8 refuses.
-int plan_points(int n_params, const double *sigma_space, int d, int nlut, int total_points,
-                PtsPlan *plan)
+int plan_points(const char *who, int n_params, const double *sigma_space, int d, int nlut,
+                int total_points, PtsPlan *plan)
 {
     for (int p = 0; p < n_params; p++) {
         const double ss = sigma_space[p] <= 0 ? 1 : sigma_space[p];
@@ -106,7 +113,7 @@ int plan_points(int n_params, const double *sigma_space, int d, int nlut, int to
         if (!g) {
             const int radius = points_radius(d, ss);
             if (radius > 4096)
-                return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: radius %d too large", radius);
+                return fail(RF_E_UNSUPPORTED, "%s: radius %d too large", who, radius);
             plan->groups.push_back(PtsGroup{ss, radius, 0, {}});
             g = &plan->groups.back();
         }
@@ -121,7 +128,7 @@ int plan_points(int n_params, const double *sigma_space, int d, int nlut, int to
         plan->lut_floats += (size_t)nlut * g.params.size();
     }
     if (plan->taps > (size_t)0x7fffffff || plan->lut_floats > (size_t)0x7fffffff)
-        return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: tables too large for one call");
+        return fail(RF_E_UNSUPPORTED, "%s: tables too large for one call", who);
     plan->off_chunks = 0;
     plan->off_taps = align256(sizeof(PtsChunk) * plan->nchunks);
     plan->off_luts = plan->off_taps + align256(sizeof(uint2) * plan->taps);
@@ -150,12 +157,25 @@ int plan_points(int n_params, const double *sigma_space, int d, int nlut, int to
 // The launch addresses its waves with an int.
 bool plan_fits_one_launch(const PtsPlan &plan) { return plan.items <= 0x7fffffffLL - kPtsWaves; }
 
-// One wave = one work item = up to 64 (point, set) lanes of one chunk.
-__global__ __launch_bounds__(64 * kPtsWaves) void jbf_points_kernel(
+// One image of a ragged call (rf_jbf_points_ragged_u8): where its pixels start in the packed
+// buffers, and its size.
+struct alignas(16) PtsImage {
+    long long first;  // pixels before the image: the sum of h * w of the images in front of it
+    int h, w;
+};
+static_assert(sizeof(PtsImage) == 16, "the workspace holds 16 bytes per image");
+
+// One wave = one work item = up to 64 (point, set) lanes of one chunk.  The lane body of both
+// kernels: with kRagged the image's first pixel and size come from images[i] of the image the
+// lane's point belongs to (they differ between the lanes of a wave once ppw > 1), without it
+// every image is h x w (wave-uniform kernel arguments) and `images` is not read.
+template <bool kRagged>
+__device__ __forceinline__ void jbf_points_lane(
     const uint8_t *__restrict__ joint, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
-    int n, int h, int w, int jcn, int scn, int border, int flags, const int *__restrict__ points,
-    const int *__restrict__ point_offsets, int total, const PtsChunk *__restrict__ chunks,
-    int nchunks, const uint2 *__restrict__ taps, const float *__restrict__ luts, int items)
+    int n, int h, int w, const PtsImage *__restrict__ images, int jcn, int scn, int border,
+    int flags, const int *__restrict__ points, const int *__restrict__ point_offsets, int total,
+    const PtsChunk *__restrict__ chunks, int nchunks, const uint2 *__restrict__ taps,
+    const float *__restrict__ luts, int items)
 {
     const int item = __builtin_amdgcn_readfirstlane(blockIdx.x * kPtsWaves + (threadIdx.x >> 6));
     if (item >= items)
@@ -176,10 +196,9 @@ __global__ __launch_bounds__(64 * kPtsWaves) void jbf_points_kernel(
     const int k = (item - ch->item_begin) * ch->ppw + sub;
     const bool active = sub < ch->ppw && k < total;
     // idle lanes follow point 0 through the loop (no divergence there) and write nothing.
-    // Points are validated by the caller; clamping keeps every read inside the images anyway.
+    // Points are validated by the caller; clamping keeps every read inside the image anyway.
     const int kk = active ? k : 0;
-    const int px = min(max(points[2 * kk], 0), w - 1);
-    const int py = min(max(points[2 * kk + 1], 0), h - 1);
+    const int rx = points[2 * kk], ry = points[2 * kk + 1];
     int ilo = 0, ihi = n - 1;  // the image: last i with point_offsets[i] <= kk
     while (ilo < ihi) {
         const int mid = (ilo + ihi + 1) >> 1;
@@ -188,7 +207,17 @@ __global__ __launch_bounds__(64 * kPtsWaves) void jbf_points_kernel(
         else
             ihi = mid - 1;
     }
-    const size_t img = (size_t)ilo * h * w;
+    size_t img;
+    if (kRagged) {
+        const PtsImage im = images[ilo];
+        img = (size_t)im.first;
+        h = im.h;
+        w = im.w;
+    } else {
+        img = (size_t)ilo * h * w;
+    }
+    const int px = min(max(rx, 0), w - 1);
+    const int py = min(max(ry, 0), h - 1);
     const uint32_t j0 = load_packed(joint, img + (size_t)py * w + px, jcn);
     const float *__restrict__ lut = luts + ch->lut_off + s;  // entry a of this set: lut[a * nsets]
     const uint2 *__restrict__ tp = taps + ch->tap_off;
@@ -237,6 +266,28 @@ __global__ __launch_bounds__(64 * kPtsWaves) void jbf_points_kernel(
         finish_pixel(out + ((size_t)ch->param[s] * total + k) * scn, sum, wsum, scn, flags);
 }
 
+__global__ __launch_bounds__(64 * kPtsWaves) void jbf_points_kernel(
+    const uint8_t *__restrict__ joint, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+    int n, int h, int w, int jcn, int scn, int border, int flags, const int *__restrict__ points,
+    const int *__restrict__ point_offsets, int total, const PtsChunk *__restrict__ chunks,
+    int nchunks, const uint2 *__restrict__ taps, const float *__restrict__ luts, int items)
+{
+    jbf_points_lane<false>(joint, src, out, n, h, w, nullptr, jcn, scn, border, flags, points,
+                           point_offsets, total, chunks, nchunks, taps, luts, items);
+}
+
+// The same lanes over images of different sizes, packed one after another.
+__global__ __launch_bounds__(64 * kPtsWaves) void jbf_points_ragged_kernel(
+    const uint8_t *__restrict__ joint, const uint8_t *__restrict__ src, uint8_t *__restrict__ out,
+    int n, const PtsImage *__restrict__ images, int jcn, int scn, int border, int flags,
+    const int *__restrict__ points, const int *__restrict__ point_offsets, int total,
+    const PtsChunk *__restrict__ chunks, int nchunks, const uint2 *__restrict__ taps,
+    const float *__restrict__ luts, int items)
+{
+    jbf_points_lane<true>(joint, src, out, n, 0, 0, images, jcn, scn, border, flags, points,
+                          point_offsets, total, chunks, nchunks, taps, luts, items);
+}
+
 bool stream_capturing(hipStream_t stream)
 {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -267,7 +318,7 @@ extern "C" size_t rf_jbf_points_workspace_bytes(int n_params, const double *sigm
     if (n_params <= 0 || !sigma_space || nlut == 0)
         return 0;
     PtsPlan plan;
-    if (plan_points(n_params, sigma_space, d, nlut, 0, &plan) != RF_OK)
+    if (plan_points("rf_jbf_points_u8", n_params, sigma_space, d, nlut, 0, &plan) != RF_OK)
         return 0;
     return plan.bytes;
 }
@@ -290,8 +341,8 @@ extern "C" int rf_debug_jbf_points_plan(int n_params, const double *sigma_space,
         return fail(RF_E_BADARG, "rf_debug_jbf_points_plan: unknown flag bits 0x%x", flags);
     const int flags_eff = joint_cn == 1 ? flags : (flags & ~RF_JBF_GREY_AS_BGR);
     PtsPlan plan;
-    const int rc = plan_points(n_params, sigma_space, d, points_nlut(joint_cn, flags_eff),
-                               total_points, &plan);
+    const int rc = plan_points("rf_jbf_points_u8", n_params, sigma_space, d,
+                               points_nlut(joint_cn, flags_eff), total_points, &plan);
     if (rc != RF_OK)
         return rc;
     if (!plan_fits_one_launch(plan))
@@ -306,60 +357,82 @@ extern "C" int rf_debug_jbf_points_plan(int n_params, const double *sigma_space,
     return plan.nchunks;
 }
 
-extern "C" int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n, int h, int w,
-                                int joint_cn, int src_cn, const int *points,
-                                const int *point_offsets, int total_points, int n_params,
-                                const double *sigma_color, const double *sigma_space, int d,
-                                int border, int flags, uint8_t *out, void *workspace,
-                                size_t workspace_bytes, void *stream_)
+namespace rf {
+namespace {
+
+// Both entries: rf_jbf_points_u8 (heights == nullptr: n images of h x w) and
+// rf_jbf_points_ragged_u8 (heights / widths: n host ints each, images packed one after another).
+// The argument checks, the plan, the table staging and the launch; `who` names the entry.
+int points_call(const char *who, const uint8_t *joint, const uint8_t *src, int n, int h, int w,
+                const int *heights, const int *widths, bool ragged, int joint_cn, int src_cn,
+                const int *points, const int *point_offsets, int total_points, int n_params,
+                const double *sigma_color, const double *sigma_space, int d, int border, int flags,
+                uint8_t *out, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    using namespace rf;
     if (n == 0)
         return RF_OK;
-    if (!joint || !src || !points || !point_offsets || !out)
-        return fail(RF_E_BADARG, "rf_jbf_points_u8: NULL pointer");
-    if (n < 0 || h <= 0 || w <= 0 || total_points < 0)
-        return fail(RF_E_BADARG, "rf_jbf_points_u8: bad size n=%d h=%d w=%d total_points=%d", n,
-                    h, w, total_points);
+    if (!joint || !src || !points || !point_offsets || !out || (ragged && (!heights || !widths)))
+        return fail(RF_E_BADARG, "%s: NULL pointer", who);
+    if (ragged) {
+        if (n < 0 || total_points < 0)
+            return fail(RF_E_BADARG, "%s: bad size n=%d total_points=%d", who, n, total_points);
+    } else if (n < 0 || h <= 0 || w <= 0 || total_points < 0) {
+        return fail(RF_E_BADARG, "%s: bad size n=%d h=%d w=%d total_points=%d", who, n, h, w,
+                    total_points);
+    }
+    size_t px = 0;  // pixels of all images
+    if (ragged) {
+        for (int i = 0; i < n; i++) {
+            if (heights[i] <= 0 || widths[i] <= 0)
+                return fail(RF_E_BADARG, "%s: bad size of image %d: h=%d w=%d", who, i,
+                            heights[i], widths[i]);
+            px += (size_t)heights[i] * widths[i];
+            if (px > ((size_t)1 << 60))
+                return fail(RF_E_BADARG, "%s: the images hold too many pixels", who);
+        }
+    } else {
+        px = (size_t)n * h * w;
+    }
     if (n_params <= 0 || !sigma_color || !sigma_space)
-        return fail(RF_E_BADARG, "rf_jbf_points_u8: no parameter sets (n_params=%d)", n_params);
+        return fail(RF_E_BADARG, "%s: no parameter sets (n_params=%d)", who, n_params);
     if ((joint_cn != 1 && joint_cn != 3) || (src_cn != 1 && src_cn != 3))
-        return fail(RF_E_UNSUPPORTED,
-                    "rf_jbf_points_u8: channels must be 1 or 3 (joint %d, src %d)", joint_cn,
-                    src_cn);
+        return fail(RF_E_UNSUPPORTED, "%s: channels must be 1 or 3 (joint %d, src %d)", who,
+                    joint_cn, src_cn);
     if (border < 0 || border > 4)
-        return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: border type %d", border);
+        return fail(RF_E_UNSUPPORTED, "%s: border type %d", who, border);
     if (flags & ~(RF_JBF_TRUE_DIVISION | RF_JBF_FORCE_GENERIC | RF_JBF_GREY_AS_BGR))
-        return fail(RF_E_BADARG, "rf_jbf_points_u8: unknown flag bits 0x%x", flags);
+        return fail(RF_E_BADARG, "%s: unknown flag bits 0x%x", who, flags);
     {
-        const size_t px = (size_t)n * h * w;
         const size_t nout = (size_t)n_params * total_points * src_cn;
         if (ranges_overlap(out, nout, joint, px * joint_cn) ||
             ranges_overlap(out, nout, src, px * src_cn))
-            return fail(RF_E_BADARG, "rf_jbf_points_u8: out must not overlap an input");
+            return fail(RF_E_BADARG, "%s: out must not overlap an input", who);
     }
     // RF_JBF_GREY_AS_BGR as in rf_jbf_u8: only a 1-channel joint is affected
     const int flags_eff = joint_cn == 1 ? flags : (flags & ~RF_JBF_GREY_AS_BGR);
     const int nlut = points_nlut(joint_cn, flags_eff);
     const int jcn_kernel = (flags_eff & RF_JBF_GREY_AS_BGR) ? -1 : joint_cn;
     PtsPlan plan;
-    int rc = plan_points(n_params, sigma_space, d, nlut, total_points, &plan);
+    int rc = plan_points(who, n_params, sigma_space, d, nlut, total_points, &plan);
     if (rc != RF_OK)
         return rc;
-    if (!workspace || workspace_bytes < plan.bytes)
-        return fail(RF_E_WORKSPACE, "rf_jbf_points_u8: workspace of %zu bytes, %zu needed",
-                    workspace ? workspace_bytes : (size_t)0, plan.bytes);
+    // a ragged call keeps its image records behind the tables: [chunks][taps][luts][images]
+    const size_t off_images = plan.bytes;
+    const size_t bytes = plan.bytes + (ragged ? align256(sizeof(PtsImage) * (size_t)n) : 0);
+    if (!workspace || workspace_bytes < bytes)
+        return fail(RF_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
+                    workspace ? workspace_bytes : (size_t)0, bytes);
     hipStream_t stream = (hipStream_t)stream_;
     if (stream_capturing(stream))
-        return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: synchronises its stream and cannot be "
-                                      "captured into a graph");
+        return fail(RF_E_UNSUPPORTED, "%s: synchronises its stream and cannot be captured into a "
+                                      "graph", who);
     if (total_points == 0)
         return RF_OK;
     if (!plan_fits_one_launch(plan))
-        return fail(RF_E_UNSUPPORTED, "rf_jbf_points_u8: too many points for one launch");
+        return fail(RF_E_UNSUPPORTED, "%s: too many points for one launch", who);
 
     // ---- tables: one host image of the workspace, copied with one call --------------------
-    std::vector<char> image(plan.bytes, 0);
+    std::vector<char> image(bytes, 0);
     PtsChunk *chunks = reinterpret_cast<PtsChunk *>(image.data() + plan.off_chunks);
     uint2 *taps = reinterpret_cast<uint2 *>(image.data() + plan.off_taps);
     float *luts = reinterpret_cast<float *>(image.data() + plan.off_luts);
@@ -371,7 +444,7 @@ extern "C" int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n,
         const PtsGroup &g = plan.groups[gi];
         jbf_space_taps(g.radius, g.sigma_space, di, dj, sw, hw);
         if ((int)di.size() != g.maxk)
-            return fail(RF_E_HIP, "rf_jbf_points_u8: tap count mismatch (internal)");
+            return fail(RF_E_HIP, "%s: tap count mismatch (internal)", who);
         for (int t = 0; t < g.maxk; t++) {
             taps[tap_off + t].x = ((uint32_t)di[t] << 16) | ((uint32_t)dj[t] & 0xffffu);
             uint32_t bits;
@@ -400,17 +473,73 @@ extern "C" int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n,
         }
         tap_off += g.maxk;
     }
+    if (ragged) {
+        PtsImage *images = reinterpret_cast<PtsImage *>(image.data() + off_images);
+        long long first = 0;
+        for (int i = 0; i < n; i++) {
+            images[i] = PtsImage{first, heights[i], widths[i]};
+            first += (long long)heights[i] * widths[i];
+        }
+    }
     // the host image must outlive the copy: the copy is waited for before the launch (this is
     // the call's one synchronisation of `stream`)
-    RF_HIP_CHECK(hipMemcpyAsync(workspace, image.data(), plan.bytes, hipMemcpyHostToDevice, stream));
+    RF_HIP_CHECK(hipMemcpyAsync(workspace, image.data(), bytes, hipMemcpyHostToDevice, stream));
     RF_HIP_CHECK(hipStreamSynchronize(stream));
     char *ws = static_cast<char *>(workspace);
     const int blocks = (item + kPtsWaves - 1) / kPtsWaves;
-    hipLaunchKernelGGL(jbf_points_kernel, dim3(blocks), dim3(64 * kPtsWaves), 0, stream, joint, src,
-                       out, n, h, w, jcn_kernel, src_cn, border, flags_eff, points, point_offsets,
-                       total_points, reinterpret_cast<const PtsChunk *>(ws + plan.off_chunks),
-                       plan.nchunks, reinterpret_cast<const uint2 *>(ws + plan.off_taps),
-                       reinterpret_cast<const float *>(ws + plan.off_luts), item);
+    const PtsChunk *d_chunks = reinterpret_cast<const PtsChunk *>(ws + plan.off_chunks);
+    const uint2 *d_taps = reinterpret_cast<const uint2 *>(ws + plan.off_taps);
+    const float *d_luts = reinterpret_cast<const float *>(ws + plan.off_luts);
+    if (ragged)
+        hipLaunchKernelGGL(jbf_points_ragged_kernel, dim3(blocks), dim3(64 * kPtsWaves), 0, stream,
+                           joint, src, out, n, reinterpret_cast<const PtsImage *>(ws + off_images),
+                           jcn_kernel, src_cn, border, flags_eff, points, point_offsets,
+                           total_points, d_chunks, plan.nchunks, d_taps, d_luts, item);
+    else
+        hipLaunchKernelGGL(jbf_points_kernel, dim3(blocks), dim3(64 * kPtsWaves), 0, stream, joint,
+                           src, out, n, h, w, jcn_kernel, src_cn, border, flags_eff, points,
+                           point_offsets, total_points, d_chunks, plan.nchunks, d_taps, d_luts,
+                           item);
     RF_HIP_CHECK(hipGetLastError());
     return RF_OK;
+}
+
+}  // namespace
+}  // namespace rf
+
+extern "C" int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n, int h, int w,
+                                int joint_cn, int src_cn, const int *points,
+                                const int *point_offsets, int total_points, int n_params,
+                                const double *sigma_color, const double *sigma_space, int d,
+                                int border, int flags, uint8_t *out, void *workspace,
+                                size_t workspace_bytes, void *stream)
+{
+    return rf::points_call("rf_jbf_points_u8", joint, src, n, h, w, nullptr, nullptr, false,
+                           joint_cn, src_cn, points, point_offsets, total_points, n_params,
+                           sigma_color, sigma_space, d, border, flags, out, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" size_t rf_jbf_points_ragged_workspace_bytes(int n, int n_params,
+                                                       const double *sigma_space, int d,
+                                                       int joint_cn, int flags)
+{
+    const size_t tables = rf_jbf_points_workspace_bytes(n_params, sigma_space, d, joint_cn, flags);
+    if (n < 0 || tables == 0)
+        return 0;
+    return tables + rf::align256(sizeof(rf::PtsImage) * (size_t)n);
+}
+
+extern "C" int rf_jbf_points_ragged_u8(const uint8_t *joint, const uint8_t *src, int n,
+                                       const int *heights, const int *widths, int joint_cn,
+                                       int src_cn, const int *points, const int *point_offsets,
+                                       int total_points, int n_params, const double *sigma_color,
+                                       const double *sigma_space, int d, int border, int flags,
+                                       uint8_t *out, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    return rf::points_call("rf_jbf_points_ragged_u8", joint, src, n, 0, 0, heights, widths, true,
+                           joint_cn, src_cn, points, point_offsets, total_points, n_params,
+                           sigma_color, sigma_space, d, border, flags, out, workspace,
+                           workspace_bytes, stream);
 }

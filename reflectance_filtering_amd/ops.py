@@ -112,6 +112,116 @@ def joint_bilateral_points_u8(joint, src, points, point_offsets, sigma_pairs, d=
     return out
 
 
+def check_points_ragged(points, point_offsets, sizes):
+    """check_points for images of different sizes: sizes is [n,2] (h, w), and every point is held to
+    the size of its own image.  Returns int32 [total,2] (x, y) and int32 [n+1] offsets."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    n = sizes.shape[0]
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.int64).reshape(-1, 2))
+    off = np.asarray(point_offsets, dtype=np.int64).ravel()
+    if off.shape[0] != n + 1 or off[0] != 0 or off[-1] != pts.shape[0] or np.any(np.diff(off) < 0):
+        raise ValueError("point_offsets must be %d non-decreasing values from 0 to the number of "
+                         "points" % (n + 1))
+    if n and sizes.min() <= 0:
+        raise ValueError("image sizes must be positive")
+    hw = np.repeat(sizes, np.diff(off), axis=0)                 # the (h, w) each point is held to
+    bad = np.flatnonzero((pts < 0).any(axis=1) | (pts[:, 0] >= hw[:, 1]) | (pts[:, 1] >= hw[:, 0]))
+    if bad.size:
+        k = int(bad[0])
+        raise IndexError("point %d (x %d, y %d) outside the %dx%d image %d" % (
+            k, pts[k, 0], pts[k, 1], hw[k, 1], hw[k, 0], int(np.searchsorted(off, k, "right")) - 1))
+    if pts.shape[0] >= 2 ** 31:
+        raise ValueError("too many points")
+    return pts.astype(np.int32), off.astype(np.int32)
+
+
+def pack_images(images, name, torch):
+    """A list of CUDA uint8 images [H_i, W_i, C] (equal C) tightly packed one after another:
+    (tensor [total pixels, C], sizes int64 [n,2] (h, w)), with one torch.cat of flattened views."""
+    images = list(images)
+    if not images:
+        raise ValueError("%s is empty" % name)
+    for t in images:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8
+                and t.dim() == 3 and t.is_contiguous() and t.shape[2] == images[0].shape[2]):
+            raise ValueError("%s must be contiguous CUDA uint8 tensors [H,W,C] with equal C" % name)
+    sizes = np.array([t.shape[:2] for t in images], dtype=np.int64).reshape(-1, 2)
+    return torch.cat([t.view(-1, t.shape[2]) for t in images]), sizes
+
+
+def joint_bilateral_points_ragged_u8(joints, srcs, points, point_offsets, sigma_pairs, d=-1,
+                                     border=_ffi.BORDER_DEFAULT, flags=0, grey_as_bgr=False,
+                                     sizes=None):
+    """joint_bilateral_points_u8 over images of different sizes, in one launch
+    (rf_jbf_points_ragged_u8).  joints / srcs: lists of n CUDA uint8 tensors [H_i, W_i, C] (equal
+    C within a list; image i of both has the same H_i, W_i), or, with sizes = [n,2] (h, w), the
+    images already packed one after another as contiguous CUDA uint8 tensors [total pixels, C].
+    Returns CUDA uint8 [P, total, src_cn] with
+    out[p, k] = joint_bilateral_u8(joints[i][None], srcs[i][None], d, *sigma_pairs[p], ...)[0, y_k, x_k],
+    byte for byte, where point k = (x_k, y_k) = points[k] belongs to image i.  points /
+    point_offsets are host arrays, checked there against each image's own size.  Synchronises
+    the current stream."""
+    if grey_as_bgr:
+        flags |= _ffi.JBF_GREY_AS_BGR
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    if sizes is None:
+        same = joints is srcs
+        srcs, sizes = pack_images(srcs, "srcs", torch)
+        if same:
+            joints = srcs
+        else:
+            joints, jsizes = pack_images(joints, "joints", torch)
+            if not np.array_equal(sizes, jsizes):
+                raise ValueError("joints and srcs must have the same sizes image by image")
+    else:
+        sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+        if sizes.shape[0] and sizes.min() <= 0:
+            raise ValueError("image sizes must be positive")
+        npx = int((sizes[:, 0] * sizes[:, 1]).sum())
+        for t, name in ((joints, "joints"), (srcs, "srcs")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8
+                    and t.dim() == 2 and t.is_contiguous() and t.shape[0] == npx):
+                raise ValueError("%s must be a contiguous CUDA uint8 tensor [%d, C]: the pixels of "
+                                 "all images" % (name, npx))
+    n = sizes.shape[0]
+    scn = srcs.shape[1]
+    if torch.is_tensor(points):
+        points = points.cpu().numpy()
+    if torch.is_tensor(point_offsets):
+        point_offsets = point_offsets.cpu().numpy()
+    pts, off = check_points_ragged(points, point_offsets, sizes)
+    if sizes.size and sizes.max() >= 2 ** 31:
+        raise ValueError("image too large")
+    pairs = np.asarray(sigma_pairs, dtype=np.float64).reshape(-1, 2)
+    if pairs.shape[0] == 0:
+        raise ValueError("sigma_pairs is empty")
+    sc = np.ascontiguousarray(pairs[:, 0])
+    ss = np.ascontiguousarray(pairs[:, 1])
+    total = pts.shape[0]
+    dev = srcs.device
+    out = torch.empty((pairs.shape[0], total, scn), dtype=torch.uint8, device=dev)
+    if n == 0 or total == 0:
+        return out
+    need = lib.rf_jbf_points_ragged_workspace_bytes(n, pairs.shape[0], ss.ctypes.data, int(d),
+                                                    joints.shape[1], int(flags))
+    if need == 0:   # arguments the entry refuses: let it say why
+        need = 1
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    d_pts = torch.from_numpy(pts).to(dev)
+    d_off = torch.from_numpy(off).to(dev)
+    hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
+    wds = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
+    rc = lib.rf_jbf_points_ragged_u8(joints.data_ptr(), srcs.data_ptr(), n, hs.ctypes.data,
+                                     wds.ctypes.data, joints.shape[1], scn, d_pts.data_ptr(),
+                                     d_off.data_ptr(), total, pairs.shape[0], sc.ctypes.data,
+                                     ss.ctypes.data, int(d), int(border), int(flags),
+                                     out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     _ffi.current_stream_ptr(torch))
+    _ffi.check(rc, "rf_jbf_points_ragged_u8")
+    return out
+
+
 def gf_workspace(n, h, w, scn, radius, device, torch):
     """Guided-filter scratch for the CURRENT stream of `device`, cached per (device, stream):
     two streams (or threads with their own streams) never share planes.  The cache keeps one

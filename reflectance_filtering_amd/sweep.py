@@ -9,8 +9,8 @@ the reference's filter_reflectance.py:1) over IIW photos and their judgements, o
 Each photo `<stem>.png` comes with IIW judgements `<stem>.json` beside it.  The CNN predicts the
 reflectance bytes (`<stem>-r.png` of decompose_with_trained_CNN); the grid is the outer product
 of the two sigma lists; every pair filters the prediction and scores it with WHDR
-(whdr.sweep: the bilateral filter evaluated at the judgement points only, the guided filter in
-full passes).  --guidance cnn filters the prediction with itself as guidance (BF/GF(CNN, CNN),
+(the bilateral filter evaluated at the judgement points only, all photos of whatever sizes in one
+ragged call per pack of 2^30 pixels; the guided filter in full passes over equal-size batches).  --guidance cnn filters the prediction with itself as guidance (BF/GF(CNN, CNN),
 the bytes of decompose_and_filter_batch), --guidance image with the photo (the reference
 README's example call).  The JSON holds the grid, the mean WHDR per pair over the images that
 have judgements, the best pair and the image count; the npz the per-image matrix.
@@ -70,7 +70,32 @@ def run(photos, filter_type, sigma_color, sigma_spatial, guidance="cnn", delta=0
         comps.append(whdr.to_pixels(whdr.load_judgements(judgements_for(f)), img.shape[0],
                                     img.shape[1]))
     per_image = np.zeros((pairs.shape[0], len(photos)), dtype=np.float64)
-    for run_ in batch.group_by_shape(list(range(len(photos))), lambda i: images[i].shape):
+    if filter_type == "bilateral":
+        # The network is per pixel, so the photos of a pack - whatever their sizes - go through
+        # it as one image [1, 1, total pixels, 3], and the point sweep takes the packed bytes as
+        # they come out.  A pack stays under whdr.SWEEP_PACK_PIXELS = 2^30 pixels, inside the
+        # width rf_cnn_reflectance_packed_u8 accepts (a positive int).
+        sizes = [img.shape[:2] for img in images]
+        dedup = [whdr.dedup_points([c], h, w) for c, (h, w) in zip(comps, sizes)]
+        packs = whdr.plan_packs([0] * len(photos), [h * w for h, w in sizes],
+                                [int(d[1][-1]) for d in dedup], pairs.shape[0], lambda k: 1)
+        for pack in packs:
+            joined = whdr.join_dedup([dedup[i] for i in pack])
+            if joined[2].shape[0] == 0:
+                continue
+            bgr = torch.from_numpy(np.concatenate([images[i].reshape(-1, 3) for i in pack])).cuda()
+            _, r8 = ops.cnn_reflectance_u8(bgr.view(1, 1, -1, 3), want_float=False)
+            r1 = r8.view(-1, 1)
+            psizes = [sizes[i] for i in pack]
+            if guidance == "cnn":
+                res = whdr.sweep_packed(r1, r1, psizes, joined, pairs, delta, grey_as_bgr=True)
+            else:
+                res = whdr.sweep_packed(r1, bgr, psizes, joined, pairs, delta)
+            per_image[:, pack] = res
+        return pairs, per_image, np.array([c.shape[0] > 0 for c in comps], dtype=bool)
+    # guided: full passes need equal shapes, batched wherever they stand in the list
+    order = sorted(range(len(photos)), key=lambda i: images[i].shape)
+    for run_ in batch.group_by_shape(order, lambda i: images[i].shape):
         bgr = torch.from_numpy(np.stack([images[i] for i in run_])).cuda()
         _, r8 = ops.cnn_reflectance_u8(bgr, want_float=False)
         r1 = r8.unsqueeze(-1)

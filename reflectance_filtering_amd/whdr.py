@@ -263,18 +263,106 @@ def _sweep_batch(filter_type, src, joint, comparisons_px, pairs, delta, grey_as_
     return out
 
 
+# a ragged bilateral call holds at most this many pixels and this many output bytes
+SWEEP_PACK_PIXELS = 1 << 30
+SWEEP_PACK_OUT_BYTES = 1 << 30
+
+
+def join_dedup(parts):
+    """dedup_points results of single images joined into the arrays of one call over all of them
+    (comparison indices are relative to their image's points, so only the offsets accumulate)."""
+    ends = (lambda k: np.concatenate([[0], np.cumsum([p[k][1] for p in parts], dtype=np.int64)]))
+    point_offsets, comp_offsets = ends(1), ends(4)
+    if comp_offsets[-1] >= 2 ** 31 or point_offsets[-1] >= 2 ** 31:
+        raise ValueError("too many comparisons")
+    cat = (lambda k, shape, dt: np.concatenate([p[k] for p in parts], axis=0).astype(dt)
+           if parts else np.zeros(shape, dt))
+    return (cat(0, (0, 2), np.int32), point_offsets.astype(np.int32), cat(2, (0, 3), np.int32),
+            cat(3, (0,), np.float64), comp_offsets.astype(np.int32))
+
+
+def dedup_points_ragged(comparisons_px, sizes):
+    """dedup_points for images of different sizes: sizes[i] = (h_i, w_i), and the points of image i
+    are deduplicated and checked with its own size.  Returns what dedup_points returns."""
+    return join_dedup([dedup_points([comp], int(h), int(w))
+                       for comp, (h, w) in zip(comparisons_px, sizes)])
+
+
+def plan_packs(keys, pixels, points, n_pairs, src_cn):
+    """The ragged calls of a bilateral sweep over a list: image indices grouped by key (the channel
+    counts) wherever they stand in the list, each group cut so that a pack stays under
+    SWEEP_PACK_PIXELS pixels and n_pairs * points * src_cn[key] under SWEEP_PACK_OUT_BYTES output
+    bytes (an image over a limit on its own is a pack of one).  Host only."""
+    packs = []
+    for key in sorted(set(keys), key=keys.index):
+        per_point = n_pairs * src_cn(key)
+        cur, npx, npt = [], 0, 0
+        for i in (i for i, k in enumerate(keys) if k == key):
+            if cur and (npx + pixels[i] > SWEEP_PACK_PIXELS
+                        or (npt + points[i]) * per_point > SWEEP_PACK_OUT_BYTES):
+                packs.append(cur)
+                cur, npx, npt = [], 0, 0
+            cur.append(i)
+            npx += pixels[i]
+            npt += points[i]
+        if cur:
+            packs.append(cur)
+    return packs
+
+
+def sweep_packed(src, joint, sizes, dedup, pairs, delta=0.1, grey_as_bgr=False):
+    """The bilateral sweep on one pack: images of sizes[i] = (h_i, w_i) packed one after another in
+    the CUDA uint8 tensors src / joint [total pixels, C], dedup = dedup_points_ragged of their
+    comparisons.  One ragged filter call and one WHDR call: float64 [P, n]."""
+    from . import ops
+    pts, point_offsets, comps, weights, comp_offsets = dedup
+    if comps.shape[0] == 0:
+        return np.zeros((np.asarray(pairs).reshape(-1, 2).shape[0], len(sizes)), dtype=np.float64)
+    samples = ops.joint_bilateral_points_ragged_u8(joint, src, pts, point_offsets, pairs, d=-1,
+                                                   grey_as_bgr=grey_as_bgr, sizes=sizes)
+    return whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta)
+
+
+def _as3(image):
+    return image.unsqueeze(-1) if image.dim() == 2 else image
+
+
+def _pack_list(images, torch):
+    """Images (CUDA tensors or numpy arrays [H,W,C] / [H,W]) packed on the device as
+    [total pixels, C]: host arrays are joined on the host and uploaded with one copy."""
+    if not any(torch.is_tensor(im) for im in images):
+        arrs = [np.asarray(im) for im in images]
+        c = arrs[0].shape[2] if arrs[0].ndim == 3 else 1
+        return torch.from_numpy(np.concatenate([a.reshape(-1, c) for a in arrs])).cuda()
+    parts = [_as3(im if torch.is_tensor(im) else torch.as_tensor(np.asarray(im))).cuda().contiguous()
+             for im in images]
+    return torch.cat([p.view(-1, p.shape[2]) for p in parts])
+
+
+def _stack(images):
+    """Equal-size images (CUDA tensors or numpy arrays) as one device batch [N,H,W,C]."""
+    import torch
+    parts = [_as3(torch.as_tensor(np.asarray(im)) if not torch.is_tensor(im) else im)
+             for im in images]
+    return torch.stack([p.cuda() for p in parts]).contiguous()
+
+
 def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_as_bgr=False):
     """WHDR of filter(joint, src) for every (sigma_color, sigma_space) pair: float64 [P, N] on the
     host, row p = pair p, column i = image i in the caller's order.
 
     src / joint: CUDA uint8 batches [N,H,W,C], or lists of N images (CUDA tensors or numpy
-    arrays [H,W,C]) that may differ in size: equal-size runs are batched (batch.group_by_shape).
-    comparisons_px: N arrays [n_i,6] in pixel coordinates (to_pixels).  grey_as_bgr: the joint
-    has one channel and counts as three equal ones (as in ops.joint_bilateral_u8).
+    arrays [H,W,C]) that may differ in size.  comparisons_px: N arrays [n_i,6] in pixel coordinates
+    (to_pixels).  grey_as_bgr: the joint has one channel and counts as three equal ones (as in
+    ops.joint_bilateral_u8).
       'bilateral'  joint_bilateral_u8(joint, src, -1, sigma_color, sigma_space) evaluated at the
-                   judgement points only (ops.joint_bilateral_points_u8: the same bytes), points
-                   deduplicated per image;
-      'guided'     guided_filter_u8(joint, src, int(sigma_space), sigma_color), full passes.
+                   judgement points only, points deduplicated per image.  A batch goes through
+                   ops.joint_bilateral_points_u8; a list is packed, whatever its sizes and their
+                   order, into ragged calls (ops.joint_bilateral_points_ragged_u8: the same bytes)
+                   of equal channel counts and at most SWEEP_PACK_PIXELS pixels, one filter launch
+                   and one WHDR launch per pack;
+      'guided'     guided_filter_u8(joint, src, int(sigma_space), sigma_color), full passes; the
+                   images of a list that have equal shapes are batched wherever they stand in it.
     Each result equals whdr_batch on the filtered bytes as float32 / 255 (planar), bit for bit."""
     from . import filter_reflectance as fr
     from .batch import group_by_shape
@@ -294,25 +382,41 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
     src, joint = list(src), list(joint)
     if len(src) != len(joint) or len(src) != len(comparisons_px):
         raise ValueError("src, joint and comparisons_px must have one entry per image")
-    for img, comp in zip(src, comparisons_px):   # points are checked before any device work
-        dedup_points([comp], img.shape[0], img.shape[1])
+    # points are deduplicated and checked with each image's own size, before any device work
+    dedup = [dedup_points([comp], img.shape[0], img.shape[1])
+             for img, comp in zip(src, comparisons_px)]
+    for s_img, j_img in zip(src, joint):
+        if tuple(s_img.shape[:2]) != tuple(j_img.shape[:2]):
+            raise ValueError("src and joint images must have the same size")
     _ffi.require_gpu()
 
     out = np.zeros((pairs.shape[0], len(src)), dtype=np.float64)
-    order = list(range(len(src)))
-    # (1 GiB runs: the guided half addresses a run's pixels with int32 offsets)
+
     def key(i):   # (H, W, src channels, joint channels): equal keys batch together
         s_shape, j_shape = tuple(src[i].shape), tuple(joint[i].shape)
         return s_shape[:2] + ((s_shape + (1,))[2], (j_shape + (1,))[2])
 
+    if filter_type == "bilateral":
+        keys = [key(i)[2:] for i in range(len(src))]
+        sizes = [key(i)[:2] for i in range(len(src))]
+        packs = plan_packs(keys, [h * w for h, w in sizes], [int(d[1][-1]) for d in dedup],
+                           pairs.shape[0], lambda k: k[0])
+        for pack in packs:
+            psizes = [sizes[i] for i in pack]
+            pdedup = join_dedup([dedup[i] for i in pack])
+            if pdedup[2].shape[0] == 0:
+                continue
+            s_p = _pack_list([src[i] for i in pack], torch)
+            j_p = s_p if all(joint[i] is src[i] for i in pack) else \
+                _pack_list([joint[i] for i in pack], torch)
+            out[:, pack] = sweep_packed(s_p, j_p, psizes, pdedup, pairs, delta, grey_as_bgr)
+        return out
+    # guided: equal shapes per pass, grouped wherever they stand in the list
+    # (1 GiB runs: the guided half addresses a run's pixels with int32 offsets)
+    order = sorted(range(len(src)), key=key)
     for run in group_by_shape(order, key, max_bytes=1 << 30):
-        def stack(images):
-            parts = [torch.as_tensor(np.asarray(im)) if not torch.is_tensor(im) else im
-                     for im in images]
-            parts = [p.unsqueeze(-1) if p.dim() == 2 else p for p in parts]
-            return torch.stack([p.cuda() for p in parts]).contiguous()
-        s_b = stack([src[i] for i in run])
-        j_b = stack([joint[i] for i in run])
+        s_b = _stack([src[i] for i in run])
+        j_b = _stack([joint[i] for i in run])
         if s_b.shape[:3] != j_b.shape[:3]:
             raise ValueError("src and joint images must have the same size")
         out[:, run] = _sweep_batch(filter_type, s_b, j_b, [comparisons_px[i] for i in run], pairs,

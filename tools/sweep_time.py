@@ -13,7 +13,14 @@ and two ways to get the WHDR of every (image, pair), BF(CNN, CNN):
 The two WHDR matrices are asserted equal.  Wall time per sweep (median of --reps after a warm-up,
 each ending in a device synchronise).  Prints one JSON line.
 
-    python tools/sweep_time.py [--n 8] [--h 384] [--w 512] [--points 300] [--reps 5]
+--mixed times the list path instead: 64 grey maps alternating 341x512 and 512x341 in list order
+with a few 384x512 among them (a sorted IIW listing: no long run of one shape), the same points
+per image and the same two grids, through whdr.sweep on the list.  Beside the time it prints how
+many point-filter calls the sweep made (one per pack with the ragged entry, one per equal-shape
+run without it) and the points per wave of every chunk of every call, from the launch plan.  It
+uses nothing newer than whdr.sweep on lists, so one copy of it times any two commits.
+
+    python tools/sweep_time.py [--n 8] [--h 384] [--w 512] [--points 300] [--reps 5] [--mixed]
 """
 import argparse
 import json
@@ -27,6 +34,80 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 GRIDS = {"s22": ([10, 15, 20, 25], [22]), "s66_88": ([10, 15, 20, 25], [66, 77, 88])}
 
 
+def judgements(rng, h, w, points):
+    """IIW-like comparisons in pixel coordinates: 2 * points comparisons sharing `points` points."""
+    import numpy as np
+    pool = np.stack([rng.integers(0, w, points), rng.integers(0, h, points)], axis=1)
+    m = 2 * points
+    a, b = pool[rng.integers(0, points, m)], pool[rng.integers(0, points, m)]
+    return np.concatenate([a, b, rng.integers(0, 3, (m, 1)), rng.random((m, 1))],
+                          axis=1).astype(np.float64)
+
+
+def mixed_shapes(n=64):
+    """Alternating 341x512 / 512x341, every 16th image 384x512."""
+    return [(384, 512) if i % 16 == 7 else ((341, 512), (512, 341))[i % 2] for i in range(n)]
+
+
+def mixed(args):
+    import numpy as np
+    import torch
+    from reflectance_filtering_amd import _ffi, ops, whdr
+    from tests import synth
+    assert torch.cuda.is_available(), "sweep_time.py needs a HIP device"
+    rng = np.random.default_rng(1)
+    shapes = mixed_shapes()
+    maps = [np.ascontiguousarray(synth.reflectance_like_u8(h, w, 100 + i)[:, :, :1])
+            for i, (h, w) in enumerate(shapes)]
+    comps = [judgements(rng, h, w, args.points) for h, w in shapes]
+    dev = [torch.from_numpy(m).cuda() for m in maps]
+    calls = []                               # points of every point-filter call of a sweep
+
+    def counted(name):
+        real = getattr(ops, name, None)
+        if real is not None:
+            def wrapper(joint, src, points, *a, **kw):
+                calls.append(int(np.asarray(points).reshape(-1, 2).shape[0]))
+                return real(joint, src, points, *a, **kw)
+            setattr(ops, name, wrapper)
+
+    counted("joint_bilateral_points_u8")
+    counted("joint_bilateral_points_ragged_u8")
+
+    def run(pairs):
+        return whdr.sweep("bilateral", dev, dev, comps, pairs, grey_as_bgr=True)
+
+    line = {"tool": "sweep_time", "case": "mixed", "n": len(shapes), "points_per_image": args.points,
+            "shape_runs": 1 + sum(a != b for a, b in zip(shapes, shapes[1:])), "grids": {}}
+    for name, (cs, ss) in GRIDS.items():
+        pairs = [(c, s) for c in cs for s in ss]
+        got = run(pairs)
+        del calls[:]
+        one = np.stack([whdr.sweep("bilateral", d[None], d[None], [c], pairs, grey_as_bgr=True)[:, 0]
+                        for d, c in zip(dev[:6], comps[:6])], axis=1)
+        assert np.array_equal(got[:, :6], one), "list sweep differs from per-image sweeps"
+        del calls[:]
+        run(pairs)
+        per_sweep = list(calls)
+        ppw = sorted({c[2] for total in per_sweep
+                      for c in _ffi.jbf_points_plan([s for _, s in pairs], -1, 1,
+                                                    _ffi.JBF_GREY_AS_BGR, total)})
+        ts = []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(pairs)
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        line["grids"][name] = {"pairs": len(pairs), "list_s": statistics.median(ts),
+                               "min_s": min(ts), "max_s": max(ts), "calls": len(per_sweep),
+                               "points": sum(per_sweep), "ppw": ppw}
+        print("%-7s %2d pairs: list sweep %.4f s in %d call(s), %d points, ppw %s"
+              % (name, len(pairs), statistics.median(ts), len(per_sweep), sum(per_sweep), ppw),
+              file=sys.stderr)
+    print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=8)
@@ -34,7 +115,10 @@ def main():
     ap.add_argument("--w", type=int, default=512)
     ap.add_argument("--points", type=int, default=300, help="distinct judgement points per image")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--mixed", action="store_true", help="the mixed-size list case (64 maps)")
     args = ap.parse_args()
+    if args.mixed:
+        return mixed(args)
     import numpy as np
     import torch
     from reflectance_filtering_amd import ops, whdr
