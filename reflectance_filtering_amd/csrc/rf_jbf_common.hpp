@@ -1,13 +1,51 @@
-// rf_jbf_common.hpp -- what the full-image joint bilateral (rf_jbf.hip) and its point form
-// (rf_jbf_points.hip) share: the host code that builds the parameter tables and the per-pixel
-// texel load and finish of jbf_generic_kernel.  One definition each, so the two entry points
-// cannot drift apart.
+// rf_jbf_common.hpp -- what the full-image joint bilateral (rf_jbf.hip, rf_jbf_f32.hip) and its
+// point form (rf_jbf_points.hip) share: the argument rules of the entry points, the host code that
+// builds the parameter tables (defined in rf_jbf_tables.hip) and the per-pixel texel load and finish
+// of jbf_generic_kernel.  One definition each, so the entry points cannot drift apart.
 #pragma once
+#include <cmath>
 #include <vector>
 
 #include "rf_common.hpp"
 
 namespace rf {
+
+// ---- argument rules (OpenCV's, and the library's limits) ----------------------------------
+// the flag bits a caller may pass
+constexpr int kJbfPublicFlags = RF_JBF_TRUE_DIVISION | RF_JBF_FORCE_GENERIC | RF_JBF_GREY_AS_BGR;
+constexpr int kJbfMaxRadius = 4096;  // a larger radius is refused
+
+// non-positive sigmas become 1
+inline double jbf_sigma(double sigma) { return sigma <= 0 ? 1 : sigma; }
+
+// radius from d, or from sigma_space (after jbf_sigma) when d <= 0; at least 1
+inline int jbf_radius(int d, double sigma_space)
+{
+    const int radius = d <= 0 ? (int)std::lrint(sigma_space * 1.5) : d / 2;
+    return radius < 1 ? 1 : radius;
+}
+
+// RF_JBF_GREY_AS_BGR affects a 1-channel joint only: it counts as 3 equal channels (colour
+// distance 3*|d|, 766-entry LUT), so the tables are those of 3 channels ...
+inline int jbf_table_cn(int joint_cn, int flags)
+{
+    return joint_cn == 1 && (flags & RF_JBF_GREY_AS_BGR) ? 3 : joint_cn;
+}
+// ... and the kernels get joint_cn = -1 and replicate the byte (load_packed)
+inline int jbf_kernel_cn(int joint_cn, int flags)
+{
+    return joint_cn == 1 && (flags & RF_JBF_GREY_AS_BGR) ? -1 : joint_cn;
+}
+
+inline bool stream_is_capturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return cs != hipStreamCaptureStatusNone;
+}
 
 // Colour weights exp(i^2 * -0.5 / sigma_color^2) rounded to float, i = 0 .. 256*joint_cn - 1,
 // computed in double with libm's exp like jointBilateralFilter_8u.  Returns the number of entries

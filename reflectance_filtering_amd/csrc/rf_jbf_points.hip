@@ -16,9 +16,9 @@
 // disk (no reduction across lanes: the summation order is the contract).  Chunks are issued in
 // order of decreasing radius, so the long chains start first.
 //
-// Tables: built on the host by the functions rf_jbf_u8's own cache uses (rf_jbf_common.hpp),
-// staged into the caller's workspace with one copy per call; the library's table cache
-// (g_tables in rf_jbf.hip) is not touched.
+// Tables: built on the host by the functions rf_jbf_u8's own cache uses, under rf_jbf_u8's argument
+// rules (both in rf_jbf_common.hpp), staged into the caller's workspace with one copy per call; the
+// library's table cache (rf_jbf_tables.hip) is not touched.
 //
 // Ragged form (rf_jbf_points_ragged_u8): the images of a call may differ in size and lie packed one
 // after another.  Every lane already finds its image by a binary search over point_offsets and
@@ -59,13 +59,6 @@ struct PtsGroup {
     std::vector<int> params;
 };
 
-// Radius rule and sigma rule of rf_jbf_u8.
-int points_radius(int d, double sigma_space)
-{
-    int radius = d <= 0 ? (int)std::lrint(sigma_space * 1.5) : d / 2;
-    return radius < 1 ? 1 : radius;
-}
-
 // Taps of the radius-r disk: the predicate of jbf_space_taps, without the weights.
 int disk_taps(int radius)
 {
@@ -105,14 +98,14 @@ int plan_points(const char *who, int n_params, const double *sigma_space, int d,
                 int total_points, PtsPlan *plan)
 {
     for (int p = 0; p < n_params; p++) {
-        const double ss = sigma_space[p] <= 0 ? 1 : sigma_space[p];
+        const double ss = jbf_sigma(sigma_space[p]);
         PtsGroup *g = nullptr;
         for (PtsGroup &e : plan->groups)
             if (e.sigma_space == ss)
                 g = &e;
         if (!g) {
-            const int radius = points_radius(d, ss);
-            if (radius > 4096)
+            const int radius = jbf_radius(d, ss);
+            if (radius > kJbfMaxRadius)
                 return fail(RF_E_UNSUPPORTED, "%s: radius %d too large", who, radius);
             plan->groups.push_back(PtsGroup{ss, radius, 0, {}});
             g = &plan->groups.back();
@@ -288,23 +281,13 @@ __global__ __launch_bounds__(64 * kPtsWaves) void jbf_points_ragged_kernel(
                           point_offsets, total, chunks, nchunks, taps, luts, items);
 }
 
-bool stream_capturing(hipStream_t stream)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return cs != hipStreamCaptureStatusNone;
-}
-
-// The colour-table length (entries per set) of a call: 256 per joint channel, 768 for a grey
-// joint read as three equal channels.  0 = bad channel count.
+// The colour-table length (entries per set) of a call: 256 per table channel (jbf_table_cn: 768
+// for a grey joint read as three equal channels).  0 = bad channel count.
 int points_nlut(int joint_cn, int flags)
 {
     if (joint_cn != 1 && joint_cn != 3)
         return 0;
-    return 256 * ((flags & RF_JBF_GREY_AS_BGR) ? 3 : joint_cn);
+    return 256 * jbf_table_cn(joint_cn, flags);
 }
 
 }  // namespace
@@ -337,12 +320,11 @@ extern "C" int rf_debug_jbf_points_plan(int n_params, const double *sigma_space,
     if (joint_cn != 1 && joint_cn != 3)
         return fail(RF_E_UNSUPPORTED, "rf_debug_jbf_points_plan: joint channels must be 1 or 3 (%d)",
                     joint_cn);
-    if (flags & ~(RF_JBF_TRUE_DIVISION | RF_JBF_FORCE_GENERIC | RF_JBF_GREY_AS_BGR))
+    if (flags & ~kJbfPublicFlags)
         return fail(RF_E_BADARG, "rf_debug_jbf_points_plan: unknown flag bits 0x%x", flags);
-    const int flags_eff = joint_cn == 1 ? flags : (flags & ~RF_JBF_GREY_AS_BGR);
     PtsPlan plan;
     const int rc = plan_points("rf_jbf_points_u8", n_params, sigma_space, d,
-                               points_nlut(joint_cn, flags_eff), total_points, &plan);
+                               points_nlut(joint_cn, flags), total_points, &plan);
     if (rc != RF_OK)
         return rc;
     if (!plan_fits_one_launch(plan))
@@ -400,7 +382,7 @@ int points_call(const char *who, const uint8_t *joint, const uint8_t *src, int n
                     joint_cn, src_cn);
     if (border < 0 || border > 4)
         return fail(RF_E_UNSUPPORTED, "%s: border type %d", who, border);
-    if (flags & ~(RF_JBF_TRUE_DIVISION | RF_JBF_FORCE_GENERIC | RF_JBF_GREY_AS_BGR))
+    if (flags & ~kJbfPublicFlags)
         return fail(RF_E_BADARG, "%s: unknown flag bits 0x%x", who, flags);
     {
         const size_t nout = (size_t)n_params * total_points * src_cn;
@@ -408,10 +390,8 @@ int points_call(const char *who, const uint8_t *joint, const uint8_t *src, int n
             ranges_overlap(out, nout, src, px * src_cn))
             return fail(RF_E_BADARG, "%s: out must not overlap an input", who);
     }
-    // RF_JBF_GREY_AS_BGR as in rf_jbf_u8: only a 1-channel joint is affected
-    const int flags_eff = joint_cn == 1 ? flags : (flags & ~RF_JBF_GREY_AS_BGR);
-    const int nlut = points_nlut(joint_cn, flags_eff);
-    const int jcn_kernel = (flags_eff & RF_JBF_GREY_AS_BGR) ? -1 : joint_cn;
+    const int nlut = points_nlut(joint_cn, flags);
+    const int jcn_kernel = jbf_kernel_cn(joint_cn, flags);
     PtsPlan plan;
     int rc = plan_points(who, n_params, sigma_space, d, nlut, total_points, &plan);
     if (rc != RF_OK)
@@ -423,7 +403,7 @@ int points_call(const char *who, const uint8_t *joint, const uint8_t *src, int n
         return fail(RF_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who,
                     workspace ? workspace_bytes : (size_t)0, bytes);
     hipStream_t stream = (hipStream_t)stream_;
-    if (stream_capturing(stream))
+    if (stream_is_capturing(stream))
         return fail(RF_E_UNSUPPORTED, "%s: synchronises its stream and cannot be captured into a "
                                       "graph", who);
     if (total_points == 0)
@@ -463,8 +443,7 @@ int points_call(const char *who, const uint8_t *joint, const uint8_t *src, int n
             for (int s = 0; s < ch.nsets; s++) {
                 const int p = g.params[pc.first + s];
                 ch.param[s] = p;
-                const double sc = sigma_color[p] <= 0 ? 1 : sigma_color[p];
-                jbf_colour_lut(nlut / 256, sc, lut);
+                jbf_colour_lut(nlut / 256, jbf_sigma(sigma_color[p]), lut);
                 for (int a = 0; a < nlut; a++)
                     luts[lut_off + (size_t)a * ch.nsets + s] = lut[a];
             }
@@ -493,11 +472,11 @@ int points_call(const char *who, const uint8_t *joint, const uint8_t *src, int n
     if (ragged)
         hipLaunchKernelGGL(jbf_points_ragged_kernel, dim3(blocks), dim3(64 * kPtsWaves), 0, stream,
                            joint, src, out, n, reinterpret_cast<const PtsImage *>(ws + off_images),
-                           jcn_kernel, src_cn, border, flags_eff, points, point_offsets,
+                           jcn_kernel, src_cn, border, flags, points, point_offsets,
                            total_points, d_chunks, plan.nchunks, d_taps, d_luts, item);
     else
         hipLaunchKernelGGL(jbf_points_kernel, dim3(blocks), dim3(64 * kPtsWaves), 0, stream, joint,
-                           src, out, n, h, w, jcn_kernel, src_cn, border, flags_eff, points,
+                           src, out, n, h, w, jcn_kernel, src_cn, border, flags, points,
                            point_offsets, total_points, d_chunks, plan.nchunks, d_taps, d_luts,
                            item);
     RF_HIP_CHECK(hipGetLastError());

@@ -1,0 +1,989 @@
+// rf_jbf_taploops.hpp -- the tap loops of the tiled joint bilateral kernels (rf_jbf.hip, which
+// describes the pipeline under "Tiled kernels").  Device only: every loop takes LDS byte addresses
+// and accumulates one lane's kPix horizontally adjacent outputs.
+//   jbf_tap_loop            the software-pipelined loop, compiler-scheduled VALU (any texel form)
+//   jbf_tap_loop_grey4      hand-interleaved form for grey tiles, gathers one column step ahead
+//   jbf_tap_loop_grey4_la2  the same two column steps ahead: the default grey loop (SLAB: slab kernel)
+//   jbf_tap_loop_rgb6       hand-interleaved colour loop on 6-byte texels
+// Every macro defined here is #undef-ed again below.
+#pragma once
+#include <type_traits>
+
+#include "rf_common.hpp"
+
+namespace rf {
+namespace {
+
+constexpr int kPix = 4;        // outputs per lane (horizontal)
+
+typedef uint32_t uint2v __attribute__((ext_vector_type(2)));
+typedef float float4v __attribute__((ext_vector_type(4)));
+
+// The LDS reads of the tap loop are issued through asm so that their order and their waits are
+// exactly the pipeline described above (left to itself the compiler sinks each read next to its
+// use and waits for lgkmcnt(0) after every gather).  The wait statement names everything it
+// releases -- and the accumulators -- as in/out operands: that keeps consumers below the wait
+// and the accumulation of the current column above it, i.e. underneath the reads in flight.
+#define RF_LDS_READ_B64(dst, addr, off) \
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
+#define RF_LDS_READ_B128(dst, addr, off) \
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
+#define RF_LDS_READ_B32(dst, addr) asm volatile("ds_read_b32 %0, %1" : "=v"(dst) : "v"(addr))
+#define RF_LDS_READ_B32_OFF(dst, addr, off) \
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
+#define RF_LDS_READ_U16_OFF(dst, addr, off) \
+    asm volatile("ds_read_u16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
+
+// Accumulates all taps of one lane's 4 outputs.  NCH = channels accumulated (3, or 1 when the
+// src is single-channel or every src texel of the tile is grey: identical bits, a third of the
+// multiply-adds).  TB = bytes per LDS texel: 8 = {BGRx joint, BGRx src}; 4 = {B,G,R joint, grey
+// src} (NCH = 1 only).  CLAMP = clamp the LUT index with v_min (otherwise the caller guarantees
+// that every reachable index is either inside the staged table or beyond the end of the
+// workgroup's LDS allocation, where ds_read returns 0).  sum/wsum must be zero on entry.
+template <int NCH, int LUTREP, bool CLAMP, int TLW, int TB>
+__device__ __forceinline__ void jbf_tap_loop(uint32_t lut_lane_addr, uint32_t sw_addr0,
+                                             uint32_t tile_lane_addr, uint32_t plane_b_lane_addr,
+                                             const uint32_t (&jc)[kPix], uint32_t amax, int ty,
+                                             int radius, int r4, int sw_len,
+                                             const int *__restrict__ hwtab, float (&sum)[kPix][NCH],
+                                             float (&wsum)[kPix])
+{
+    static_assert((TB == 8) || (TB == 4 && NCH == 1) || (TB == 6 && NCH == 3),
+                  "4-byte texels carry one src channel, 6-byte ones three");
+    constexpr int TA = TB == 6 ? 4 : TB;  // bytes per texel in the main plane
+    constexpr int Q4 = TLW / 4;
+    using texel_t = typename std::conditional<TB == 8, uint2v, uint32_t>::type;
+    auto joint_of = [](const texel_t &t) -> uint32_t {
+        if constexpr (TB == 8)
+            return t.x;
+        else
+            return t & 0x00ffffffu;
+    };
+    // all four addresses first, then the four reads back to back: LDS instructions issued in
+    // a cluster disturb the VALU stream less than reads interleaved with their address math
+    // (+2.8 % on the hand-scheduled grey loop, in-process A/B)
+    auto issue_gathers = [&](uint32_t jtex, float *g) {
+        uint32_t a[kPix];
+#pragma unroll
+        for (int p = 0; p < kPix; p++) {
+            uint32_t alpha = __builtin_amdgcn_sad_u8(jtex, jc[p], 0u);
+            if (CLAMP)
+                alpha = min(alpha, amax);
+            a[p] = alpha * (LUTREP * 4u) + lut_lane_addr;
+        }
+        asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]));
+#pragma unroll
+        for (int p = 0; p < kPix; p++)
+            RF_LDS_READ_B32(g[p], a[p]);
+    };
+    // TB == 6: second plane of 2-byte texels {G src, R src}; U = ring slot
+#define RF_READ_TEXEL(U, off_texels)                                   \
+    if constexpr (TB == 8) {                                           \
+        RF_LDS_READ_B64(tq[U], ta, (off_texels) * 8);                  \
+    } else {                                                           \
+        RF_LDS_READ_B32_OFF(tq[U], ta, (off_texels) * 4);              \
+        if constexpr (TB == 6)                                         \
+            RF_LDS_READ_U16_OFF(tqb[U], tb, (off_texels) * 2);         \
+    }
+
+    for (int i = -radius; i <= radius; i++) {
+        const int hw = hwtab[i + radius];
+        const int hw4 = (hw + 3) & ~3;
+        const int ai = i < 0 ? -i : i;
+        // column c = 4*gq + u - hw4 (gq = 0 .. hw4/2): tile column X = c + r4 + 4*tx, i.e. texel
+        // address = ta + (u*Q4 + gq)*TB with ta the per-lane address of (row, group 0, u = 0)
+        const uint32_t texel0 = (uint32_t)((ty + i + radius) * TLW + ((r4 - hw4) >> 2));
+        uint32_t ta = tile_lane_addr + texel0 * TA;
+        uint32_t tb = plane_b_lane_addr + texel0 * 2;
+        // weight of tap (i, j) = swc[j] = swc[-j]; group gq needs swc[hw4 - 4*gq - 4 .. +3]
+        uint32_t wa_addr = sw_addr0 + (uint32_t)((ai * sw_len + (r4 + 8) + hw4 - 4) * 4);
+        const int ngroups = (hw4 >> 1) + 1;
+
+        // Register rings with compile-time indices only: column 4*gq+u lives in tq[u], its
+        // gathers in gg[u & 1].  Every read issued in a step is released by the wait at the END
+        // of that step, so nothing is in flight across the loop back-edge (a value in flight
+        // there would be copied by the compiler's phi moves before it has landed).
+        texel_t tq[4];
+        uint32_t tqb[4] = {0u, 0u, 0u, 0u};  // second plane (TB == 6 only)
+        float4v wna, wnb;
+        float gg[2][kPix];
+        RF_READ_TEXEL(0, 0)
+        RF_READ_TEXEL(1, Q4)
+        RF_LDS_READ_B128(wna, wa_addr, 0);
+        RF_LDS_READ_B128(wnb, wa_addr, 16);
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(tq[0]), "+v"(tq[1]), "+v"(tqb[0]), "+v"(tqb[1]), "+v"(wna), "+v"(wnb));
+        issue_gathers(joint_of(tq[0]), gg[0]);
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(gg[0][0]), "+v"(gg[0][1]), "+v"(gg[0][2]), "+v"(gg[0][3]));
+
+#define RF_ACCUM(U)                                                                  \
+    {                                                                                \
+        float s[NCH];                                                                \
+        if constexpr (TB == 8) {                                                     \
+            const uint32_t sv = tq[(U)].y;                                           \
+            s[0] = (float)(sv & 0xff);                                               \
+            if constexpr (NCH == 3) {                                                \
+                s[1] = (float)((sv >> 8) & 0xff);                                    \
+                s[2] = (float)((sv >> 16) & 0xff);                                   \
+            }                                                                        \
+        } else {                                                                     \
+            s[0] = (float)(tq[(U)] >> 24);                                           \
+            if constexpr (TB == 6) {                                                 \
+                s[1] = (float)(tqb[(U)] & 0xff);                                     \
+                s[2] = (float)((tqb[(U)] >> 8) & 0xff);                              \
+            }                                                                        \
+        }                                                                            \
+        _Pragma("unroll") for (int p = 0; p < kPix; p++)                             \
+        {                                                                            \
+            const float wgt = __fmul_rn(wv[4 + p - (U)], gg[(U) & 1][p]);            \
+            _Pragma("unroll") for (int ch = 0; ch < NCH; ch++) sum[p][ch] =          \
+                __fadd_rn(sum[p][ch], __fmul_rn(wgt, s[ch]));                        \
+            wsum[p] = __fadd_rn(wsum[p], wgt);                                       \
+        }                                                                            \
+    }
+#define RF_TEXEL_OFF(U) ((((U) + 2) & 3) * Q4 + (((U) + 2) >> 2))
+        // Pins the accumulators at this point of the instruction stream (no instruction).
+#define RF_PIN_ACC()                                                                            \
+    if constexpr (NCH == 3) {                                                                   \
+        asm volatile(""                                                                         \
+                     : "+v"(sum[0][0]), "+v"(sum[1][0]), "+v"(sum[2][0]), "+v"(sum[3][0]),      \
+                       "+v"(sum[0][1]), "+v"(sum[1][1]), "+v"(sum[2][1]), "+v"(sum[3][1]),      \
+                       "+v"(sum[0][NCH - 1]), "+v"(sum[1][NCH - 1]), "+v"(sum[2][NCH - 1]),     \
+                       "+v"(sum[3][NCH - 1]), "+v"(wsum[0]), "+v"(wsum[1]), "+v"(wsum[2]),      \
+                       "+v"(wsum[3]));                                                          \
+    } else {                                                                                    \
+        asm volatile(""                                                                         \
+                     : "+v"(sum[0][0]), "+v"(sum[1][0]), "+v"(sum[2][0]), "+v"(sum[3][0]),      \
+                       "+v"(wsum[0]), "+v"(wsum[1]), "+v"(wsum[2]), "+v"(wsum[3]));             \
+    }
+        // one column: issue texel(+2) and gathers(+1), accumulate column +0 underneath them,
+        // then release what was issued
+#define RF_STEP(U)                                                                            \
+    RF_READ_TEXEL(((U) + 2) & 3, RF_TEXEL_OFF(U))                                             \
+    issue_gathers(joint_of(tq[((U) + 1) & 3]), gg[((U) + 1) & 1]);                            \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    RF_ACCUM(U)                                                                               \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    RF_PIN_ACC()                                                                              \
+    __builtin_amdgcn_sched_barrier(0);                                                        \
+    asm volatile("s_waitcnt lgkmcnt(0)"                                                       \
+                 : "+v"(tq[((U) + 2) & 3]), "+v"(tqb[((U) + 2) & 3]),                         \
+                   "+v"(gg[((U) + 1) & 1][0]), "+v"(gg[((U) + 1) & 1][1]),                    \
+                   "+v"(gg[((U) + 1) & 1][2]), "+v"(gg[((U) + 1) & 1][3]));                   \
+    __builtin_amdgcn_sched_barrier(0);
+
+        for (int gq = 0; gq < ngroups; gq++) {
+            float wv[8];
+            wv[0] = wna.x; wv[1] = wna.y; wv[2] = wna.z; wv[3] = wna.w;
+            wv[4] = wnb.x; wv[5] = wnb.y; wv[6] = wnb.z; wv[7] = wnb.w;
+            RF_STEP(0)
+            RF_STEP(1)
+            RF_STEP(2)
+            // u = 3 also fetches the next group's weight window
+            RF_READ_TEXEL(1, RF_TEXEL_OFF(3))
+            issue_gathers(joint_of(tq[0]), gg[0]);
+            wa_addr -= 16;
+            RF_LDS_READ_B128(wna, wa_addr, 0);
+            RF_LDS_READ_B128(wnb, wa_addr, 16);
+            __builtin_amdgcn_sched_barrier(0);
+            RF_ACCUM(3)
+            __builtin_amdgcn_sched_barrier(0);
+            RF_PIN_ACC()
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(tq[1]), "+v"(tqb[1]), "+v"(wna), "+v"(wnb), "+v"(gg[0][0]),
+                           "+v"(gg[0][1]), "+v"(gg[0][2]), "+v"(gg[0][3]));
+            __builtin_amdgcn_sched_barrier(0);
+            ta += TA;
+            tb += 2;
+        }
+#undef RF_STEP
+#undef RF_PIN_ACC
+#undef RF_ACCUM
+#undef RF_TEXEL_OFF
+    }
+#undef RF_READ_TEXEL
+}
+
+// Hand-scheduled tap loop for grey tiles (4-byte texels, one accumulated channel), same
+// arithmetic and the same pipeline as jbf_tap_loop<1, LUTREP, false, TLW, 4>.
+//
+// Why asm: a gfx950 SIMD retires two wave-instructions per 4 cycles only if at most one of them
+// is a "full-pipe" opcode (v_sad_u8, v_lshl_add_u32, v_cvt_*, anything with an SGPR/constant
+// operand ...; 4 cycles each back to back) and the other a "simple" one (v_mul_f32 / v_add_f32 /
+// v_and_b32 on VGPRs; 2 cycles each) -- tools/microbench/valu_rates2.hip.  Per column this loop
+// needs 9 full-pipe and 17 simple instructions; hipcc emits them as an 8-instruction full-pipe
+// burst followed by the simple ones, the blocks below interleave them one for one.
+// J1: the joint has one channel and its texel field holds the value pre-multiplied by the LUT's
+// byte stride (3x that for RF_JBF_GREY_AS_BGR), so v_sad_u32(texel, centre, lane address) IS the
+// gather address: no v_lshl_add_u32, 22 instead of 26 VALU instructions per column step.
+template <int LUTREP, int TLW, bool J1 = false>
+__device__ __forceinline__ void jbf_tap_loop_grey4(uint32_t lut_lane_addr, uint32_t sw_addr0,
+                                                   uint32_t tile_lane_addr,
+                                                   const uint32_t (&jc)[kPix], int ty, int radius,
+                                                   int r4, int sw_len,
+                                                   const int *__restrict__ hwtab,
+                                                   float (&sum)[kPix][1], float (&wsum)[kPix])
+{
+    constexpr int Q4 = TLW / 4;
+    constexpr int SHIFT = LUTREP == 32 ? 7 : LUTREP == 16 ? 6 : LUTREP == 8 ? 5 : 4;
+    static_assert(LUTREP == 32 || LUTREP == 16 || LUTREP == 8 || LUTREP == 4, "LUT replicas");
+    uint32_t mask = 0x00ffffffu;
+    asm volatile("" : "+v"(mask));  // keep the mask in a VGPR (a literal operand is full-pipe)
+
+    // Row geometry: the lane's first texel address and the address of the first weight window.
+    auto row_addr = [&](int i, uint32_t &ta_out, uint32_t &wa_out, int &ngroups_out) {
+        const int hw = hwtab[i + radius];
+        const int hw4 = (hw + 3) & ~3;
+        const int ai = i < 0 ? -i : i;
+        ta_out = tile_lane_addr + (uint32_t)(((ty + i + radius) * TLW + ((r4 - hw4) >> 2)) * 4);
+        wa_out = sw_addr0 + (uint32_t)((ai * sw_len + (r4 + 8) + hw4 - 4) * 4);
+        ngroups_out = (hw4 >> 1) + 1;
+    };
+
+    // look-ahead texels of columns 0..3 of a group as two register pairs: columns (0, 1) and
+    // (2, 3) are each fetched by one ds_read2_b32 (their tile addresses differ by Q4 texels)
+    uint2v tp[2];
+    float4v wna, wnb;
+    float gg[2][kPix];
+    uint32_t ta, wa_addr;
+    int ngroups;
+    row_addr(-radius, ta, wa_addr, ngroups);
+    // prologue of the first tap row: texels of columns 0 and 1, weight window of group 0,
+    // gathers of column 0.  Every later row gets these from the last group of the row before.
+    asm volatile("ds_read2_b32 %0, %1 offset1:%2" : "=&v"(tp[0]) : "v"(ta), "n"(Q4));
+    asm volatile("ds_read_b128 %0, %2\n\t"
+                 "ds_read_b128 %1, %2 offset:16"
+                 : "=&v"(wna), "=&v"(wnb)
+                 : "v"(wa_addr));
+    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(tp[0]));
+    {
+        const uint32_t tj = tp[0].x & mask;
+#pragma unroll
+        for (int p = 0; p < kPix; p++) {
+            const uint32_t a =
+                J1 ? (tj > jc[p] ? tj - jc[p] : jc[p] - tj) + lut_lane_addr
+                   : __builtin_amdgcn_sad_u8(tj, jc[p], 0u) * (LUTREP * 4u) + lut_lane_addr;
+            asm volatile("ds_read_b32 %0, %1" : "=v"(gg[0][p]) : "v"(a));
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(tp[0]), "+v"(wna), "+v"(wnb), "+v"(gg[0][0]), "+v"(gg[0][1]),
+                   "+v"(gg[0][2]), "+v"(gg[0][3]));
+
+    // even steps fetch the texels of two columns (this step's look-ahead and the next step's);
+    // the pair is an output of the even steps only
+#define RF_TQ(U) tp[((U) & 3) >> 1][(U) & 1]
+#define RF_G4_TNOUT(U) RF_G4_TNOUT_##U
+#define RF_G4_TNOUT_0 [tn] "=&v"(tp[1]),
+#define RF_G4_TNOUT_2 [tn] "=&v"(tp[0]),
+#define RF_G4_TNOUT_1
+#define RF_G4_TNOUT_3
+#define RF_G4_READ(U) RF_G4_READ_##U
+#define RF_G4_READ_0 "ds_read2_b32 %[tn], %[ta] offset0:%[o0] offset1:%[o1]\n\t"
+#define RF_G4_READ_2 "ds_read2_b32 %[tn], %[ta] offset0:%[o0] offset1:%[o1]\n\t"
+#define RF_G4_READ_1 ""
+#define RF_G4_READ_3 ""
+#define RF_TEXEL_OFF4(U) (((((U) + 2) & 3) * Q4 + (((U) + 2) >> 2)) * 4)
+    // Column step U of a group: texel of column +2 (from address TA + OFF), SAD + gathers of
+    // column +1, accumulation of column +0.  GA = gathers being consumed, GB = gathers being
+    // issued (their registers first hold alpha, then the LDS address, then the LUT value).
+#define RF_G4_PART1(U, GA, GB, TA, OFF, OFF1)                                                          \
+    float w0_, w1_, w2_, w3_, s_;                                                                \
+    uint32_t tj_;                                                                                \
+    asm volatile(RF_G4_READ(U)                                                                   \
+                 "v_and_b32 %[tj], %[mask], %[t1]\n\t"                                           \
+                 "v_sad_u8 %[a0], %[tj], %[jc0], 0\n\t"                                          \
+                 "v_mul_f32 %[w0], %[wv0], %[g0]\n\t"                                            \
+                 "v_sad_u8 %[a1], %[tj], %[jc1], 0\n\t"                                          \
+                 "v_mul_f32 %[w1], %[wv1], %[g1]\n\t"                                            \
+                 "v_sad_u8 %[a2], %[tj], %[jc2], 0\n\t"                                          \
+                 "v_mul_f32 %[w2], %[wv2], %[g2]\n\t"                                            \
+                 "v_sad_u8 %[a3], %[tj], %[jc3], 0\n\t"                                          \
+                 "v_mul_f32 %[w3], %[wv3], %[g3]\n\t"                                            \
+                 "v_cvt_f32_ubyte3 %[s], %[t0]"                                                  \
+                 : RF_G4_TNOUT(U)[tj] "=&v"(tj_), [a0] "=&v"(GB[0]),                             \
+                   [a1] "=&v"(GB[1]), [a2] "=&v"(GB[2]), [a3] "=&v"(GB[3]), [w0] "=&v"(w0_),     \
+                   [w1] "=&v"(w1_), [w2] "=&v"(w2_), [w3] "=&v"(w3_), [s] "=&v"(s_)              \
+                 : [ta] "v"(TA), [o0] "n"((OFF) / 4), [o1] "n"((OFF1) / 4), [mask] "v"(mask),    \
+                   [t1] "v"(RF_TQ((U) + 1)), [t0] "v"(RF_TQ(U)), [jc0] "v"(jc[0]),               \
+                   [jc1] "v"(jc[1]), [jc2] "v"(jc[2]), [jc3] "v"(jc[3]), [wv0] "v"(wv[4 - (U)]), \
+                   [wv1] "v"(wv[5 - (U)]), [wv2] "v"(wv[6 - (U)]), [wv3] "v"(wv[7 - (U)]),       \
+                   [g0] "v"(GA[0]), [g1] "v"(GA[1]), [g2] "v"(GA[2]), [g3] "v"(GA[3]));          \
+    asm volatile("v_lshl_add_u32 %[a0], %[a0], %[sh], %[la]\n\t"                                 \
+                 "v_add_f32 %[ws0], %[ws0], %[w0]\n\t"                                           \
+                 "v_lshl_add_u32 %[a1], %[a1], %[sh], %[la]\n\t"                                 \
+                 "v_add_f32 %[ws1], %[ws1], %[w1]\n\t"                                           \
+                 "v_lshl_add_u32 %[a2], %[a2], %[sh], %[la]\n\t"                                 \
+                 "v_add_f32 %[ws2], %[ws2], %[w2]\n\t"                                           \
+                 "v_lshl_add_u32 %[a3], %[a3], %[sh], %[la]\n\t"                                 \
+                 "v_add_f32 %[ws3], %[ws3], %[w3]\n\t"                                           \
+                 "ds_read_b32 %[a0], %[a0]\n\t"                                                  \
+                 "ds_read_b32 %[a1], %[a1]\n\t"                                                  \
+                 "ds_read_b32 %[a2], %[a2]\n\t"                                                  \
+                 "ds_read_b32 %[a3], %[a3]"                                                      \
+                 : [a0] "+v"(GB[0]), [a1] "+v"(GB[1]), [a2] "+v"(GB[2]), [a3] "+v"(GB[3]),       \
+                   [ws0] "+v"(wsum[0]), [ws1] "+v"(wsum[1]), [ws2] "+v"(wsum[2]),                \
+                   [ws3] "+v"(wsum[3])                                                           \
+                 : [sh] "n"(SHIFT), [la] "v"(lut_lane_addr), [w0] "v"(w0_), [w1] "v"(w1_),       \
+                   [w2] "v"(w2_), [w3] "v"(w3_));
+    // the same step for a single-channel joint (J1): the SAD of the pre-scaled values plus the
+    // lane's LUT address is the gather address
+#define RF_G4_PART1_J1(U, GA, GB, TA, OFF, OFF1)                                                       \
+    float w0_, w1_, w2_, w3_, s_;                                                                \
+    uint32_t tj_;                                                                                \
+    asm volatile(RF_G4_READ(U)                                                                   \
+                 "v_and_b32 %[tj], %[mask], %[t1]\n\t"                                           \
+                 "v_sad_u32 %[a0], %[tj], %[jc0], %[la]\n\t"                                     \
+                 "v_mul_f32 %[w0], %[wv0], %[g0]\n\t"                                            \
+                 "v_sad_u32 %[a1], %[tj], %[jc1], %[la]\n\t"                                     \
+                 "v_mul_f32 %[w1], %[wv1], %[g1]\n\t"                                            \
+                 "v_sad_u32 %[a2], %[tj], %[jc2], %[la]\n\t"                                     \
+                 "v_mul_f32 %[w2], %[wv2], %[g2]\n\t"                                            \
+                 "v_sad_u32 %[a3], %[tj], %[jc3], %[la]\n\t"                                     \
+                 "v_mul_f32 %[w3], %[wv3], %[g3]\n\t"                                            \
+                 "v_cvt_f32_ubyte3 %[s], %[t0]"                                                  \
+                 : RF_G4_TNOUT(U)[tj] "=&v"(tj_), [a0] "=&v"(GB[0]),                             \
+                   [a1] "=&v"(GB[1]), [a2] "=&v"(GB[2]), [a3] "=&v"(GB[3]), [w0] "=&v"(w0_),     \
+                   [w1] "=&v"(w1_), [w2] "=&v"(w2_), [w3] "=&v"(w3_), [s] "=&v"(s_)              \
+                 : [ta] "v"(TA), [o0] "n"((OFF) / 4), [o1] "n"((OFF1) / 4), [mask] "v"(mask),    \
+                   [la] "v"(lut_lane_addr),                                                      \
+                   [t1] "v"(RF_TQ((U) + 1)), [t0] "v"(RF_TQ(U)), [jc0] "v"(jc[0]),               \
+                   [jc1] "v"(jc[1]), [jc2] "v"(jc[2]), [jc3] "v"(jc[3]), [wv0] "v"(wv[4 - (U)]), \
+                   [wv1] "v"(wv[5 - (U)]), [wv2] "v"(wv[6 - (U)]), [wv3] "v"(wv[7 - (U)]),       \
+                   [g0] "v"(GA[0]), [g1] "v"(GA[1]), [g2] "v"(GA[2]), [g3] "v"(GA[3]));          \
+    asm volatile("v_add_f32 %[ws0], %[ws0], %[w0]\n\t"                                           \
+                 "v_add_f32 %[ws1], %[ws1], %[w1]\n\t"                                           \
+                 "v_add_f32 %[ws2], %[ws2], %[w2]\n\t"                                           \
+                 "v_add_f32 %[ws3], %[ws3], %[w3]\n\t"                                           \
+                 "ds_read_b32 %[a0], %[a0]\n\t"                                                  \
+                 "ds_read_b32 %[a1], %[a1]\n\t"                                                  \
+                 "ds_read_b32 %[a2], %[a2]\n\t"                                                  \
+                 "ds_read_b32 %[a3], %[a3]"                                                      \
+                 : [a0] "+v"(GB[0]), [a1] "+v"(GB[1]), [a2] "+v"(GB[2]), [a3] "+v"(GB[3]),       \
+                   [ws0] "+v"(wsum[0]), [ws1] "+v"(wsum[1]), [ws2] "+v"(wsum[2]),                \
+                   [ws3] "+v"(wsum[3])                                                           \
+                 : [w0] "v"(w0_), [w1] "v"(w1_), [w2] "v"(w2_), [w3] "v"(w3_));
+#define RF_G4_PART2(TN, GB, EXTRA_OPERANDS)                                                      \
+    asm volatile("v_mul_f32 %[w0], %[w0], %[s]\n\t"                                              \
+                 "v_mul_f32 %[w1], %[w1], %[s]\n\t"                                              \
+                 "v_mul_f32 %[w2], %[w2], %[s]\n\t"                                              \
+                 "v_mul_f32 %[w3], %[w3], %[s]\n\t"                                              \
+                 "v_add_f32 %[s0], %[s0], %[w0]\n\t"                                             \
+                 "v_add_f32 %[s1], %[s1], %[w1]\n\t"                                             \
+                 "v_add_f32 %[s2], %[s2], %[w2]\n\t"                                             \
+                 "v_add_f32 %[s3], %[s3], %[w3]\n\t"                                             \
+                 "s_waitcnt lgkmcnt(0)"                                                          \
+                 : [w0] "+v"(w0_), [w1] "+v"(w1_), [w2] "+v"(w2_), [w3] "+v"(w3_),               \
+                   [s0] "+v"(sum[0][0]), [s1] "+v"(sum[1][0]), [s2] "+v"(sum[2][0]),             \
+                   [s3] "+v"(sum[3][0]), "+v"(TN), "+v"(GB[0]), "+v"(GB[1]), "+v"(GB[2]),        \
+                   "+v"(GB[3]) EXTRA_OPERANDS                                                    \
+                 : [s] "v"(s_));
+#define RF_COMMA_W , "+v"(wna), "+v"(wnb)
+#define RF_LOAD_WINDOW(ADDR)                                                                     \
+    asm volatile("ds_read_b128 %0, %2\n\t"                                                       \
+                 "ds_read_b128 %1, %2 offset:16"                                                 \
+                 : "=&v"(wna), "=&v"(wnb)                                                        \
+                 : "v"(ADDR));
+
+#define RF_ROW_LOOP(P1)                                                            \
+    for (int i = -radius; i <= radius; i++) {                                                       \
+        uint32_t ta_next, wa_next;                                                                  \
+        int ngroups_next;                                                                           \
+        row_addr(i < radius ? i + 1 : i, ta_next, wa_next, ngroups_next);                           \
+        for (int gq = 0; gq < ngroups - 1; gq++) {                                                  \
+            float wv[8];                                                                            \
+            wv[0] = wna.x; wv[1] = wna.y; wv[2] = wna.z; wv[3] = wna.w;                             \
+            wv[4] = wnb.x; wv[5] = wnb.y; wv[6] = wnb.z; wv[7] = wnb.w;                             \
+            {                                                                                       \
+                P1(0, gg[0], gg[1], ta, RF_TEXEL_OFF4(0), RF_TEXEL_OFF4(1))                         \
+                RF_G4_PART2(tp[1], gg[1], )                                                         \
+            }                                                                                       \
+            {                                                                                       \
+                P1(1, gg[1], gg[0], ta, 0, 0)                                                       \
+                RF_G4_PART2(tp[1], gg[0], )                                                         \
+            }                                                                                       \
+            {                                                                                       \
+                P1(2, gg[0], gg[1], ta, RF_TEXEL_OFF4(2), RF_TEXEL_OFF4(3))                         \
+                RF_G4_PART2(tp[0], gg[1], )                                                         \
+            }                                                                                       \
+            {                                                                                       \
+                P1(3, gg[1], gg[0], ta, 0, 0)                                                       \
+                wa_addr -= 16;                                                                      \
+                RF_LOAD_WINDOW(wa_addr)                                                             \
+                RF_G4_PART2(tp[0], gg[0], RF_COMMA_W)                                               \
+            }                                                                                       \
+            ta += 4;                                                                                \
+        }                                                                                           \
+        {                                                                                           \
+            float wv[8];                                                                            \
+            wv[0] = wna.x; wv[1] = wna.y; wv[2] = wna.z; wv[3] = wna.w;                             \
+            wv[4] = wnb.x; wv[5] = wnb.y; wv[6] = wnb.z; wv[7] = wnb.w;                             \
+            {                                                                                       \
+                P1(0, gg[0], gg[1], ta, RF_TEXEL_OFF4(0), RF_TEXEL_OFF4(1))                         \
+                RF_G4_PART2(tp[1], gg[1], )                                                         \
+            }                                                                                       \
+            {                                                                                       \
+                P1(1, gg[1], gg[0], ta, 0, 0)                                                       \
+                RF_G4_PART2(tp[1], gg[0], )                                                         \
+            }                                                                                       \
+            {                                                                                       \
+                P1(2, gg[0], gg[1], ta_next, 0, Q4 * 4)                                             \
+                RF_G4_PART2(tp[0], gg[1], )                                                         \
+            }                                                                                       \
+            {                                                                                       \
+                P1(3, gg[1], gg[0], ta_next, 0, 0)                                                  \
+                RF_LOAD_WINDOW(wa_next)                                                             \
+                RF_G4_PART2(tp[0], gg[0], RF_COMMA_W)                                               \
+            }                                                                                       \
+        }                                                                                           \
+        ta = ta_next;                                                                               \
+        wa_addr = wa_next;                                                                          \
+        ngroups = ngroups_next;                                                                     \
+    }
+    // (per tap row: all groups but the last run the plain steps; in the last group the two
+    //  look-ahead reads fetch columns 0 and 1 of the NEXT row - the columns past the end of this
+    //  one carry no weight - step 3 issues that row's first gathers and loads its first weight
+    //  window, so the next row starts with a full pipe.  The last row prefetches itself again.)
+    if constexpr (J1) {
+        RF_ROW_LOOP(RF_G4_PART1_J1)
+    } else {
+        RF_ROW_LOOP(RF_G4_PART1)
+    }
+#undef RF_ROW_LOOP
+#undef RF_G4_PART1_J1
+#undef RF_LOAD_WINDOW
+#undef RF_COMMA_W
+#undef RF_G4_PART1
+#undef RF_G4_PART2
+#undef RF_TEXEL_OFF4
+#undef RF_TQ
+#undef RF_G4_READ
+#undef RF_G4_READ_0
+#undef RF_G4_READ_1
+#undef RF_G4_READ_2
+#undef RF_G4_READ_3
+#undef RF_G4_TNOUT
+#undef RF_G4_TNOUT_0
+#undef RF_G4_TNOUT_1
+#undef RF_G4_TNOUT_2
+#undef RF_G4_TNOUT_3
+}
+
+// jbf_tap_loop_grey4 with the gathers TWO column steps ahead of their use (round 5).  In the form above
+// a column's four LUT gathers are issued in the step before the one that multiplies by them, and the
+// step ends in s_waitcnt lgkmcnt(0): a wave has 8 instructions of its own between issue and wait, the
+// rest of the LDS latency has to come from the SIMD's other three waves - with the CU's one LDS pipeline
+// 62 % busy that is not enough, and VALU and LDS each sit at 0.68 of their floors.  Here step c issues
+// the gathers of column c + 2 and waits with lgkmcnt(4): everything but those four gathers - i.e. the
+// gathers of column c + 1, the texel pair and the weight window - has landed (LDS operations of a wave
+// return in order, so the window is issued BEFORE the step's gathers).  Four gather buffers (indexed by
+// the step within the group), the src byte converted when its texel is at hand for the SAD (two steps
+// before use) so that a texel pair is free for re-use after its second SAD: two pairs still suffice.
+// Same instructions per step, same arithmetic and order: identical bytes.
+// SLAB (round 6, jbf_slab_kernel): the loop runs the tap rows i_first .. i_last only - a slab of the disk's
+// rows whose texels are what the LDS tile holds at the moment, tile row of tap row i for the lane's output
+// row = ty + i + row_bias - and ADDS to sum / wsum: slabs taken in increasing i keep every pixel's taps in
+// row-major order, so any radius runs through this loop with the bytes of one pass over the whole disk.
+template <int LUTREP, int TLW, bool J1 = false, bool SLAB = false>
+__device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
+                                                       const float *__restrict__ swsym,
+                                                       uint32_t tile_lane_addr,
+                                                       const uint32_t (&jc)[kPix], int ty, int radius,
+                                                       int r4, int sw_len,
+                                                       const int *__restrict__ hwtab,
+                                                       float (&sum)[kPix][1], float (&wsum)[kPix],
+                                                       int i_first = 0, int i_last = 0, int row_bias = 0)
+{
+    const int i_lo = SLAB ? i_first : -radius, i_hi = SLAB ? i_last : radius;
+    const int bias = SLAB ? row_bias : radius;
+    constexpr int Q4 = TLW / 4;
+    constexpr int SHIFT = LUTREP == 32 ? 7 : LUTREP == 16 ? 6 : LUTREP == 8 ? 5 : 4;
+    static_assert(LUTREP == 32 || LUTREP == 16 || LUTREP == 8 || LUTREP == 4, "LUT replicas");
+    static_assert(Q4 + 1 <= 255, "ds_read2_b32 offsets are 8 bits (the largest one here: Q4 + 1)");
+    static_assert(TLW % 4 == 0, "column-interleaved planes");
+    uint32_t mask = 0x00ffffffu;
+    asm volatile("" : "+v"(mask));  // keep the mask in a VGPR (a literal operand is full-pipe)
+
+    // A tap row of half-width hw serves the lane's four outputs from the 2 hw + 4 columns -hw .. hw + 3.
+    // The row starts at the EVEN column -hws (hws = hw rounded up to even) and runs whole groups of four
+    // from there: at most two columns of zero weight per row (round 4 started at a multiple of four, the
+    // alignment its ds_read_b128 weight windows needed: up to six; 3,664 column steps instead of 3,764
+    // per output quad at radius 33).  A row that starts in the middle of a quad of the column-
+    // interleaved tile (phase 1) finds columns (0, 1) of a group in planes 2, 3 and columns (2, 3) in
+    // planes 0, 1 of the next quad: each of the two pair reads has its own address register.
+    const uint32_t lane_row0 = tile_lane_addr + (uint32_t)(ty * TLW * 4);  // the lane's part of an address
+    auto row_addr = [&](int i, int hw, uint32_t &ta_out, uint32_t &tb_out, uint32_t &wa_out,
+                        int &ngroups_out) {
+        const int hws = (hw + 1) & ~1;
+        const int ai = i < 0 ? -i : i;
+        const int c0 = r4 - hws;  // first column, relative to the lane's quad origin
+        const int quad = (i + bias) * TLW + (c0 >> 2);
+        const int phase = (c0 >> 1) & 1;
+        ta_out = lane_row0 + (uint32_t)((quad + (phase ? 2 * Q4 : 0)) * 4);
+        tb_out = lane_row0 + (uint32_t)((quad + (phase ? 1 : 2 * Q4)) * 4);
+        wa_out = (uint32_t)(ai * sw_len + (r4 + 8) + hws - 4);  // index of the first window's first weight
+        ngroups_out = (hws + hw + 4 + 3) >> 2;
+    };
+
+    uint2v tp[2];        // texel pairs: tp[0] = columns (0, 1), tp[1] = columns (2, 3) of a group
+    // The weight window of a group (8 wave-uniform floats) lives in SGPRs: a v_mul_f32 with an SGPR
+    // operand hides behind its neighbours like the SADs do (a pair with a v_sad_u8 or a v_add_f32 issues
+    // in 4.2 cycles, tools/microbench/pipe_overlap.hip), and two broadcast ds_read_b128 per group - 2 of
+    // the 7 dwords an LDS return carried per step, 5 % of the launch - are gone.  Scalar loads share
+    // lgkmcnt with the LDS and return out of order, so the window of the NEXT group, requested in step 0,
+    // needs a full wait: RF_L2_WAIT_WINDOW, placed where it is free.
+    typedef float float8v __attribute__((ext_vector_type(8)));
+    float8v ws8, wn8;    // this group's window, the next group's
+    float gg[4][kPix];   // gg[u]: LUT values of the group's column u (in flight, then consumed at step u)
+    float sv[4];         // sv[u]: src value of column u as float
+    uint32_t ta, tb, wa_addr;
+    int ngroups;
+    if constexpr (SLAB) {
+        int hw0;
+        const int *hp0 = hwtab + (i_lo + radius);
+        asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(hw0) : "s"(hp0));
+        row_addr(i_lo, __builtin_amdgcn_readfirstlane(hw0), ta, tb, wa_addr, ngroups);
+    } else {
+        row_addr(-radius, 0, ta, tb, wa_addr, ngroups);  // (the top row of the disk: half-width 0)
+    }
+    // The half-width of row i + 1 is needed during row i (its last group reads ahead into row i + 1).
+    // A load the compiler issues gets its wait - a full one - at the first use, in the middle of a row
+    // with four gathers in flight: one pipeline drain per row.  So the value is requested a row early
+    // by hand (hw_ahead, at the top of row i - 1) and taken over at the top of row i: every group has a
+    // full wait in the middle of its step 3 (RF_L2_WAIT_WINDOW), a row at least one group.
+    int hw_ahead;
+    {
+        const int *hp = SLAB ? hwtab + ((i_lo + 1 < i_hi ? i_lo + 1 : i_hi) + radius) : hwtab + 1;
+        asm volatile("s_load_dword %0, %1, 0x0" : "=s"(hw_ahead) : "s"(hp));  // (waited for below)
+    }
+    // prologue: both texel pairs and the weight window of the first group, gathers and src values of
+    // its columns 0 and 1
+    asm volatile("ds_read2_b32 %0, %2 offset1:%4\n\t"
+                 "ds_read2_b32 %1, %3 offset1:%4"
+                 : "=&v"(tp[0]), "=&v"(tp[1])
+                 : "v"(ta), "v"(tb), "n"(Q4));
+    {
+        const float *wp = swsym + wa_addr;
+        asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(ws8) : "s"(wp));
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tp[0]), "+v"(tp[1]), "+s"(ws8));
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+        const uint32_t tx = c == 0 ? tp[0].x : tp[0].y;
+        const uint32_t tj = tx & mask;
+#pragma unroll
+        for (int p = 0; p < kPix; p++) {
+            const uint32_t a =
+                J1 ? (tj > jc[p] ? tj - jc[p] : jc[p] - tj) + lut_lane_addr
+                   : __builtin_amdgcn_sad_u8(tj, jc[p], 0u) * (LUTREP * 4u) + lut_lane_addr;
+            asm volatile("ds_read_b32 %0, %1" : "=v"(gg[c][p]) : "v"(a));
+        }
+        sv[c] = (float)(tx >> 24);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(gg[0][0]), "+v"(gg[0][1]), "+v"(gg[0][2]),
+                   "+v"(gg[0][3]), "+v"(gg[1][0]), "+v"(gg[1][1]), "+v"(gg[1][2]), "+v"(gg[1][3]));
+
+#define RF_L2_TQ(U) tp[((U) & 3) >> 1][(U) & 1]
+    // even steps read a texel pair of the NEXT group (or of the next row's first group): step 0 its
+    // columns (0, 1) into tp[0], step 2 its columns (2, 3) into tp[1].  Where a pair sits depends on the
+    // phase of its row: each of the two reads has its own address register (ta: columns (0, 1), tb:
+    // columns (2, 3)), set per row, and the ds_read2 offsets are the same for both phases - one v_add
+    // per group more, and no branch in the loop (at a join the compiler may move registers, and
+    // gathers are in flight at every group end; issuing the read twice under complementary EXEC masks
+    // was measured too: the three EXEC writes per read cost more than the shorter rows return)
+#define RF_L2_TNOUT(U) RF_L2_TNOUT_##U
+#define RF_L2_TNOUT_0 [tn] "=&v"(tp[0]),
+#define RF_L2_TNOUT_2 [tn] "=&v"(tp[1]),
+#define RF_L2_TNOUT_1
+#define RF_L2_TNOUT_3
+#define RF_L2_READ(U) RF_L2_READ_##U
+#define RF_L2_READ_0 "ds_read2_b32 %[tn], %[ta] offset0:%[o0] offset1:%[o1]\n\t"
+#define RF_L2_READ_2 RF_L2_READ_0
+#define RF_L2_READ_1 ""
+#define RF_L2_READ_3 ""
+    // Step U of a group, ONE statement (hipcc puts an s_nop at every boundary between asm statements:
+    // three per step cost 0.5 %): [texel pair]; SADs of column U + 2 interleaved with the weights of column
+    // U (GA = its gathered LUT values); src value of column U + 2; [MID: the group's full wait, step 3];
+    // gather addresses of column U + 2 interleaved with the weight sums of column U; the four gathers
+    // (clustered: an LDS instruction between VALU instructions costs their pairing); accumulation of
+    // column U (its src value converted two steps ago); the wait that leaves this step's four gathers in
+    // flight.  SADn / ADRn: the instruction that forms output n's table index and the one that turns it
+    // into an LDS address (J1: one v_sad_u32 does both).
+#define RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, SAD0, SAD1, SAD2, SAD3, ADR0, ADR1, ADR2, \
+                     ADR3)                                                                       \
+    {                                                                                            \
+        float w0_, w1_, w2_, w3_;                                                                \
+        uint32_t tj_;                                                                            \
+        asm volatile(RF_L2_READ(U)                                                               \
+                     "v_and_b32 %[tj], %[mask], %[t2]\n\t"                                       \
+                     SAD0 "v_mul_f32 %[w0], %[wv0], %[g0]\n\t"                                   \
+                     SAD1 "v_mul_f32 %[w1], %[wv1], %[g1]\n\t"                                   \
+                     SAD2 "v_mul_f32 %[w2], %[wv2], %[g2]\n\t"                                   \
+                     SAD3 "v_mul_f32 %[w3], %[wv3], %[g3]\n\t"                                   \
+                     "v_cvt_f32_ubyte3 %[s2], %[t2]\n\t"                                         \
+                     MID                                                                         \
+                     ADR0 "v_add_f32 %[ws0], %[ws0], %[w0]\n\t"                                  \
+                     ADR1 "v_add_f32 %[ws1], %[ws1], %[w1]\n\t"                                  \
+                     ADR2 "v_add_f32 %[ws2], %[ws2], %[w2]\n\t"                                  \
+                     ADR3 "v_add_f32 %[ws3], %[ws3], %[w3]\n\t"                                  \
+                     "ds_read_b32 %[a0], %[a0]\n\t"                                              \
+                     "ds_read_b32 %[a1], %[a1]\n\t"                                              \
+                     "ds_read_b32 %[a2], %[a2]\n\t"                                              \
+                     "ds_read_b32 %[a3], %[a3]\n\t"                                              \
+                     "v_mul_f32 %[w0], %[w0], %[s]\n\t"                                          \
+                     "v_mul_f32 %[w1], %[w1], %[s]\n\t"                                          \
+                     "v_mul_f32 %[w2], %[w2], %[s]\n\t"                                          \
+                     "v_mul_f32 %[w3], %[w3], %[s]\n\t"                                          \
+                     "v_add_f32 %[s0], %[s0], %[w0]\n\t"                                         \
+                     "v_add_f32 %[s1], %[s1], %[w1]\n\t"                                         \
+                     "v_add_f32 %[s2_], %[s2_], %[w2]\n\t"                                       \
+                     "v_add_f32 %[s3], %[s3], %[w3]\n\t"                                         \
+                     WAITTXT                                                                     \
+                     : RF_L2_TNOUT(U)[tj] "=&v"(tj_), [a0] "=&v"(GB[0]), [a1] "=&v"(GB[1]),      \
+                       [a2] "=&v"(GB[2]), [a3] "=&v"(GB[3]), [w0] "=&v"(w0_), [w1] "=&v"(w1_),   \
+                       [w2] "=&v"(w2_), [w3] "=&v"(w3_), [s2] "=&v"(sv[((U) + 2) & 3]),          \
+                       [ws0] "+v"(wsum[0]), [ws1] "+v"(wsum[1]), [ws2] "+v"(wsum[2]),            \
+                       [ws3] "+v"(wsum[3]), [s0] "+v"(sum[0][0]), [s1] "+v"(sum[1][0]),          \
+                       [s2_] "+v"(sum[2][0]), [s3] "+v"(sum[3][0])                               \
+                     : [ta] "v"(TA), [o0] "n"(O0), [o1] "n"(O1), [mask] "v"(mask),               \
+                       [t2] "v"(RF_L2_TQ((U) + 2)), [jc0] "v"(jc[0]), [jc1] "v"(jc[1]),          \
+                       [jc2] "v"(jc[2]), [jc3] "v"(jc[3]), [wv0] "s"(wv[4 - (U)]),               \
+                       [wv1] "s"(wv[5 - (U)]), [wv2] "s"(wv[6 - (U)]), [wv3] "s"(wv[7 - (U)]),   \
+                       [g0] "v"(GA[0]), [g1] "v"(GA[1]), [g2] "v"(GA[2]), [g3] "v"(GA[3]),       \
+                       [sh] "n"(SHIFT), [la] "v"(lut_lane_addr), [s] "v"(sv[(U)]));              \
+    }
+#define RF_L2_STEP(U, GA, GB, TA, O0, O1, MID, WAITTXT)                                           \
+    RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, "v_sad_u8 %[a0], %[tj], %[jc0], 0\n\t",      \
+                 "v_sad_u8 %[a1], %[tj], %[jc1], 0\n\t", "v_sad_u8 %[a2], %[tj], %[jc2], 0\n\t",  \
+                 "v_sad_u8 %[a3], %[tj], %[jc3], 0\n\t",                                         \
+                 "v_lshl_add_u32 %[a0], %[a0], %[sh], %[la]\n\t",                                \
+                 "v_lshl_add_u32 %[a1], %[a1], %[sh], %[la]\n\t",                                \
+                 "v_lshl_add_u32 %[a2], %[a2], %[sh], %[la]\n\t",                                \
+                 "v_lshl_add_u32 %[a3], %[a3], %[sh], %[la]\n\t")
+#define RF_L2_STEP_J1(U, GA, GB, TA, O0, O1, MID, WAITTXT)                                        \
+    RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, "v_sad_u32 %[a0], %[tj], %[jc0], %[la]\n\t", \
+                 "v_sad_u32 %[a1], %[tj], %[jc1], %[la]\n\t",                                    \
+                 "v_sad_u32 %[a2], %[tj], %[jc2], %[la]\n\t",                                    \
+                 "v_sad_u32 %[a3], %[tj], %[jc3], %[la]\n\t", "", "", "", "")
+    // (The last step of a row waits like any other: four gathers stay in flight across the row loop's
+    //  back edge, where the compiler writes code of its own - the next row's addresses.  That it moves
+    //  none of the registers in flight there is checked on the machine code, along every path of the
+    //  control-flow graph: tests/test_cabi.py.  A variant of this loop once got such a v_mov; a full wait
+    //  at the row end, which this loop had until the check walked branches, costs 0.3 %.)
+    // the window changes hands after the group: the empty statement is ordered behind step 3 and its full
+    // wait (both are volatile) and keeps the copy behind itself.  (Load and hand-over are statements of
+    // their own, outside any branch: where an SGPR tuple written by an asm statement meets a value of
+    // another origin at a join, the backend merges them in VGPRs and cannot give the result back to an
+    // "s" operand.)
+#define RF_L2_HAND_OVER                                                                          \
+    asm volatile("" : "+s"(wn8));                                                                \
+    ws8 = wn8;
+    // the next group's window: a scalar load of 8 floats from the table in global memory (scalar cache)
+#define RF_L2_LOAD_WINDOW(IDX)                                                                   \
+    {                                                                                            \
+        const float *wp_ = swsym + (IDX);                                                        \
+        asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(wn8) : "s"(wp_));                      \
+    }
+    // one group of four steps; NA / NB = address registers of the texel pairs read ahead (this row's next
+    // group or the next row's first one), PA / PB their ds_read2 offsets; the group's full wait - for the
+    // weight window requested before step 0 - sits in the middle of step 3, where nothing is in flight but
+    // the gathers of step 2, a whole step old (step 3 reads no texel pair)
+#define RF_L2_GROUP(STEP, NA, NB, PA, PB)                                                         \
+    {                                                                                            \
+        STEP(0, gg[0], gg[2], NA, PA, PB, "", "s_waitcnt lgkmcnt(4)")                            \
+        STEP(1, gg[1], gg[3], NA, 0, 0, "", "s_waitcnt lgkmcnt(4)")                              \
+        STEP(2, gg[2], gg[0], NB, PA, PB, "", "s_waitcnt lgkmcnt(4)")                            \
+        STEP(3, gg[3], gg[1], NB, 0, 0, "s_waitcnt lgkmcnt(0)\n\t", "s_waitcnt lgkmcnt(4)")      \
+    }
+#define RF_L2_ROW_LOOP(STEP)                                                                      \
+    for (int i = i_lo; i <= i_hi; i++) {                                                          \
+        uint32_t ta_next, tb_next, wa_next;                                                       \
+        int ngroups_next;                                                                         \
+        asm volatile("" : "+s"(hw_ahead)); /* behind the full waits of the row before */           \
+        row_addr(i < i_hi ? i + 1 : i, __builtin_amdgcn_readfirstlane(hw_ahead), ta_next,         \
+                 tb_next, wa_next, ngroups_next);                                                 \
+        {                                                                                         \
+            const int *hp_ = hwtab + ((i + 2 < i_hi ? i + 2 : i_hi) + radius);                    \
+            asm volatile("s_load_dword %0, %1, 0x0" : "=s"(hw_ahead) : "s"(hp_));                 \
+        }                                                                                         \
+        for (int gq = 0; gq < ngroups - 1; gq++) {                                                \
+            float wv[8];                                                                          \
+            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];                       \
+            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];                       \
+            wa_addr -= 4;                                                                         \
+            RF_L2_LOAD_WINDOW(wa_addr)                                                            \
+            RF_L2_GROUP(STEP, ta, tb, 1, Q4 + 1)                                                 \
+            RF_L2_HAND_OVER                                                                       \
+            ta += 4;                                                                              \
+            tb += 4;                                                                              \
+        }                                                                                         \
+        {                                                                                         \
+            float wv[8];                                                                          \
+            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];                       \
+            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];                       \
+            RF_L2_LOAD_WINDOW(wa_next)                                                            \
+            RF_L2_GROUP(STEP, ta_next, tb_next, 0, Q4)                                           \
+            RF_L2_HAND_OVER                                                                       \
+        }                                                                                         \
+        ta = ta_next;                                                                             \
+        wa_addr = wa_next;                                                                        \
+        ngroups = ngroups_next;                                                                   \
+        tb = tb_next;                                                                             \
+    }
+    if constexpr (J1) {
+        RF_L2_ROW_LOOP(RF_L2_STEP_J1)
+    } else {
+        RF_L2_ROW_LOOP(RF_L2_STEP)
+    }
+    // the last steps' gathers (of a row that does not exist) are still in flight: nothing may re-use
+    // their registers before they have landed
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(gg[0][0]), "+v"(gg[0][1]), "+v"(gg[0][2]), "+v"(gg[0][3]), "+v"(gg[1][0]),
+                   "+v"(gg[1][1]), "+v"(gg[1][2]), "+v"(gg[1][3]), "+v"(tp[0]), "+v"(tp[1]),
+                   "+s"(ws8), "+s"(wn8), "+s"(hw_ahead));
+#undef RF_L2_ROW_LOOP
+#undef RF_L2_GROUP
+#undef RF_L2_LOAD_WINDOW
+#undef RF_L2_HAND_OVER
+#undef RF_L2_STEP_J1
+#undef RF_L2_STEP
+#undef RF_L2_STEP_X
+#undef RF_L2_READ
+#undef RF_L2_READ_0
+#undef RF_L2_READ_1
+#undef RF_L2_READ_2
+#undef RF_L2_READ_3
+#undef RF_L2_TNOUT
+#undef RF_L2_TNOUT_0
+#undef RF_L2_TNOUT_1
+#undef RF_L2_TNOUT_2
+#undef RF_L2_TNOUT_3
+#undef RF_L2_TQ
+}
+
+// Hand-scheduled tap loop for colour tiles with 6-byte texels (main plane {B,G,R joint, B src},
+// second plane {G src, R src}): the arithmetic and the pipeline of jbf_tap_loop<3, LUTREP, false,
+// TLW, 6>, the row-carried prologue of jbf_tap_loop_grey4.  Per column step 44 VALU instructions,
+// 12 of them on the full pipe (v_and with the literal mask kept in a VGPR is not): 4 v_sad_u8,
+// 4 v_lshl_add_u32, 3 v_cvt_f32_ubyte*; hipcc emits the SADs and address computations as one
+// burst of nine, here each full-pipe instruction is followed by a simple one (v_mul/v_add).
+// SLAB: tap rows i_first .. i_last only, tile row of tap row i = ty + i + row_bias, sums ADDED to (see
+// jbf_tap_loop_grey4_la2).
+template <int LUTREP, int TLW, bool SLAB = false>
+__device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
+                                                  const float *__restrict__ swsym,
+                                                  uint32_t tile_lane_addr,
+                                                  uint32_t plane_b_lane_addr,
+                                                  const uint32_t (&jc)[kPix], int ty, int radius,
+                                                  int r4, int sw_len,
+                                                  const int *__restrict__ hwtab,
+                                                  float (&sum)[kPix][3], float (&wsum)[kPix],
+                                                  int i_first = 0, int i_last = 0, int row_bias = 0)
+{
+    const int i_lo = SLAB ? i_first : -radius, i_hi = SLAB ? i_last : radius;
+    const int bias = SLAB ? row_bias : radius;
+    constexpr int Q4 = TLW / 4;
+    constexpr int SHIFT = LUTREP == 32 ? 7 : LUTREP == 16 ? 6 : LUTREP == 8 ? 5 : 4;
+    static_assert(LUTREP == 32 || LUTREP == 16 || LUTREP == 8 || LUTREP == 4, "LUT replicas");
+    uint32_t mask = 0x00ffffffu;
+    asm volatile("" : "+v"(mask));  // keep the mask in a VGPR (a literal operand is full-pipe)
+
+    // Rows start at the even column -hws and run whole groups of four, as in jbf_tap_loop_grey4_la2.
+    // Steps 0, 1 of a group read columns 2, 3 of the group through the address pair (ta, tb), steps 2, 3
+    // read columns 0, 1 of the NEXT group through (ta2, tb2) - the row's phase decides which planes of
+    // the column-interleaved tile those are, the offsets in the instructions do not change.
+    auto row_addr = [&](int i, uint32_t &ta_out, uint32_t &tb_out, uint32_t &ta2_out,
+                        uint32_t &tb2_out, uint32_t &wa_out, int &ngroups_out) {
+        const int hw = hwtab[i + radius];
+        const int hws = (hw + 1) & ~1;
+        const int ai = i < 0 ? -i : i;
+        const int c0 = r4 - hws;  // first column, relative to the lane's quad origin
+        const uint32_t quad = (uint32_t)((ty + i + bias) * TLW + (c0 >> 2));
+        const bool phase = ((c0 >> 1) & 1) != 0;
+        const uint32_t q23 = quad + (phase ? 1u : 2u * Q4);  // columns 2, 3 of the row's first group
+        const uint32_t q01 = quad + (phase ? 2u * Q4 : 0u);  // columns 0, 1 of the row's first group
+        ta_out = tile_lane_addr + q23 * 4;
+        tb_out = plane_b_lane_addr + q23 * 2;
+        ta2_out = tile_lane_addr + q01 * 4;
+        tb2_out = plane_b_lane_addr + q01 * 2;
+        wa_out = (uint32_t)(ai * sw_len + (r4 + 8) + hws - 4);  // index of the first window's first weight
+        ngroups_out = (hws + hw + 4 + 3) >> 2;
+    };
+
+    uint32_t tq[4], tqb[4];
+    // the weight window of a group in SGPRs, as in jbf_tap_loop_grey4_la2: every step ends with a full
+    // wait here, so the scalar load of the next window (issued in step 3, after that step's gathers)
+    // needs no wait of its own
+    typedef float float8v __attribute__((ext_vector_type(8)));
+    float8v ws8, wn8;
+    float gg[2][kPix];
+    uint32_t ta, tb, ta2, tb2, wa_addr;
+    int ngroups;
+    row_addr(i_lo, ta, tb, ta2, tb2, wa_addr, ngroups);
+    // prologue of the first tap row (later rows get theirs from the last group of the row before)
+    asm volatile("ds_read_b32 %0, %4\n\t"
+                 "ds_read_b32 %1, %4 offset:%6\n\t"
+                 "ds_read_u16 %2, %5\n\t"
+                 "ds_read_u16 %3, %5 offset:%7"
+                 : "=&v"(tq[0]), "=&v"(tq[1]), "=&v"(tqb[0]), "=&v"(tqb[1])
+                 : "v"(ta2), "v"(tb2), "n"(Q4 * 4), "n"(Q4 * 2));
+    {
+        const float *wp = swsym + wa_addr;
+        asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(ws8) : "s"(wp));
+    }
+    // (a scalar load returns out of order: the first texel needs a full wait as well)
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(tq[0]), "+v"(tq[1]), "+v"(tqb[0]), "+v"(tqb[1]), "+s"(ws8));
+    {
+        const uint32_t tj = tq[0] & mask;
+#pragma unroll
+        for (int p = 0; p < kPix; p++) {
+            const uint32_t a = __builtin_amdgcn_sad_u8(tj, jc[p], 0u) * (LUTREP * 4u) + lut_lane_addr;
+            asm volatile("ds_read_b32 %0, %1" : "=v"(gg[0][p]) : "v"(a));
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(gg[0][0]), "+v"(gg[0][1]), "+v"(gg[0][2]), "+v"(gg[0][3]));
+
+    // Column step U: texel (both planes) of column +2 from TA/TB + offset, SAD + gathers of column
+    // +1, accumulation of column +0.  GA = gathers consumed, GB = gathers issued (their registers
+    // hold alpha, then the LDS address, then the LUT value).
+#define RF_C6_STEP(U, GA, GB, TA, TB, OFFT, EXTRA_ASM, EXTRA_OPERANDS)                           \
+    {                                                                                            \
+        float w0_, w1_, w2_, w3_, s0_, s1_, s2_, m0_, m1_, m2_, m3_;                             \
+        uint32_t tj_;                                                                            \
+        EXTRA_ASM /* (step 3: the next window's scalar load; the step ends in a full wait) */    \
+        asm volatile("ds_read_b32 %[tn], %[ta] offset:%[off4]\n\t"                               \
+                     "ds_read_u16 %[tnb], %[tb] offset:%[off2]\n\t"                              \
+                     "v_and_b32 %[tj], %[mask], %[t1]\n\t"                                       \
+                     "v_sad_u8 %[a0], %[tj], %[jc0], 0\n\t"                                      \
+                     "v_mul_f32 %[w0], %[wv0], %[g0]\n\t"                                        \
+                     "v_sad_u8 %[a1], %[tj], %[jc1], 0\n\t"                                      \
+                     "v_mul_f32 %[w1], %[wv1], %[g1]\n\t"                                        \
+                     "v_sad_u8 %[a2], %[tj], %[jc2], 0\n\t"                                      \
+                     "v_mul_f32 %[w2], %[wv2], %[g2]\n\t"                                        \
+                     "v_sad_u8 %[a3], %[tj], %[jc3], 0\n\t"                                      \
+                     "v_mul_f32 %[w3], %[wv3], %[g3]\n\t"                                        \
+                     "v_cvt_f32_ubyte3 %[s0], %[t0]\n\t"                                         \
+                     "v_add_f32 %[ws0], %[ws0], %[w0]\n\t"                                       \
+                     "v_cvt_f32_ubyte0 %[s1], %[tb0]\n\t"                                        \
+                     "v_add_f32 %[ws1], %[ws1], %[w1]\n\t"                                       \
+                     "v_cvt_f32_ubyte1 %[s2], %[tb0]\n\t"                                        \
+                     "v_add_f32 %[ws2], %[ws2], %[w2]\n\t"                                       \
+                     "v_lshl_add_u32 %[a0], %[a0], %[sh], %[la]\n\t"                             \
+                     "v_add_f32 %[ws3], %[ws3], %[w3]\n\t"                                       \
+                     "v_lshl_add_u32 %[a1], %[a1], %[sh], %[la]\n\t"                             \
+                     "v_mul_f32 %[m0], %[w0], %[s0]\n\t"                                         \
+                     "v_lshl_add_u32 %[a2], %[a2], %[sh], %[la]\n\t"                             \
+                     "v_mul_f32 %[m1], %[w1], %[s0]\n\t"                                         \
+                     "v_lshl_add_u32 %[a3], %[a3], %[sh], %[la]\n\t"                             \
+                     "v_mul_f32 %[m2], %[w2], %[s0]\n\t"                                         \
+                     "ds_read_b32 %[a0], %[a0]\n\t"                                              \
+                     "ds_read_b32 %[a1], %[a1]\n\t"                                              \
+                     "ds_read_b32 %[a2], %[a2]\n\t"                                              \
+                     "ds_read_b32 %[a3], %[a3]\n\t"                                              \
+                     "v_mul_f32 %[m3], %[w3], %[s0]\n\t"                                         \
+                     "v_add_f32 %[c00], %[c00], %[m0]\n\t"                                       \
+                     "v_add_f32 %[c10], %[c10], %[m1]\n\t"                                       \
+                     "v_add_f32 %[c20], %[c20], %[m2]\n\t"                                       \
+                     "v_add_f32 %[c30], %[c30], %[m3]\n\t"                                       \
+                     "v_mul_f32 %[m0], %[w0], %[s1]\n\t"                                         \
+                     "v_mul_f32 %[m1], %[w1], %[s1]\n\t"                                         \
+                     "v_mul_f32 %[m2], %[w2], %[s1]\n\t"                                         \
+                     "v_mul_f32 %[m3], %[w3], %[s1]\n\t"                                         \
+                     "v_add_f32 %[c01], %[c01], %[m0]\n\t"                                       \
+                     "v_add_f32 %[c11], %[c11], %[m1]\n\t"                                       \
+                     "v_add_f32 %[c21], %[c21], %[m2]\n\t"                                       \
+                     "v_add_f32 %[c31], %[c31], %[m3]\n\t"                                       \
+                     "v_mul_f32 %[m0], %[w0], %[s2]\n\t"                                         \
+                     "v_mul_f32 %[m1], %[w1], %[s2]\n\t"                                         \
+                     "v_mul_f32 %[m2], %[w2], %[s2]\n\t"                                         \
+                     "v_mul_f32 %[m3], %[w3], %[s2]\n\t"                                         \
+                     "v_add_f32 %[c02], %[c02], %[m0]\n\t"                                       \
+                     "v_add_f32 %[c12], %[c12], %[m1]\n\t"                                       \
+                     "v_add_f32 %[c22], %[c22], %[m2]\n\t"                                       \
+                     "v_add_f32 %[c32], %[c32], %[m3]\n\t"                                       \
+                     "s_waitcnt lgkmcnt(0)"                                                      \
+                     : [tn] "=&v"(tq[((U) + 2) & 3]), [tnb] "=&v"(tqb[((U) + 2) & 3]),           \
+                       [tj] "=&v"(tj_), [a0] "=&v"(GB[0]), [a1] "=&v"(GB[1]), [a2] "=&v"(GB[2]), \
+                       [a3] "=&v"(GB[3]), [w0] "=&v"(w0_), [w1] "=&v"(w1_), [w2] "=&v"(w2_),     \
+                       [w3] "=&v"(w3_), [s0] "=&v"(s0_), [s1] "=&v"(s1_), [s2] "=&v"(s2_),       \
+                       [m0] "=&v"(m0_), [m1] "=&v"(m1_), [m2] "=&v"(m2_), [m3] "=&v"(m3_),       \
+                       [ws0] "+v"(wsum[0]), [ws1] "+v"(wsum[1]), [ws2] "+v"(wsum[2]),            \
+                       [ws3] "+v"(wsum[3]),                                                      \
+                       [c00] "+v"(sum[0][0]), [c10] "+v"(sum[1][0]), [c20] "+v"(sum[2][0]),      \
+                       [c30] "+v"(sum[3][0]), [c01] "+v"(sum[0][1]), [c11] "+v"(sum[1][1]),      \
+                       [c21] "+v"(sum[2][1]), [c31] "+v"(sum[3][1]), [c02] "+v"(sum[0][2]),      \
+                       [c12] "+v"(sum[1][2]), [c22] "+v"(sum[2][2]), [c32] "+v"(sum[3][2])       \
+                       EXTRA_OPERANDS                                                            \
+                     : [ta] "v"(TA), [tb] "v"(TB), [off4] "n"((OFFT) * 4), [off2] "n"((OFFT) * 2), \
+                       [mask] "v"(mask), [t1] "v"(tq[((U) + 1) & 3]), [t0] "v"(tq[(U)]),         \
+                       [tb0] "v"(tqb[(U)]), [jc0] "v"(jc[0]), [jc1] "v"(jc[1]), [jc2] "v"(jc[2]), \
+                       [jc3] "v"(jc[3]), [wv0] "s"(wv[4 - (U)]), [wv1] "s"(wv[5 - (U)]),         \
+                       [wv2] "s"(wv[6 - (U)]), [wv3] "s"(wv[7 - (U)]), [g0] "v"(GA[0]),          \
+                       [g1] "v"(GA[1]), [g2] "v"(GA[2]), [g3] "v"(GA[3]), [sh] "n"(SHIFT),       \
+                       [la] "v"(lut_lane_addr));                                                 \
+    }
+#define RF_C6_NOASM
+#define RF_C6_COMMA_W , "+s"(wn8)
+#define RF_C6_LOAD_WINDOW(IDX)                                                                   \
+    {                                                                                            \
+        const float *wp_ = swsym + (IDX);                                                        \
+        asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(wn8) : "s"(wp_));                      \
+    }
+
+    for (int i = i_lo; i <= i_hi; i++) {
+        uint32_t ta_next, tb_next, ta2_next, tb2_next, wa_next;
+        int ngroups_next;
+        row_addr(i < i_hi ? i + 1 : i, ta_next, tb_next, ta2_next, tb2_next, wa_next, ngroups_next);
+        for (int gq = 0; gq < ngroups - 1; gq++) {
+            float wv[8];
+            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];
+            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];
+            RF_C6_STEP(0, gg[0], gg[1], ta, tb, 0, RF_C6_NOASM, )
+            RF_C6_STEP(1, gg[1], gg[0], ta, tb, Q4, RF_C6_NOASM, )
+            RF_C6_STEP(2, gg[0], gg[1], ta2, tb2, 1, RF_C6_NOASM, )
+            wa_addr -= 4;
+            RF_C6_STEP(3, gg[1], gg[0], ta2, tb2, Q4 + 1, RF_C6_LOAD_WINDOW(wa_addr),
+                       RF_C6_COMMA_W)
+            ws8 = wn8;
+            ta += 4;
+            tb += 2;
+            ta2 += 4;
+            tb2 += 2;
+        }
+        {
+            float wv[8];
+            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];
+            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];
+            RF_C6_STEP(0, gg[0], gg[1], ta, tb, 0, RF_C6_NOASM, )
+            RF_C6_STEP(1, gg[1], gg[0], ta, tb, Q4, RF_C6_NOASM, )
+            // the columns past the end of this row carry no weight: fetch the next row's first two
+            RF_C6_STEP(2, gg[0], gg[1], ta2_next, tb2_next, 0, RF_C6_NOASM, )
+            RF_C6_STEP(3, gg[1], gg[0], ta2_next, tb2_next, Q4, RF_C6_LOAD_WINDOW(wa_next),
+                       RF_C6_COMMA_W)
+            ws8 = wn8;
+        }
+        ta = ta_next;
+        tb = tb_next;
+        ta2 = ta2_next;
+        tb2 = tb2_next;
+        wa_addr = wa_next;
+        ngroups = ngroups_next;
+    }
+#undef RF_C6_LOAD_WINDOW
+#undef RF_C6_COMMA_W
+#undef RF_C6_NOASM
+#undef RF_C6_STEP
+}
+#undef RF_LDS_READ_B64
+#undef RF_LDS_READ_B128
+#undef RF_LDS_READ_B32
+#undef RF_LDS_READ_B32_OFF
+#undef RF_LDS_READ_U16_OFF
+
+}  // namespace
+}  // namespace rf

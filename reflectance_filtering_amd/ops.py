@@ -49,19 +49,51 @@ def joint_bilateral_u8(joint, src, d, sigma_color, sigma_space, border=_ffi.BORD
     return out
 
 
-def check_points(points, point_offsets, n, h, w):
-    """Host copies of a point list for images of h x w: int32 [total,2] (x, y) and int32 [n+1]
-    offsets, checked (the C entry cannot read device points to check them)."""
+def _points_host(points, point_offsets, n):
+    """int64 host copies of a point list, [total,2] (x, y) and [n+1] offsets; the offsets checked."""
     pts = np.ascontiguousarray(np.asarray(points, dtype=np.int64).reshape(-1, 2))
     off = np.asarray(point_offsets, dtype=np.int64).ravel()
     if off.shape[0] != n + 1 or off[0] != 0 or off[-1] != pts.shape[0] or np.any(np.diff(off) < 0):
         raise ValueError("point_offsets must be %d non-decreasing values from 0 to the number of "
                          "points" % (n + 1))
-    if pts.shape[0] and (pts.min() < 0 or pts[:, 0].max() >= w or pts[:, 1].max() >= h):
-        raise IndexError("point outside the %dx%d images" % (w, h))
+    return pts, off
+
+
+def _points_int32(pts, off):
     if pts.shape[0] >= 2 ** 31:
         raise ValueError("too many points")
     return pts.astype(np.int32), off.astype(np.int32)
+
+
+def check_points(points, point_offsets, n, h, w):
+    """Host copies of a point list for images of h x w: int32 [total,2] (x, y) and int32 [n+1]
+    offsets, checked (the C entry cannot read device points to check them)."""
+    pts, off = _points_host(points, point_offsets, n)
+    if pts.shape[0] and (pts.min() < 0 or pts[:, 0].max() >= w or pts[:, 1].max() >= h):
+        raise IndexError("point outside the %dx%d images" % (w, h))
+    return _points_int32(pts, off)
+
+
+def _to_host(a, torch):
+    return a.cpu().numpy() if torch.is_tensor(a) else a
+
+
+def _points_out(sigma_pairs, total, scn, dev, torch):
+    """The sigma arrays of a point call (float64 [P] each) and its output [P, total, scn]."""
+    pairs = np.asarray(sigma_pairs, dtype=np.float64).reshape(-1, 2)
+    if pairs.shape[0] == 0:
+        raise ValueError("sigma_pairs is empty")
+    sc = np.ascontiguousarray(pairs[:, 0])
+    ss = np.ascontiguousarray(pairs[:, 1])
+    return sc, ss, torch.empty((pairs.shape[0], total, scn), dtype=torch.uint8, device=dev)
+
+
+def _points_stage(need, pts, off, dev, torch):
+    """The workspace of `need` bytes and the device copies of the points and their offsets."""
+    if need == 0:   # arguments the entry refuses: let it say why
+        need = 1
+    return (torch.empty(need, dtype=torch.uint8, device=dev), torch.from_numpy(pts).to(dev),
+            torch.from_numpy(off).to(dev))
 
 
 def joint_bilateral_points_u8(joint, src, points, point_offsets, sigma_pairs, d=-1,
@@ -81,30 +113,16 @@ def joint_bilateral_points_u8(joint, src, points, point_offsets, sigma_pairs, d=
     if joint.shape[:3] != src.shape[:3]:
         raise ValueError("joint and src must have the same N,H,W")
     n, h, w, scn = src.shape
-    if torch.is_tensor(points):
-        points = points.cpu().numpy()
-    if torch.is_tensor(point_offsets):
-        point_offsets = point_offsets.cpu().numpy()
-    pts, off = check_points(points, point_offsets, n, h, w)
-    pairs = np.asarray(sigma_pairs, dtype=np.float64).reshape(-1, 2)
-    if pairs.shape[0] == 0:
-        raise ValueError("sigma_pairs is empty")
-    sc = np.ascontiguousarray(pairs[:, 0])
-    ss = np.ascontiguousarray(pairs[:, 1])
+    pts, off = check_points(_to_host(points, torch), _to_host(point_offsets, torch), n, h, w)
     total = pts.shape[0]
-    dev = src.device
-    out = torch.empty((pairs.shape[0], total, scn), dtype=torch.uint8, device=dev)
-    need = lib.rf_jbf_points_workspace_bytes(pairs.shape[0], ss.ctypes.data, int(d),
+    sc, ss, out = _points_out(sigma_pairs, total, scn, src.device, torch)
+    need = lib.rf_jbf_points_workspace_bytes(sc.shape[0], ss.ctypes.data, int(d),
                                              joint.shape[3], int(flags))
     if n == 0 or total == 0:
         return out
-    if need == 0:   # arguments the entry refuses: let it say why
-        need = 1
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    d_pts = torch.from_numpy(pts).to(dev)
-    d_off = torch.from_numpy(off).to(dev)
+    ws, d_pts, d_off = _points_stage(need, pts, off, src.device, torch)
     rc = lib.rf_jbf_points_u8(joint.data_ptr(), src.data_ptr(), n, h, w, joint.shape[3], scn,
-                              d_pts.data_ptr(), d_off.data_ptr(), total, pairs.shape[0],
+                              d_pts.data_ptr(), d_off.data_ptr(), total, sc.shape[0],
                               sc.ctypes.data, ss.ctypes.data, int(d), int(border), int(flags),
                               out.data_ptr(), ws.data_ptr(), ws.numel(),
                               _ffi.current_stream_ptr(torch))
@@ -117,11 +135,7 @@ def check_points_ragged(points, point_offsets, sizes):
     the size of its own image.  Returns int32 [total,2] (x, y) and int32 [n+1] offsets."""
     sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
     n = sizes.shape[0]
-    pts = np.ascontiguousarray(np.asarray(points, dtype=np.int64).reshape(-1, 2))
-    off = np.asarray(point_offsets, dtype=np.int64).ravel()
-    if off.shape[0] != n + 1 or off[0] != 0 or off[-1] != pts.shape[0] or np.any(np.diff(off) < 0):
-        raise ValueError("point_offsets must be %d non-decreasing values from 0 to the number of "
-                         "points" % (n + 1))
+    pts, off = _points_host(points, point_offsets, n)
     if n and sizes.min() <= 0:
         raise ValueError("image sizes must be positive")
     hw = np.repeat(sizes, np.diff(off), axis=0)                 # the (h, w) each point is held to
@@ -130,9 +144,7 @@ def check_points_ragged(points, point_offsets, sizes):
         k = int(bad[0])
         raise IndexError("point %d (x %d, y %d) outside the %dx%d image %d" % (
             k, pts[k, 0], pts[k, 1], hw[k, 1], hw[k, 0], int(np.searchsorted(off, k, "right")) - 1))
-    if pts.shape[0] >= 2 ** 31:
-        raise ValueError("too many points")
-    return pts.astype(np.int32), off.astype(np.int32)
+    return _points_int32(pts, off)
 
 
 def pack_images(images, name, torch):
@@ -186,35 +198,21 @@ def joint_bilateral_points_ragged_u8(joints, srcs, points, point_offsets, sigma_
                                  "all images" % (name, npx))
     n = sizes.shape[0]
     scn = srcs.shape[1]
-    if torch.is_tensor(points):
-        points = points.cpu().numpy()
-    if torch.is_tensor(point_offsets):
-        point_offsets = point_offsets.cpu().numpy()
-    pts, off = check_points_ragged(points, point_offsets, sizes)
+    pts, off = check_points_ragged(_to_host(points, torch), _to_host(point_offsets, torch), sizes)
     if sizes.size and sizes.max() >= 2 ** 31:
         raise ValueError("image too large")
-    pairs = np.asarray(sigma_pairs, dtype=np.float64).reshape(-1, 2)
-    if pairs.shape[0] == 0:
-        raise ValueError("sigma_pairs is empty")
-    sc = np.ascontiguousarray(pairs[:, 0])
-    ss = np.ascontiguousarray(pairs[:, 1])
     total = pts.shape[0]
-    dev = srcs.device
-    out = torch.empty((pairs.shape[0], total, scn), dtype=torch.uint8, device=dev)
+    sc, ss, out = _points_out(sigma_pairs, total, scn, srcs.device, torch)
     if n == 0 or total == 0:
         return out
-    need = lib.rf_jbf_points_ragged_workspace_bytes(n, pairs.shape[0], ss.ctypes.data, int(d),
+    need = lib.rf_jbf_points_ragged_workspace_bytes(n, sc.shape[0], ss.ctypes.data, int(d),
                                                     joints.shape[1], int(flags))
-    if need == 0:   # arguments the entry refuses: let it say why
-        need = 1
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    d_pts = torch.from_numpy(pts).to(dev)
-    d_off = torch.from_numpy(off).to(dev)
+    ws, d_pts, d_off = _points_stage(need, pts, off, srcs.device, torch)
     hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
     wds = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
     rc = lib.rf_jbf_points_ragged_u8(joints.data_ptr(), srcs.data_ptr(), n, hs.ctypes.data,
                                      wds.ctypes.data, joints.shape[1], scn, d_pts.data_ptr(),
-                                     d_off.data_ptr(), total, pairs.shape[0], sc.ctypes.data,
+                                     d_off.data_ptr(), total, sc.shape[0], sc.ctypes.data,
                                      ss.ctypes.data, int(d), int(border), int(flags),
                                      out.data_ptr(), ws.data_ptr(), ws.numel(),
                                      _ffi.current_stream_ptr(torch))
