@@ -73,6 +73,36 @@ int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst, int n, int
               int flags, void *stream);
 
 /*
+ * rf_jbf_u8 over images of different sizes (IIW photos come in many shapes) in one call.
+ *   joint, src, dst  the n images tightly packed one after another: image i starts at pixel
+ *                  sum over j < i of heights[j] * widths[j] (offsets are formed in 64 bits) and is
+ *                  heights[i] rows of widths[i] pixels; dst must not overlap joint or src (judged
+ *                  on the summed pixel count)
+ *   heights, widths  n ints each, HOST memory: every entry must be > 0 (RF_E_BADARG otherwise, and
+ *                  for a NULL array)
+ *   workspace      device scratch, 16-byte aligned, of at least rf_jbf_ragged_workspace_bytes(n,
+ *                  heights, widths, joint_cn, src_cn, d, sigma_space, flags) bytes: 32 bytes per 64x64
+ *                  tile of every image (ceil(h/64) * ceil(w/64) each), rounded up to 256; 0 = arguments
+ *                  the call refuses.  A NULL, misaligned or smaller workspace is RF_E_BADARG.
+ * The bytes written for image i are, byte for byte, what rf_jbf_u8(n = 1, heights[i], widths[i], ...)
+ * writes with the same other arguments; sigma, radius, flag, channel and border rules and refusals
+ * are rf_jbf_u8's; n == 0 is RF_OK whatever the pointers are.
+ * Radius <= 52 (the paper's c20 s22 and c15 s28 among them): the tiles of all images run in one
+ * launch per tile shape - at most four - from one record per tile (first pixel, height, width, tile
+ * origin), staged in the workspace by one copy.  For that copy the call SYNCHRONISES THE STREAM once.
+ * Every other route of rf_jbf_u8 (radius 53 and up, RF_JBF_FORCE_GENERIC, a device whose LDS probe
+ * fails, the "jbf_tune" debug switch) is taken by calling rf_jbf_u8 once per image: the same bytes
+ * with n launches and no synchronisation.  Either way the call is refused (RF_E_UNSUPPORTED) on a
+ * stream that is being captured into a graph.
+ */
+size_t rf_jbf_ragged_workspace_bytes(int n, const int *heights, const int *widths, int joint_cn,
+                                     int src_cn, int d, double sigma_space, int flags);
+int rf_jbf_ragged_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst, int n,
+                     const int *heights, const int *widths, int joint_cn, int src_cn, int d,
+                     double sigma_color, double sigma_space, int border, int flags, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
+/*
  * Guided filter, 8-bit, colour guide.
  * Replaces  cv2.ximgproc.guidedFilter(guide, src, radius, eps)  as called at
  * /root/reference/filter_reflectance.py:67-70 (radius = int(sigma_spatial), eps = sigma_color).

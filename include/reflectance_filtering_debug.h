@@ -70,7 +70,8 @@
  *
  * Besides the switches, rf_debug_jbf_points_plan reports the launch plan of rf_jbf_points_u8 (how
  * its parameter sets are cut into chunks and how many points a wave of each chunk takes) without
- * touching a device, so that tests can assert which lane mapping a call runs at.
+ * touching a device, so that tests can assert which lane mapping a call runs at, and
+ * rf_debug_jbf_ragged_plan the tile classes rf_jbf_ragged_u8 launches.
  */
 #ifndef REFLECTANCE_FILTERING_DEBUG_H
 #define REFLECTANCE_FILTERING_DEBUG_H
@@ -103,6 +104,20 @@ const char *rf_debug_build_info(void);
  * or a negative RF_E* for arguments the entry refuses.  Host only: needs no device. */
 int rf_debug_jbf_points_plan(int n_params, const double *sigma_space, int d, int joint_cn, int flags,
                              int total_points, int *out, int max_chunks);
+
+/* The launches of rf_jbf_ragged_u8 for these arguments: per tile class, in launch order (64x64
+ * tiles, the 32x128 and 16x256 bottom strips, the 128x32 right strip; classes without tiles are
+ * left out), the four ints {tile rows, tile columns, row pitch, tiles of all images} for the first
+ * `cap` launches at out[4 * launch].  Decided by the planning function the entry launches from (the
+ * debug switches included; the LDS probe of the device is not consulted).  Returns the number of
+ * launches (it may exceed cap; out may be NULL when cap is 0), -1 where the entry falls back to
+ * rf_jbf_u8 once per image, or the entry's RF_E_UNSUPPORTED (-2) for channels or a radius it
+ * refuses.  RF_E_BADARG (bad sizes, NULL size arrays, unknown flag bits, a bad cap) is -1 as well:
+ * for n > 0 and a valid cap, rf_jbf_ragged_workspace_bytes of the same arguments is 0 exactly when
+ * the entry refuses them, which tells the two apart.  Host only: needs no device. */
+int rf_debug_jbf_ragged_plan(int n, const int *heights, const int *widths, int joint_cn, int src_cn,
+                             int d, double sigma_color, double sigma_space, int flags, int *out,
+                             int cap);
 
 #ifdef __cplusplus
 }

@@ -31,11 +31,11 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
            "rf_colorize_srgb_u8", "rf_whdr_f32", "rf_jbf_f32_workspace_bytes", "rf_jbf_f32",
            "rf_gf_f32_workspace_bytes", "rf_gf_f32", "rf_jbf_points_workspace_bytes",
            "rf_jbf_points_u8", "rf_jbf_points_ragged_workspace_bytes", "rf_jbf_points_ragged_u8",
-           "rf_whdr_points_u8")
+           "rf_whdr_points_u8", "rf_jbf_ragged_workspace_bytes", "rf_jbf_ragged_u8")
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
-                 "rf_debug_jbf_points_plan")
+                 "rf_debug_jbf_points_plan", "rf_debug_jbf_ragged_plan")
 # switches that leave work out (wrong results, timing experiments only); all others keep the bytes
 RESULT_CHANGING_OPTIONS = ("jbf_stage_only", "gf_exp_skip")
 
@@ -108,6 +108,11 @@ def load_library():
         lib.rf_jbf_points_ragged_u8.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, ci, ci, vp, vp, ci,
                                                 ci, ci, vp, vp, sz, vp]
         lib.rf_jbf_points_ragged_u8.restype = ci
+        lib.rf_jbf_ragged_workspace_bytes.argtypes = [ci, vp, vp, ci, ci, ci, cd, ci]
+        lib.rf_jbf_ragged_workspace_bytes.restype = sz
+        lib.rf_jbf_ragged_u8.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, ci, cd, cd, ci, ci, vp, sz,
+                                         vp]
+        lib.rf_jbf_ragged_u8.restype = ci
         lib.rf_whdr_points_u8.argtypes = [vp, ci, ctypes.c_longlong, ci, ci, vp, vp, vp, vp, cd, vp,
                                           vp]
         lib.rf_whdr_points_u8.restype = ci
@@ -119,6 +124,8 @@ def load_library():
         lib.rf_debug_build_info.restype = ctypes.c_char_p
         lib.rf_debug_jbf_points_plan.argtypes = [ci, vp, ci, ci, ci, ci, vp, ci]
         lib.rf_debug_jbf_points_plan.restype = ci
+        lib.rf_debug_jbf_ragged_plan.argtypes = [ci, vp, vp, ci, ci, ci, cd, cd, ci, vp, ci]
+        lib.rf_debug_jbf_ragged_plan.restype = ci
         # RF_DEBUG_OPTIONS="name=value,...": preset the test / benchmark switches of
         # include/reflectance_filtering_debug.h for a whole process (timing experiments only).
         # Every preset is announced on stderr - loudly for the switches that change results.
@@ -191,6 +198,33 @@ def jbf_points_plan(sigma_space, d, joint_cn, flags, total_points):
     if lib.rf_debug_jbf_points_plan(*(args + (out.ctypes.data, nchunks))) != nchunks:
         raise RFError("rf_debug_jbf_points_plan: the chunk count changed between two calls")
     return [tuple(int(v) for v in row) for row in out[:nchunks]]
+
+
+def jbf_ragged_plan(sizes, joint_cn, src_cn, d, sigma_color, sigma_space, flags=0):
+    """The launches of rf_jbf_ragged_u8 for images of these sizes ([n,2] (h, w))
+    (rf_debug_jbf_ragged_plan, host only): one (tile rows, tile cols, pitch, tiles) tuple per
+    launch, or None where the entry falls back to one rf_jbf_u8 call per image."""
+    import numpy as np
+    lib = load_library()
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
+    ws = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
+    out = np.zeros((4, 4), dtype=np.int32)
+    rc = lib.rf_debug_jbf_ragged_plan(sizes.shape[0], hs.ctypes.data, ws.ctypes.data, int(joint_cn),
+                                      int(src_cn), int(d), float(sigma_color), float(sigma_space),
+                                      int(flags), out.ctypes.data, 4)
+    if rc == -1:
+        # -1 is the fall-back and RF_E_BADARG alike: a workspace size of 0 (for n > 0) says refused
+        if sizes.shape[0] == 0 or lib.rf_jbf_ragged_workspace_bytes(
+                sizes.shape[0], hs.ctypes.data, ws.ctypes.data, int(joint_cn), int(src_cn), int(d),
+                float(sigma_space), int(flags)) > 0:
+            return None
+        lib.rf_debug_jbf_ragged_plan(sizes.shape[0], hs.ctypes.data, ws.ctypes.data, int(joint_cn),
+                                     int(src_cn), int(d), float(sigma_color), float(sigma_space),
+                                     int(flags), out.ctypes.data, 4)     # (its message again)
+    if rc < 0:
+        check(rc, "rf_debug_jbf_ragged_plan")
+    return [tuple(int(v) for v in row) for row in out[:rc]]
 
 
 def require_gpu():

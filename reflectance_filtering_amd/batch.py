@@ -7,8 +7,9 @@ files shards embarrassingly: each rank (torchrun sets RANK/WORLD_SIZE/LOCAL_RANK
 contiguous slice of the sorted file list and works through it in steps of 16 files as a pipeline
 - a thread pool decodes the next step and encodes the previous one while the device filters the
 current one - grouping the images of a step by size, pushing each group through the
-device-resident batch operators and writing the same output files the single-image tools would
-write.  No collective is involved.
+device-resident batch operators (a bilateral step whose images differ in size goes through one
+ragged call instead, filter_reflectance.apply_filter_list) and writing the same output files the
+single-image tools would write.  No collective is involved.
 
     python -m reflectance_filtering_amd.batch filter --filter_type=bilateral --sigma_color=20 \
         --sigma_spatial=22 --inputs 'out/*-r.png' --guidance 'photos/{stem}.png' --path_out out
@@ -142,7 +143,32 @@ def filter_files(filter_type, inputs, guidance_pattern, sigma_color, sigma_spati
             raise ValueError("input {} and its guidance differ in size".format(f))
         return f, img, gui
 
+    def out_name(f):
+        name = f
+        for _ in range(iterations):  # the chained CLI runs append the suffix once per pass
+            name = fr.output_filename(name, path_out, filter_type, sigma_color, sigma_spatial)
+        return name
+
+    def compute_ragged(loaded):
+        """A bilateral step whose images differ in shape: one ragged call per pass over the whole
+        step (fr.apply_filter_list) instead of one launch per run of equal shapes.  The grey
+        reductions of `compute` below, judged over the step: identical bytes."""
+        grey_src = all(_is_grey(t[1]) for t in loaded)
+        grey_gui = grey_src and all(_is_grey(t[2]) for t in loaded)
+        cut = lambda a, grey: np.ascontiguousarray(a[..., :1]) if grey else a
+        images = [torch.from_numpy(cut(t[1], grey_src)).cuda() for t in loaded]
+        joints = [torch.from_numpy(cut(t[2], grey_gui)).cuda() for t in loaded]
+        outs = fr.apply_filter_list(filter_type, images, joints, sigma_color, sigma_spatial,
+                                    iterations=iterations, grey_as_bgr=grey_gui)
+        jobs = []
+        for (f, _, _), res in zip(loaded, outs):
+            res = res.cpu().numpy()
+            jobs.append((out_name(f), np.repeat(res, 3, axis=2) if grey_src else res))
+        return jobs
+
     def compute(loaded):
+        if filter_type == "bilateral" and len(set(t[1].shape for t in loaded)) > 1:
+            return compute_ragged(loaded)
         jobs = []
         for group in group_by_shape(loaded, lambda t: t[1].shape):
             imgs = np.stack([t[1] for t in group])
@@ -175,11 +201,7 @@ def filter_files(filter_type, inputs, guidance_pattern, sigma_color, sigma_spati
             if grey_src:
                 out = np.repeat(out, 3, axis=3)
             for (f, _, _), res in zip(group, out):
-                name = f
-                for _ in range(iterations):  # the chained CLI runs append the suffix once per pass
-                    name = fr.output_filename(name, path_out, filter_type, sigma_color,
-                                              sigma_spatial)
-                jobs.append((name, res))
+                jobs.append((out_name(f), res))
         return jobs
 
     return pipeline(mine, load, compute)

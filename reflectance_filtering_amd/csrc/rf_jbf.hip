@@ -11,6 +11,9 @@
 //   jbf_tile64_kernel  default for radius <= 52: one workgroup = 64x64 output tile (32x128,
 //                      16x256 or 128x32 for the image's remainder rows / columns), 1024 threads
 //                      (4 waves/SIMD), LDS-staged texel tile, LUT at the end of LDS.
+//                      Its kRagged instantiation serves rf_jbf_ragged_u8 (images of different sizes
+//                      packed one after another): the tile's image, size and origin come from a
+//                      32-byte record per workgroup; everything after that read is the same code.
 //   jbf_slab_kernel    radius 53..468: the same 64x64 outputs with the disk's tap rows taken in slabs
 //                      (row pitch 208 .. 1008; the grey loop; a colour src in one pass of the colour
 //                      loop, or one pass per channel of the grey loop where that leaves no slab).
@@ -46,6 +49,15 @@ constexpr int kJbfMaxTiledR4 = 468;  // radius (rounded up to 4) the slab kernel
 // rf_debug_option() as the kernels see them
 constexpr int kJbfStageOnly = 0x1000, kJbfCompilerLoop = 0x2000, kJbfTile64Only = 0x4000;
 constexpr int kJbfLookahead1 = 0x8000;  // grey asm loop with its gathers one column step ahead (round-4 form)
+
+// the test / benchmark switches (rf_debug_option) as they travel to the kernels: private flag bits
+int jbf_debug_flags()
+{
+    return (debug_get(kDbgJbfStageOnly) ? kJbfStageOnly : 0) |
+           (debug_get(kDbgJbfCompilerLoop) ? kJbfCompilerLoop : 0) |
+           (debug_get(kDbgJbfTile64Only) ? kJbfTile64Only : 0) |
+           (debug_get(kDbgJbfLookahead1) ? kJbfLookahead1 : 0);
+}
 
 // Four consecutive pixels (cn interleaved bytes each, any alignment) -> four packed dwords.
 __device__ inline void load_packed4(const uint8_t *img, size_t pix, int cn, uint32_t (&out)[4])
@@ -358,15 +370,36 @@ __global__ __launch_bounds__(16 * TH) void jbf_tiled2_kernel(
 // ------------------------------------------------------------------------------------------
 constexpr int kT64Lds = 163840;
 
+// One tile of a ragged launch (rf_jbf_ragged_u8: images of different sizes packed one after
+// another): where its image starts in the packed buffers, the image's size and the tile's origin.
+// Written by the host, one per workgroup, indexed by the xcd_contiguous_tile id.
+struct alignas(16) JbfTileRec {
+    unsigned long long first;  // pixels before the image
+    int h, w, tile_y0, tile_x0, pad[2];
+};
+static_assert(sizeof(JbfTileRec) == 32, "the workspace holds 32 bytes per tile");
+
+// The tiles argument of jbf_tile64_kernel: tiles per image row (uniform launch: every image is
+// h x w), or the tile records (ragged launch; h, w, tiles_per_img, y_base, x_base are unused).
+template <bool kRagged>
+struct JbfTilesArg {
+    using type = int;
+};
+template <>
+struct JbfTilesArg<true> {
+    using type = const JbfTileRec *__restrict__;
+};
+
 // TH = tile rows: 64 (64x64 tile), or 32 / 16 for the 32x128 and 16x256 strips that cover the
 // last h % 64 rows (same 1024 lanes, same tap loops, less padding; 3-channel sources only have
 // the 32-row strip, whose colour tile still fits the LDS in one pass).
-template <int SCN, int GREP, int CREP, int TLW, int TH = 64>
+template <int SCN, int GREP, int CREP, int TLW, int TH = 64, bool kRagged = false>
 __global__ __launch_bounds__(1024) void jbf_tile64_kernel(
     const uint8_t *__restrict__ joint, const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
     int h, int w, int jcn, int radius, int border, const float *__restrict__ lut, int nz,
-    const int *__restrict__ hwtab, const float *__restrict__ swsym, int sw_len, int tiles_x,
-    int tiles_per_img, int flags, int crows, int y_base, int x_base)
+    const int *__restrict__ hwtab, const float *__restrict__ swsym, int sw_len,
+    typename JbfTilesArg<kRagged>::type tiles_x, int tiles_per_img, int flags, int crows, int y_base,
+    int x_base)
 {
     constexpr int NT = 1024;
     constexpr int QW = NT / TH;   // lanes (4-pixel quads) per tile row
@@ -391,11 +424,23 @@ __global__ __launch_bounds__(1024) void jbf_tile64_kernel(
 
     const int tid = threadIdx.x;
     const int tile_id = xcd_contiguous_tile((int)blockIdx.x, (int)gridDim.x);
-    const int img_idx = tile_id / tiles_per_img;
-    const int t_in_img = tile_id - img_idx * tiles_per_img;
-    const int tile_y0 = y_base + (t_in_img / tiles_x) * TH;
-    const int tile_x0 = x_base + (t_in_img % tiles_x) * TW;
-    const size_t img = (size_t)img_idx * h * w;
+    int tile_y0, tile_x0;
+    size_t img;
+    if constexpr (kRagged) {
+        // one record per workgroup: the same words in every lane (scalar loads, scalar registers)
+        const JbfTileRec *rec = tiles_x + tile_id;
+        img = (size_t)rec->first;
+        h = rec->h;
+        w = rec->w;
+        tile_y0 = rec->tile_y0;
+        tile_x0 = rec->tile_x0;
+    } else {
+        const int img_idx = tile_id / tiles_per_img;
+        const int t_in_img = tile_id - img_idx * tiles_per_img;
+        tile_y0 = y_base + (t_in_img / tiles_x) * TH;
+        tile_x0 = x_base + (t_in_img % tiles_x) * TW;
+        img = (size_t)img_idx * h * w;
+    }
     const int r4 = (radius + 3) & ~3;
     const int tx = tid % QW;
     const int ty = tid / QW;
@@ -767,22 +812,27 @@ int launch_tile64(const JbfTables &t, int nz, int crows, const uint8_t *joint, c
 // 1024 lanes x all taps).  3-channel sources only have the 32x128 strip, whose colour tile still
 // fits the LDS in one pass.  Strips may overlap at the bottom right corner: both write the same
 // bytes.
-template <int SCN, int GREP, int CREP>
-int launch_tile64_rows(const JbfTables &t, int nz, int crows, const uint8_t *joint,
-                       const uint8_t *src, uint8_t *dst, int n, int h, int w, int jcn, int border,
-                       int flags, hipStream_t stream)
+// The areas of an h x w image: 64x64 tiles cover [0, rows_main) x [0, cols_main), the 32x128 strip
+// the s32 rows below them, the 16x256 strip the s16 rows below that, the 128x32 strip the last sx
+// columns over all h rows.  Decided here for the uniform launches and the ragged ones alike.
+struct Tile64Areas {
+    int rows_main, cols_main, s32, s16, sx;
+};
+
+Tile64Areas tile64_areas(const JbfTables &t, int nz, int grep, int crep, int scn, int flags, int h,
+                         int w)
 {
     const bool only64 = (flags & kJbfTile64Only) != 0;  // benchmark / test aid: 64x64 tiles only
     // ---- right strip (single-channel sources)
     int sx = 0;
-    if (SCN == 1 && !only64 && (w & 63) > 0 && (w & 63) <= 32 &&
-        tile64_fits(t, nz, GREP, CREP, SCN, 136, 128, flags) > 0 && ceil_div(h, 128) < ceil_div(h, 64))
+    if (scn == 1 && !only64 && (w & 63) > 0 && (w & 63) <= 32 &&
+        tile64_fits(t, nz, grep, crep, scn, 136, 128, flags) > 0 && ceil_div(h, 128) < ceil_div(h, 64))
         sx = w & 63;
     const int cols_main = w - sx;
     // ---- bottom strips
     const int rem = h & 63;
-    const bool ok32 = tile64_fits(t, nz, GREP, CREP, SCN, 208, 32, flags) > 0;
-    const bool ok16 = SCN == 1 && tile64_fits(t, nz, GREP, CREP, SCN, 336, 16, flags) > 0;
+    const bool ok32 = tile64_fits(t, nz, grep, crep, scn, 208, 32, flags) > 0;
+    const bool ok16 = scn == 1 && tile64_fits(t, nz, grep, crep, scn, 336, 16, flags) > 0;
     int s32 = 0, s16 = 0;  // rows given to each strip
     if (rem > 0 && rem <= 16 && ok16)
         s16 = rem;
@@ -794,7 +844,16 @@ int launch_tile64_rows(const JbfTables &t, int nz, int crows, const uint8_t *joi
         (s32 ? ceil_div(cols_main, 128) : 0) + (s16 ? ceil_div(cols_main, 256) : 0);
     if (only64 || cols_main == 0 || ((s32 || s16) && strip_blocks >= ceil_div(cols_main, 64)))
         s32 = s16 = 0;
-    const int rows_main = h - s32 - s16;
+    return Tile64Areas{h - s32 - s16, cols_main, s32, s16, sx};
+}
+
+template <int SCN, int GREP, int CREP>
+int launch_tile64_rows(const JbfTables &t, int nz, int crows, const uint8_t *joint,
+                       const uint8_t *src, uint8_t *dst, int n, int h, int w, int jcn, int border,
+                       int flags, hipStream_t stream)
+{
+    const Tile64Areas a = tile64_areas(t, nz, GREP, CREP, SCN, flags, h, w);
+    const int rows_main = a.rows_main, cols_main = a.cols_main, s32 = a.s32, s16 = a.s16, sx = a.sx;
     int rc = RF_OK;
     if (rows_main > 0 && cols_main > 0)
         rc = launch_tile64<SCN, GREP, CREP, 144>(t, nz, crows, joint, src, dst, n, h, w, jcn,
@@ -811,6 +870,128 @@ int launch_tile64_rows(const JbfTables &t, int nz, int crows, const uint8_t *joi
         if (rc == RF_OK && sx)
             rc = launch_tile64<1, GREP, CREP, 136, 128>(t, nz, 32, joint, src, dst, n, h, w, jcn,
                                                         border, flags, stream, 0, h, cols_main, sx);
+    }
+    return rc;
+}
+
+// The tile shapes jbf_tile64_kernel is instantiated for, in order of preference:
+// X(grey LUT replicas, colour LUT replicas, row pitch).  Row pitch 144 serves radius <= 36, 176
+// radius <= 52 (colour tiles of the wide pitch run in 16- or 8-row passes).
+#define RF_T64_SHAPES(X)                                                                          \
+    X(32, 32, 144) X(32, 16, 144) X(16, 8, 144) X(8, 4, 144) X(32, 16, 176) X(32, 8, 176)         \
+    X(32, 4, 176) X(16, 8, 176) X(8, 4, 176)
+
+struct Tile64Shape {
+    int grep, crep, tlw, crows;  // crows: rows per colour pass (tile64_fits)
+};
+
+// The shape a call runs at; it depends on the tables, not on the image sizes.  False: none fits.
+// A colour src first looks for a shape whose colour tile fits in ONE pass over the 64 rows,
+// on all 1024 lanes, even with fewer LUT replicas - down to 8 - (the reference's c15 s28,
+// README.md:64, at pitch 176: 8 replicas, +3.5 % over two 32-row passes on half the lanes
+// with 16), then for one that needs passes.
+bool tile64_choose(const JbfTables &t, int nz, int src_cn, int flags, Tile64Shape *out)
+{
+    for (int min_rows = src_cn == 3 ? 64 : 1; min_rows >= 1; min_rows = min_rows == 64 ? 1 : 0) {
+#define RF_T64_TRY(G_, C_, W_)                                                                    \
+    if ((min_rows < 64 || C_ >= 8) && tile64_fits(t, nz, G_, C_, src_cn, W_, 64, flags) >= min_rows) { \
+        *out = Tile64Shape{G_, C_, W_, tile64_fits(t, nz, G_, C_, src_cn, W_, 64, flags)};        \
+        return true;                                                                              \
+    }
+        RF_T64_SHAPES(RF_T64_TRY)
+#undef RF_T64_TRY
+    }
+    return false;
+}
+
+// ---- ragged form (rf_jbf_ragged_u8) ------------------------------------------------------------
+// The tile classes of a ragged call in launch order: {tile rows, row pitch}; tile columns = 4096 / rows.
+constexpr int kRaggedClasses = 4;
+constexpr int kRaggedTh[kRaggedClasses] = {64, 32, 16, 128};
+constexpr int kRaggedPitch144[kRaggedClasses] = {144, 208, 336, 136};
+
+// What a ragged call launches: the shape (once per call) and, per tile class, the records of all
+// images' tiles in image order.  tile64_areas decides per image, as for a uniform launch.
+struct RaggedPlan {
+    bool tiled = false;  // false: the entry falls back to one uniform call per image
+    Tile64Shape shape{};
+    std::vector<JbfTileRec> recs[kRaggedClasses];
+};
+
+void plan_ragged(const JbfTables &t, int n, const int *heights, const int *widths, int src_cn,
+                 int flags, int tune, RaggedPlan *plan)
+{
+    const int nz = t.lut_len < 256 * t.joint_cn ? t.lut_len - 1 : t.lut_len;
+    plan->tiled = !(flags & RF_JBF_FORCE_GENERIC) && tune == 0 &&
+                  tile64_choose(t, nz, src_cn, flags, &plan->shape);
+    if (!plan->tiled)
+        return;
+    const Tile64Shape &s = plan->shape;
+    unsigned long long first = 0;
+    for (int i = 0; i < n; i++) {
+        const int h = heights[i], w = widths[i];
+        Tile64Areas a{h, w, 0, 0, 0};  // the wide pitch has 64x64 tiles alone
+        if (s.tlw == 144)
+            a = tile64_areas(t, nz, s.grep, s.crep, src_cn, flags, h, w);
+        // {y_base, rows, x_base, cols} of each class's area, as launch_tile64_rows hands them on
+        const int area[kRaggedClasses][4] = {{0, a.rows_main, 0, a.cols_main},
+                                             {a.rows_main, a.s32, 0, a.cols_main},
+                                             {a.rows_main + a.s32, a.s16, 0, a.cols_main},
+                                             {0, a.sx ? h : 0, a.cols_main, a.sx}};
+        for (int c = 0; c < kRaggedClasses; c++) {
+            const int th = kRaggedTh[c], tw = 4096 / th;
+            for (int y = 0; y < area[c][1]; y += th)
+                for (int x = 0; x < area[c][3]; x += tw)
+                    plan->recs[c].push_back(
+                        JbfTileRec{first, h, w, area[c][0] + y, area[c][2] + x, {0, 0}});
+        }
+        first += (unsigned long long)h * w;
+    }
+}
+
+// One tile class of a ragged call: every image's tiles of TH rows in one launch.
+template <int SCN, int GREP, int CREP, int TLW, int TH>
+int launch_tile64_ragged(const JbfTables &t, int nz, int crows, const uint8_t *joint,
+                         const uint8_t *src, uint8_t *dst, const JbfTileRec *d_recs, size_t ntiles,
+                         int jcn, int border, int flags, hipStream_t stream)
+{
+    if (ntiles == 0)
+        return RF_OK;
+    if (ntiles > (size_t)0x7fffffff)
+        return fail(RF_E_UNSUPPORTED, "rf_jbf_ragged_u8: too many tiles for one launch");
+    auto kern = jbf_tile64_kernel<SCN, GREP, CREP, TLW, TH, true>;
+    RF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kT64Lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(1024), kT64Lds, stream, joint, src, dst, 0,
+                       0, jcn, t.radius, border, t.d_lut, nz, t.d_hw, t.d_swsym, t.sw_len, d_recs, 0,
+                       flags, crows, 0, 0);
+    return RF_OK;
+}
+
+// The launches of a ragged plan; d_recs[c] = the device copy of plan.recs[c].
+template <int SCN, int GREP, int CREP, int TLW>
+int launch_ragged(const JbfTables &t, int nz, const RaggedPlan &plan, const uint8_t *joint,
+                  const uint8_t *src, uint8_t *dst, const JbfTileRec *const *d_recs, int jcn,
+                  int border, int flags, hipStream_t stream)
+{
+    int rc = launch_tile64_ragged<SCN, GREP, CREP, TLW, 64>(t, nz, plan.shape.crows, joint, src, dst,
+                                                            d_recs[0], plan.recs[0].size(), jcn,
+                                                            border, flags, stream);
+    if constexpr (TLW == 144) {
+        if (rc == RF_OK)
+            rc = launch_tile64_ragged<SCN, GREP, CREP, 208, 32>(t, nz, 32, joint, src, dst, d_recs[1],
+                                                                plan.recs[1].size(), jcn, border,
+                                                                flags, stream);
+        if constexpr (SCN == 1) {
+            if (rc == RF_OK)
+                rc = launch_tile64_ragged<1, GREP, CREP, 336, 16>(t, nz, 32, joint, src, dst,
+                                                                  d_recs[2], plan.recs[2].size(), jcn,
+                                                                  border, flags, stream);
+            if (rc == RF_OK)
+                rc = launch_tile64_ragged<1, GREP, CREP, 136, 128>(t, nz, 32, joint, src, dst,
+                                                                   d_recs[3], plan.recs[3].size(),
+                                                                   jcn, border, flags, stream);
+        }
     }
     return rc;
 }
@@ -1006,11 +1187,8 @@ extern "C" int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst,
         return fail(RF_E_BADARG, "rf_jbf_u8: NULL image pointer");
     if (n < 0 || h <= 0 || w <= 0)
         return fail(RF_E_BADARG, "rf_jbf_u8: bad size n=%d h=%d w=%d", n, h, w);
-    if ((joint_cn != 1 && joint_cn != 3) || (src_cn != 1 && src_cn != 3))
-        return fail(RF_E_UNSUPPORTED, "rf_jbf_u8: channels must be 1 or 3 (joint %d, src %d)",
-                    joint_cn, src_cn);
-    if (border < 0 || border > 4)
-        return fail(RF_E_UNSUPPORTED, "rf_jbf_u8: border type %d", border);
+    if (int bad = jbf_check_format("rf_jbf_u8", joint_cn, src_cn, border))
+        return bad;
     {
         const size_t px = (size_t)n * h * w;
         if (ranges_overlap(dst, px * src_cn, joint, px * joint_cn) ||
@@ -1019,11 +1197,7 @@ extern "C" int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst,
     }
     if (flags & ~kJbfPublicFlags)
         return fail(RF_E_BADARG, "rf_jbf_u8: unknown flag bits 0x%x", flags);
-    // test / benchmark switches (rf_debug_option) travel to the kernels as private flag bits
-    flags |= (debug_get(kDbgJbfStageOnly) ? kJbfStageOnly : 0) |
-             (debug_get(kDbgJbfCompilerLoop) ? kJbfCompilerLoop : 0) |
-             (debug_get(kDbgJbfTile64Only) ? kJbfTile64Only : 0) |
-             (debug_get(kDbgJbfLookahead1) ? kJbfLookahead1 : 0);
+    flags |= jbf_debug_flags();
     // OpenCV's sigma and radius rules, RF_JBF_GREY_AS_BGR: rf_jbf_common.hpp
     sigma_color = jbf_sigma(sigma_color);
     sigma_space = jbf_sigma(sigma_space);
@@ -1058,45 +1232,31 @@ extern "C" int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst,
         // table entries before the zero tail (the whole table if it has none)
         const int nz = t.lut_len < 256 * joint_cn ? t.lut_len - 1 : t.lut_len;
         if (oob_ok) {
-            // row pitch 144 serves radius <= 36, 176 radius <= 52 (colour tiles of the wide
-            // pitch run in 16- or 8-row passes)
+            Tile64Shape shape;
+            if (tile64_choose(t, nz, src_cn, flags, &shape)) {
 #define RF_T64(G_, C_, W_)                                                                        \
-    if (!done && (min_rows < 64 || C_ >= 8) &&                                                    \
-        tile64_fits(t, nz, G_, C_, src_cn, W_, 64, flags) >= min_rows) {                          \
-        const int crows_ = tile64_fits(t, nz, G_, C_, src_cn, W_, 64, flags);                     \
+    if (shape.grep == G_ && shape.crep == C_ && shape.tlw == W_) {                                \
         if (W_ == 144)                                                                            \
-            rc = src_cn == 3 ? launch_tile64_rows<3, G_, C_>(t, nz, crows_, joint, src, dst, n,   \
-                                                             h, w, jcn_kernel, border, flags,     \
+            rc = src_cn == 3 ? launch_tile64_rows<3, G_, C_>(t, nz, shape.crows, joint, src, dst, \
+                                                             n, h, w, jcn_kernel, border, flags,  \
                                                              stream)                              \
-                             : launch_tile64_rows<1, G_, C_>(t, nz, crows_, joint, src, dst, n,   \
-                                                             h, w, jcn_kernel, border, flags,     \
+                             : launch_tile64_rows<1, G_, C_>(t, nz, shape.crows, joint, src, dst, \
+                                                             n, h, w, jcn_kernel, border, flags,  \
                                                              stream);                             \
         else                                                                                      \
-            rc = src_cn == 3 ? launch_tile64<3, G_, C_, W_>(t, nz, crows_, joint, src, dst, n, h, \
-                                                            w, jcn_kernel, border, flags, stream) \
-                             : launch_tile64<1, G_, C_, W_>(t, nz, crows_, joint, src, dst, n, h, \
-                                                            w, jcn_kernel, border, flags, stream);\
-        if (rc != RF_OK)                                                                          \
-            return rc;                                                                            \
-        done = true;                                                                              \
+            rc = src_cn == 3 ? launch_tile64<3, G_, C_, W_>(t, nz, shape.crows, joint, src, dst,  \
+                                                            n, h, w, jcn_kernel, border, flags,   \
+                                                            stream)                               \
+                             : launch_tile64<1, G_, C_, W_>(t, nz, shape.crows, joint, src, dst,  \
+                                                            n, h, w, jcn_kernel, border, flags,   \
+                                                            stream);                              \
     }
-            // A colour src first looks for a shape whose colour tile fits in ONE pass over the 64 rows,
-            // on all 1024 lanes, even with fewer LUT replicas - down to 8 - (the reference's c15 s28,
-            // README.md:64, at pitch 176: 8 replicas, +3.5 % over two 32-row passes on half the lanes
-            // with 16), then for one that needs passes.
-            for (int min_rows = src_cn == 3 ? 64 : 1; min_rows >= 1 && !done;
-                 min_rows = min_rows == 64 ? 1 : 0) {
-                RF_T64(32, 32, 144)
-                RF_T64(32, 16, 144)
-                RF_T64(16, 8, 144)
-                RF_T64(8, 4, 144)
-                RF_T64(32, 16, 176)
-                RF_T64(32, 8, 176)
-                RF_T64(32, 4, 176)
-                RF_T64(16, 8, 176)
-                RF_T64(8, 4, 176)
-            }
+                RF_T64_SHAPES(RF_T64)
 #undef RF_T64
+                if (rc != RF_OK)
+                    return rc;
+                done = true;
+            }
             // radius 53..468: tap-row slabs (jbf_slab_kernel) at the narrowest pitch that holds r4
             if (!done && t.r4 > 52 && t.r4 <= kJbfMaxTiledR4) {
                 int tlw = 0;
@@ -1168,6 +1328,187 @@ extern "C" int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst,
                            jcn_kernel, src_cn, border, t.d_lut, t.d_di, t.d_dj, t.d_sw, t.maxk,
                            flags);
     }
+    RF_HIP_CHECK(hipGetLastError());
+    return RF_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Ragged form: images of different sizes packed one after another, one launch per tile class
+// over all images (radius <= 52), else rf_jbf_u8 once per image.
+// ------------------------------------------------------------------------------------------
+namespace rf {
+namespace {
+
+// The checks of both ragged entries and of the plan query that need no device: sizes, channels,
+// flags, radius.  *px = pixels of all images, *tiles = their 64x64-tile count (no plan has more
+// tiles: a strip is only taken where it saves workgroups).
+int ragged_check(const char *who, int n, const int *heights, const int *widths, int joint_cn,
+                 int src_cn, int d, double sigma_space, int border, int flags, size_t *px,
+                 size_t *tiles)
+{
+    if (!heights || !widths)
+        return fail(RF_E_BADARG, "%s: NULL size array", who);
+    if (n < 0)
+        return fail(RF_E_BADARG, "%s: bad size n=%d", who, n);
+    *px = *tiles = 0;
+    for (int i = 0; i < n; i++) {
+        if (heights[i] <= 0 || widths[i] <= 0)
+            return fail(RF_E_BADARG, "%s: bad size of image %d: h=%d w=%d", who, i, heights[i],
+                        widths[i]);
+        *px += (size_t)heights[i] * widths[i];
+        *tiles += (size_t)ceil_div(heights[i], 64) * ceil_div(widths[i], 64);
+        if (*px > ((size_t)1 << 60))
+            return fail(RF_E_BADARG, "%s: the images hold too many pixels", who);
+    }
+    if (int bad = jbf_check_format(who, joint_cn, src_cn, border))
+        return bad;
+    if (flags & ~kJbfPublicFlags)
+        return fail(RF_E_BADARG, "%s: unknown flag bits 0x%x", who, flags);
+    const int radius = jbf_radius(d, jbf_sigma(sigma_space));
+    if (radius > kJbfMaxRadius)
+        return fail(RF_E_UNSUPPORTED, "%s: radius %d too large", who, radius);
+    return RF_OK;
+}
+
+size_t ragged_bytes(size_t tiles) { return (tiles * sizeof(JbfTileRec) + 255) & ~(size_t)255; }
+
+}  // namespace
+}  // namespace rf
+
+extern "C" size_t rf_jbf_ragged_workspace_bytes(int n, const int *heights, const int *widths,
+                                                int joint_cn, int src_cn, int d, double sigma_space,
+                                                int flags)
+{
+    using namespace rf;
+    size_t px, tiles;
+    if (ragged_check("rf_jbf_ragged_workspace_bytes", n, heights, widths, joint_cn, src_cn, d,
+                     sigma_space, RF_BORDER_DEFAULT, flags, &px, &tiles) != RF_OK)
+        return 0;
+    return ragged_bytes(tiles);
+}
+
+extern "C" int rf_debug_jbf_ragged_plan(int n, const int *heights, const int *widths, int joint_cn,
+                                        int src_cn, int d, double sigma_color, double sigma_space,
+                                        int flags, int *out, int cap)
+{
+    using namespace rf;
+    size_t px, tiles;
+    if (cap < 0 || (cap > 0 && !out))
+        return fail(RF_E_BADARG, "rf_debug_jbf_ragged_plan: bad cap=%d", cap);
+    if (int bad = ragged_check("rf_debug_jbf_ragged_plan", n, heights, widths, joint_cn, src_cn, d,
+                               sigma_space, RF_BORDER_DEFAULT, flags, &px, &tiles))
+        return bad;
+    std::vector<float> lut;
+    const JbfTables t = jbf_host_tables(jbf_radius(d, jbf_sigma(sigma_space)),
+                                        jbf_table_cn(joint_cn, flags), jbf_sigma(sigma_color),
+                                        jbf_sigma(sigma_space), lut);
+    RaggedPlan plan;
+    plan_ragged(t, n, heights, widths, src_cn, flags | jbf_debug_flags(),
+                debug_get(kDbgJbfTune) & 0xf, &plan);
+    if (!plan.tiled)
+        return -1;
+    int launches = 0;
+    for (int c = 0; c < kRaggedClasses; c++) {
+        if (plan.recs[c].empty())
+            continue;
+        if (launches < cap) {
+            out[4 * launches + 0] = kRaggedTh[c];
+            out[4 * launches + 1] = 4096 / kRaggedTh[c];
+            out[4 * launches + 2] = plan.shape.tlw == 144 ? kRaggedPitch144[c] : plan.shape.tlw;
+            out[4 * launches + 3] = (int)std::min<size_t>(plan.recs[c].size(), 0x7fffffff);
+        }
+        launches++;
+    }
+    return launches;
+}
+
+extern "C" int rf_jbf_ragged_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst, int n,
+                                const int *heights, const int *widths, int joint_cn, int src_cn,
+                                int d, double sigma_color, double sigma_space, int border, int flags,
+                                void *workspace, size_t workspace_bytes, void *stream_)
+{
+    using namespace rf;
+    const char *who = "rf_jbf_ragged_u8";
+    if (n == 0)  // an empty list is valid whatever the (possibly NULL) pointers are
+        return RF_OK;
+    if (!joint || !src || !dst)
+        return fail(RF_E_BADARG, "%s: NULL image pointer", who);
+    size_t px, tiles;
+    if (int bad = ragged_check(who, n, heights, widths, joint_cn, src_cn, d, sigma_space, border,
+                               flags, &px, &tiles))
+        return bad;
+    if (ranges_overlap(dst, px * src_cn, joint, px * joint_cn) ||
+        ranges_overlap(dst, px * src_cn, src, px * src_cn))
+        return fail(RF_E_BADARG, "%s: dst must not overlap an input", who);
+    if (!workspace || workspace_bytes < ragged_bytes(tiles) || ((uintptr_t)workspace & 15))
+        return fail(RF_E_BADARG, "%s: workspace of %zu bytes, %zu needed (16-byte aligned)", who,
+                    workspace ? workspace_bytes : (size_t)0, ragged_bytes(tiles));
+    hipStream_t stream = (hipStream_t)stream_;
+    if (stream_is_capturing(stream))
+        return fail(RF_E_UNSUPPORTED, "%s: synchronises its stream and cannot be captured into a "
+                                      "graph", who);
+    const int user_flags = flags;
+    flags |= jbf_debug_flags();
+    const double sc = jbf_sigma(sigma_color), ss = jbf_sigma(sigma_space);
+    const int radius = jbf_radius(d, ss);
+    const int jcn_kernel = jbf_kernel_cn(joint_cn, flags);
+    const int table_cn = jbf_table_cn(joint_cn, flags);
+    const int tune = debug_get(kDbgJbfTune) & 0xf;
+    RaggedPlan plan;
+    JbfTables t;
+    TablesHold hold{t};
+    // (no tile shape holds r4 > 52: such a call needs no tables here, rf_jbf_u8 fetches its own)
+    if (!(flags & RF_JBF_FORCE_GENERIC) && tune == 0 && ((radius + 3) & ~3) <= 52) {
+        int rc = get_tables(radius, table_cn, sc, ss, stream, &t);
+        if (rc != RF_OK)
+            return rc;
+        bool oob_ok = false;
+        rc = lds_oob_reads_zero(t.device, &oob_ok);
+        if (rc != RF_OK)
+            return rc;
+        if (oob_ok)
+            plan_ragged(t, n, heights, widths, src_cn, flags, tune, &plan);
+    }
+    if (!plan.tiled) {
+        // every other route (slab kernel, generic kernel, failed LDS probe, a tuning override):
+        // the uniform entry once per image - the same bytes with n launches
+        size_t first = 0;
+        for (int i = 0; i < n; i++) {
+            const int rc = rf_jbf_u8(joint + first * joint_cn, src + first * src_cn,
+                                     dst + first * src_cn, 1, heights[i], widths[i], joint_cn, src_cn,
+                                     d, sigma_color, sigma_space, border, user_flags, stream_);
+            if (rc != RF_OK)
+                return rc;
+            first += (size_t)heights[i] * widths[i];
+        }
+        return RF_OK;
+    }
+    // ---- the tile records of all classes, one after another, copied with one call ---------
+    std::vector<JbfTileRec> image;
+    const JbfTileRec *d_recs[kRaggedClasses];
+    for (int c = 0; c < kRaggedClasses; c++) {
+        d_recs[c] = static_cast<const JbfTileRec *>(workspace) + image.size();
+        image.insert(image.end(), plan.recs[c].begin(), plan.recs[c].end());
+    }
+    if (image.size() > tiles)
+        return fail(RF_E_HIP, "%s: tile count mismatch (internal)", who);
+    // the host image must outlive the copy: the copy is waited for before the launches (this is
+    // the call's one synchronisation of `stream`)
+    RF_HIP_CHECK(hipMemcpyAsync(workspace, image.data(), image.size() * sizeof(JbfTileRec),
+                                hipMemcpyHostToDevice, stream));
+    RF_HIP_CHECK(hipStreamSynchronize(stream));
+    const int nz = t.lut_len < 256 * table_cn ? t.lut_len - 1 : t.lut_len;
+    int rc = RF_OK;
+#define RF_T64(G_, C_, W_)                                                                        \
+    if (plan.shape.grep == G_ && plan.shape.crep == C_ && plan.shape.tlw == W_)                   \
+        rc = src_cn == 3 ? launch_ragged<3, G_, C_, W_>(t, nz, plan, joint, src, dst, d_recs,      \
+                                                        jcn_kernel, border, flags, stream)        \
+                         : launch_ragged<1, G_, C_, W_>(t, nz, plan, joint, src, dst, d_recs,      \
+                                                        jcn_kernel, border, flags, stream);
+    RF_T64_SHAPES(RF_T64)
+#undef RF_T64
+    if (rc != RF_OK)
+        return rc;
     RF_HIP_CHECK(hipGetLastError());
     return RF_OK;
 }

@@ -37,6 +37,17 @@ inline int jbf_kernel_cn(int joint_cn, int flags)
     return joint_cn == 1 && (flags & RF_JBF_GREY_AS_BGR) ? -1 : joint_cn;
 }
 
+// channel counts and border type every u8 entry accepts; `who` names the entry in the message
+inline int jbf_check_format(const char *who, int joint_cn, int src_cn, int border)
+{
+    if ((joint_cn != 1 && joint_cn != 3) || (src_cn != 1 && src_cn != 3))
+        return fail(RF_E_UNSUPPORTED, "%s: channels must be 1 or 3 (joint %d, src %d)", who,
+                    joint_cn, src_cn);
+    if (border < 0 || border > 4)
+        return fail(RF_E_UNSUPPORTED, "%s: border type %d", who, border);
+    return RF_OK;
+}
+
 inline bool stream_is_capturing(hipStream_t stream)
 {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;

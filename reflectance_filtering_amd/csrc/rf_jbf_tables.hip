@@ -117,6 +117,21 @@ TablesHold::~TablesHold()
     }
 }
 
+JbfTables jbf_host_tables(int radius, int joint_cn, double sigma_color, double sigma_space,
+                          std::vector<float> &lut)
+{
+    JbfTables t;
+    t.radius = radius;
+    t.joint_cn = joint_cn;
+    t.sigma_color = sigma_color;
+    t.sigma_space = sigma_space;
+    // keep entries up to and including the first exact zero (the LUT is non-increasing)
+    t.lut_len = jbf_colour_lut(joint_cn, sigma_color, lut);
+    t.r4 = (radius + 3) & ~3;
+    t.sw_len = 2 * (t.r4 + 8);
+    return t;
+}
+
 // Host-side parameter tables, computed in double exactly like jointBilateralFilter_8u does.
 int get_tables(int radius, int joint_cn, double sigma_color, double sigma_space, hipStream_t stream,
                JbfTables *out)
@@ -137,23 +152,15 @@ int get_tables(int radius, int joint_cn, double sigma_color, double sigma_space,
         note_use_on(*out, stream);
         return RF_OK;
     }
-    JbfTables t;
-    t.device = dev;
-    t.radius = radius;
-    t.joint_cn = joint_cn;
-    t.sigma_color = sigma_color;
-    t.sigma_space = sigma_space;
-    const int nlut = 256 * joint_cn;
     std::vector<float> lut;
-    // keep entries up to and including the first exact zero (the LUT is non-increasing)
-    t.lut_len = jbf_colour_lut(joint_cn, sigma_color, lut);
+    JbfTables t = jbf_host_tables(radius, joint_cn, sigma_color, sigma_space, lut);
+    t.device = dev;
+    const int nlut = 256 * joint_cn;
     const int d = 2 * radius + 1;
     std::vector<int> di, dj, hw;
     std::vector<float> sw;
     jbf_space_taps(radius, sigma_space, di, dj, sw, hw);
     t.maxk = (int)di.size();
-    t.r4 = (radius + 3) & ~3;
-    t.sw_len = 2 * (t.r4 + 8);
     std::vector<float> swsym((size_t)(radius + 1) * t.sw_len, 0.0f);
     for (size_t k = 0; k < di.size(); k++)
         if (di[k] >= 0)

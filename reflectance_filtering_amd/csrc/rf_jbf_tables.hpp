@@ -2,6 +2,7 @@
 // users see them: rf_jbf_u8 (rf_jbf.hip) and rf_jbf_f32 (rf_jbf_f32.hip).  Host only.
 #pragma once
 #include <memory>
+#include <vector>
 
 #include "rf_common.hpp"
 
@@ -25,6 +26,12 @@ struct JbfTables {
     float *d_swsym = nullptr;
     std::shared_ptr<void> keep;  // JbfTableOwner of the arrays above
 };
+
+// The fields of a parameter set that need no device - radius, joint_cn, the sigmas, r4, sw_len and
+// lut_len - which is all the launch plans read (rf_debug_jbf_ragged_plan); get_tables starts from it.
+// lut: the colour table (jbf_colour_lut).
+JbfTables jbf_host_tables(int radius, int joint_cn, double sigma_color, double sigma_space,
+                          std::vector<float> &lut);
 
 // While alive, this thread may make the "unsafe" runtime calls (allocation, creation of events,
 // synchronisation of OTHER streams) although one of its streams is capturing: the first use of a

@@ -118,6 +118,33 @@ def decompose_and_filter_batch(images, sigma_color=20.0, sigma_spatial=22.0, wei
     return r8, out.squeeze(-1)
 
 
+def decompose_and_filter_list(images, sigma_color=20.0, sigma_spatial=22.0, weights=None,
+                              filter_type="bilateral"):
+    """decompose_and_filter_batch for photos of different sizes: a list of CUDA uint8 BGR tensors
+    [H_i,W_i,3] -> (list of r_u8 [H_i,W_i], list of filtered [H_i,W_i]), each byte for byte what
+    decompose_and_filter_batch makes of that photo alone.  The network is per pixel, so the packed
+    photos go through it once as one image [1, 1, total pixels, 3]; 'bilateral' then filters the
+    packed grey maps in one ragged call (ops.joint_bilateral_ragged_u8), 'guided' in one batch per
+    group of equal shapes (filter_reflectance.apply_filter_list)."""
+    from . import filter_reflectance as fr
+    if filter_type not in ("bilateral", "guided"):
+        raise ValueError("filter_type must be 'bilateral' or 'guided'.")
+    torch = _ffi.require_gpu()
+    bgr, sizes = ops.pack_images(images, "images", torch)
+    if bgr.shape[1] != 3:
+        raise ValueError("images must have 3 channels")
+    _, r8 = ops.cnn_reflectance_u8(bgr.view(1, 1, -1, 3), weights=weights, want_float=False)
+    r1 = r8.view(-1, 1)
+    maps = ops.split_packed(r1, sizes)
+    if filter_type == "guided":
+        out = fr.apply_filter_list("guided", maps, maps, sigma_color, sigma_spatial,
+                                   grey_as_bgr=True)
+    else:
+        _, out = ops.joint_bilateral_ragged_u8(r1, r1, -1, sigma_color, sigma_spatial,
+                                               grey_as_bgr=True, sizes=sizes)
+    return [m.squeeze(-1) for m in maps], [o.squeeze(-1) for o in out]
+
+
 def decompose_batch(images, weights=None):
     """Everything decompose_image writes, for a device-resident batch: CUDA uint8 BGR
     [N,H,W,3] -> (r float32 [N,H,W], r_u8 [N,H,W] = `-r.png`, reflectance bytes [N,H,W,3] =

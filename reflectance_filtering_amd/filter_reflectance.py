@@ -15,7 +15,7 @@ import os
 import sys
 
 from . import image_utils as iu
-from . import ops, ximgproc
+from . import _ffi, ops, ximgproc
 
 FILTER_TYPES = ("bilateral", "guided")
 
@@ -70,6 +70,57 @@ def apply_filter_batch(filter_type, images, joints, sigma_color, sigma_spatial, 
         out = ops.joint_bilateral_u8(joints, out, -1, sigma_color, sigma_spatial,
                                      grey_as_bgr=grey_as_bgr)
     return out
+
+
+def _stack(images):
+    import torch
+    return torch.stack(list(images))
+
+
+def apply_filter_list(filter_type, images, joints, sigma_color, sigma_spatial, iterations=1,
+                      grey_as_bgr=False):
+    """apply_filter_batch for images of different sizes: ``images``/``joints`` are lists of CUDA
+    uint8 tensors [H_i,W_i,C] (equal C within a list, image i of both of one size); returns the
+    list of filtered images in the caller's order, each byte for byte what apply_filter_batch
+    makes of that image alone.  'bilateral' packs the list and runs it as one ragged call per
+    pass (ops.joint_bilateral_ragged_u8), the passes of ``iterations`` > 1 ping-ponging between
+    two packed buffers; 'guided' needs equal shapes and runs one batch per group of equal
+    shapes, wherever its members stand in the list."""
+    _check_params(filter_type, sigma_color, sigma_spatial)
+    if iterations < 1:
+        raise ValueError("iterations must be >= 1")
+    same = joints is images                  # self-guided: one list, packed once
+    images = list(images)
+    joints = images if same else list(joints)
+    if len(images) != len(joints):
+        raise ValueError("images and joints must have the same length")
+    for i, (im, jt) in enumerate(zip(images, joints)):
+        if tuple(im.shape[:2]) != tuple(jt.shape[:2]):
+            raise ValueError("image {} and its joint differ in size".format(i))
+    if not images:
+        return []
+    torch = _ffi.require_gpu()
+    if filter_type == "guided":
+        from .batch import group_by_shape
+        # (a flat key: group_by_shape takes its product as the bytes of an item)
+        key = lambda i: tuple(images[i].shape) + (joints[i].shape[2],)
+        out = [None] * len(images)
+        for run in group_by_shape(sorted(range(len(images)), key=key), key, max_bytes=1 << 30):
+            res = apply_filter_batch(filter_type, _stack([images[i] for i in run]),
+                                     _stack([joints[i] for i in run]), sigma_color, sigma_spatial,
+                                     iterations=iterations, grey_as_bgr=grey_as_bgr)
+            for i, r in zip(run, res):
+                out[i] = r
+        return out
+    src, sizes = ops.pack_images(images, "images", torch)
+    joint = src if joints is images else ops.pack_images(joints, "joints", torch)[0]
+    bufs = [torch.empty_like(src) for _ in range(min(iterations, 2))]
+    views = None
+    for it in range(iterations):
+        src, views = ops.joint_bilateral_ragged_u8(joint, src, -1, sigma_color, sigma_spatial,
+                                                   grey_as_bgr=grey_as_bgr, sizes=sizes,
+                                                   out=bufs[it % 2])
+    return views
 
 
 def output_filename(filename_in, path_out, filter_type, sigma_color, sigma_spatial):

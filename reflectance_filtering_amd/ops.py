@@ -11,11 +11,14 @@ _gf_workspaces = {}
 _GF_CACHE_PER_DEVICE = 4
 _GF_CACHE_BYTES_PER_DEVICE = 64 << 30     # ... and at most this much scratch kept per device
 _cnn_consts = {}
+_jbf_ragged_workspaces = {}
 
 
 def release_workspaces():
-    """Drop the cached guided-filter scratch buffers and CNN constants (device memory)."""
+    """Drop the cached guided-filter and ragged-bilateral scratch buffers and CNN constants
+    (device memory)."""
     _gf_workspaces.clear()
+    _jbf_ragged_workspaces.clear()
     _cnn_consts.clear()
     _steps_dev.clear()
 
@@ -161,22 +164,10 @@ def pack_images(images, name, torch):
     return torch.cat([t.view(-1, t.shape[2]) for t in images]), sizes
 
 
-def joint_bilateral_points_ragged_u8(joints, srcs, points, point_offsets, sigma_pairs, d=-1,
-                                     border=_ffi.BORDER_DEFAULT, flags=0, grey_as_bgr=False,
-                                     sizes=None):
-    """joint_bilateral_points_u8 over images of different sizes, in one launch
-    (rf_jbf_points_ragged_u8).  joints / srcs: lists of n CUDA uint8 tensors [H_i, W_i, C] (equal
-    C within a list; image i of both has the same H_i, W_i), or, with sizes = [n,2] (h, w), the
-    images already packed one after another as contiguous CUDA uint8 tensors [total pixels, C].
-    Returns CUDA uint8 [P, total, src_cn] with
-    out[p, k] = joint_bilateral_u8(joints[i][None], srcs[i][None], d, *sigma_pairs[p], ...)[0, y_k, x_k],
-    byte for byte, where point k = (x_k, y_k) = points[k] belongs to image i.  points /
-    point_offsets are host arrays, checked there against each image's own size.  Synchronises
-    the current stream."""
-    if grey_as_bgr:
-        flags |= _ffi.JBF_GREY_AS_BGR
-    torch = _ffi.require_gpu()
-    lib = _ffi.load_library()
+def _packed_pair(joints, srcs, sizes, torch):
+    """The image arguments of the ragged ops as packed tensors: lists of images are packed
+    (pack_images; joints is srcs stays one pack), packed tensors are checked against sizes.
+    Returns (joints [total pixels, C], srcs [total pixels, C], sizes int64 [n,2] (h, w))."""
     if sizes is None:
         same = joints is srcs
         srcs, sizes = pack_images(srcs, "srcs", torch)
@@ -196,6 +187,89 @@ def joint_bilateral_points_ragged_u8(joints, srcs, points, point_offsets, sigma_
                     and t.dim() == 2 and t.is_contiguous() and t.shape[0] == npx):
                 raise ValueError("%s must be a contiguous CUDA uint8 tensor [%d, C]: the pixels of "
                                  "all images" % (name, npx))
+    return joints, srcs, sizes
+
+
+def split_packed(packed, sizes):
+    """The [H_i, W_i, C] views of a packed tensor [total pixels, C], image by image."""
+    views, first = [], 0
+    for h, w in np.asarray(sizes, dtype=np.int64).reshape(-1, 2).tolist():
+        views.append(packed[first:first + h * w].view(h, w, packed.shape[1]))
+        first += h * w
+    return views
+
+
+def _jbf_ragged_workspace(need, device, torch):
+    """The tile-record scratch of joint_bilateral_ragged_u8 for the CURRENT stream of `device`, cached
+    per (device, stream) and grown on demand (work on one stream is ordered, so the next call's
+    copy cannot overtake the kernels still reading the records); release_workspaces() drops it."""
+    dev = device.index if device.index is not None else torch.cuda.current_device()
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _jbf_ragged_workspaces.get(key)
+    if ws is None or ws.numel() < need:
+        if len(_jbf_ragged_workspaces) >= 16:       # streams come and go
+            _jbf_ragged_workspaces.clear()
+        ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=device)
+        _jbf_ragged_workspaces[key] = ws
+    return ws
+
+
+def joint_bilateral_ragged_u8(joints, srcs, d, sigma_color, sigma_space, border=_ffi.BORDER_DEFAULT,
+                              flags=0, grey_as_bgr=False, sizes=None, out=None):
+    """joint_bilateral_u8 over images of different sizes in one call (rf_jbf_ragged_u8: radius <= 52
+    runs the tiles of all images in one launch per tile shape; a larger radius takes one launch
+    per image).  joints / srcs: lists of n CUDA uint8 tensors [H_i, W_i, C] (equal C within a
+    list; image i of both has the same H_i, W_i), or, with sizes = [n,2] (h, w), the images
+    already packed one after another as contiguous CUDA uint8 tensors [total pixels, C].
+    out: the packed result buffer [total pixels, src C], if the caller has one.
+    Returns (packed result [total pixels, src C], list of its [H_i, W_i, C] views); image i is,
+    byte for byte, joint_bilateral_u8(joints[i][None], srcs[i][None], ...)[0].  Synchronises
+    the current stream."""
+    if grey_as_bgr:
+        flags |= _ffi.JBF_GREY_AS_BGR
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    joints, srcs, sizes = _packed_pair(joints, srcs, sizes, torch)
+    if sizes.size and sizes.max() >= 2 ** 31:
+        raise ValueError("image too large")
+    if out is None:
+        out = torch.empty_like(srcs)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8
+              and out.is_contiguous() and out.shape == srcs.shape):
+        raise ValueError("out must be a contiguous CUDA uint8 tensor shaped like the packed srcs")
+    n = sizes.shape[0]
+    if n == 0:
+        return out, []
+    hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
+    wds = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
+    need = lib.rf_jbf_ragged_workspace_bytes(n, hs.ctypes.data, wds.ctypes.data, joints.shape[1],
+                                             srcs.shape[1], int(d), float(sigma_space), int(flags))
+    ws = _jbf_ragged_workspace(need, srcs.device, torch)   # need == 0: the entry says why
+    rc = lib.rf_jbf_ragged_u8(joints.data_ptr(), srcs.data_ptr(), out.data_ptr(), n,
+                              hs.ctypes.data, wds.ctypes.data, joints.shape[1], srcs.shape[1],
+                              int(d), float(sigma_color), float(sigma_space), int(border),
+                              int(flags), ws.data_ptr(), ws.numel(), _ffi.current_stream_ptr(torch))
+    _ffi.check(rc, "rf_jbf_ragged_u8")
+    return out, split_packed(out, sizes)
+
+
+def joint_bilateral_points_ragged_u8(joints, srcs, points, point_offsets, sigma_pairs, d=-1,
+                                     border=_ffi.BORDER_DEFAULT, flags=0, grey_as_bgr=False,
+                                     sizes=None):
+    """joint_bilateral_points_u8 over images of different sizes, in one launch
+    (rf_jbf_points_ragged_u8).  joints / srcs: lists of n CUDA uint8 tensors [H_i, W_i, C] (equal
+    C within a list; image i of both has the same H_i, W_i), or, with sizes = [n,2] (h, w), the
+    images already packed one after another as contiguous CUDA uint8 tensors [total pixels, C].
+    Returns CUDA uint8 [P, total, src_cn] with
+    out[p, k] = joint_bilateral_u8(joints[i][None], srcs[i][None], d, *sigma_pairs[p], ...)[0, y_k, x_k],
+    byte for byte, where point k = (x_k, y_k) = points[k] belongs to image i.  points /
+    point_offsets are host arrays, checked there against each image's own size.  Synchronises
+    the current stream."""
+    if grey_as_bgr:
+        flags |= _ffi.JBF_GREY_AS_BGR
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    joints, srcs, sizes = _packed_pair(joints, srcs, sizes, torch)
     n = sizes.shape[0]
     scn = srcs.shape[1]
     pts, off = check_points_ragged(_to_host(points, torch), _to_host(point_offsets, torch), sizes)
