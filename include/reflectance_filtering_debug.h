@@ -71,7 +71,8 @@
  * Besides the switches, rf_debug_jbf_points_plan reports the launch plan of rf_jbf_points_u8 (how
  * its parameter sets are cut into chunks and how many points a wave of each chunk takes) without
  * touching a device, so that tests can assert which lane mapping a call runs at, and
- * rf_debug_jbf_ragged_plan the tile classes rf_jbf_ragged_u8 launches.
+ * rf_debug_jbf_ragged_plan the tile classes rf_jbf_ragged_u8 launches, rf_debug_jbf_ragged_slab_plan
+ * its one launch of tap-row slabs at radius 53..468.
  */
 #ifndef REFLECTANCE_FILTERING_DEBUG_H
 #define REFLECTANCE_FILTERING_DEBUG_H
@@ -118,6 +119,20 @@ int rf_debug_jbf_points_plan(int n_params, const double *sigma_space, int d, int
 int rf_debug_jbf_ragged_plan(int n, const int *heights, const int *widths, int joint_cn, int src_cn,
                              int d, double sigma_color, double sigma_space, int flags, int *out,
                              int cap);
+
+/* The slab launch of rf_jbf_ragged_u8 (radius 53..468, where no tile class of the query above holds
+ * the radius: every image's 64x64 tiles in one launch of the slab kernel) for the same arguments:
+ * the seven ints {row pitch, LUT replicas, rows per band and rows per slab with 4-byte texels, the
+ * same two with 6-byte texels (0, 0: a colour tile takes one grey pass per channel; always 0, 0 for
+ * a single-channel src), 64x64 tiles of all images} at out[0..6] when cap >= 1.  Decided by the
+ * functions the entry and rf_jbf_u8 launch from (the debug switches included; the LDS probe of the
+ * device is not consulted).  Returns 1 where the entry runs that launch (out may be NULL when cap
+ * is 0), -1 where it does not (the tile classes above, or rf_jbf_u8 once per image), and what
+ * rf_debug_jbf_ragged_plan returns for arguments the entry refuses or a bad cap - told apart from
+ * the -1 above in the same way.  Host only: needs no device. */
+int rf_debug_jbf_ragged_slab_plan(int n, const int *heights, const int *widths, int joint_cn,
+                                  int src_cn, int d, double sigma_color, double sigma_space, int flags,
+                                  int *out, int cap);
 
 #ifdef __cplusplus
 }

@@ -35,7 +35,8 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
-                 "rf_debug_jbf_points_plan", "rf_debug_jbf_ragged_plan")
+                 "rf_debug_jbf_points_plan", "rf_debug_jbf_ragged_plan",
+                 "rf_debug_jbf_ragged_slab_plan")
 # switches that leave work out (wrong results, timing experiments only); all others keep the bytes
 RESULT_CHANGING_OPTIONS = ("jbf_stage_only", "gf_exp_skip")
 
@@ -126,6 +127,8 @@ def load_library():
         lib.rf_debug_jbf_points_plan.restype = ci
         lib.rf_debug_jbf_ragged_plan.argtypes = [ci, vp, vp, ci, ci, ci, cd, cd, ci, vp, ci]
         lib.rf_debug_jbf_ragged_plan.restype = ci
+        lib.rf_debug_jbf_ragged_slab_plan.argtypes = [ci, vp, vp, ci, ci, ci, cd, cd, ci, vp, ci]
+        lib.rf_debug_jbf_ragged_slab_plan.restype = ci
         # RF_DEBUG_OPTIONS="name=value,...": preset the test / benchmark switches of
         # include/reflectance_filtering_debug.h for a whole process (timing experiments only).
         # Every preset is announced on stderr - loudly for the switches that change results.
@@ -225,6 +228,30 @@ def jbf_ragged_plan(sizes, joint_cn, src_cn, d, sigma_color, sigma_space, flags=
     if rc < 0:
         check(rc, "rf_debug_jbf_ragged_plan")
     return [tuple(int(v) for v in row) for row in out[:rc]]
+
+
+def jbf_ragged_slab_plan(sizes, joint_cn, src_cn, d, sigma_color, sigma_space, flags=0):
+    """The slab launch of rf_jbf_ragged_u8 (radius 53..468) for images of these sizes ([n,2] (h, w))
+    (rf_debug_jbf_ragged_slab_plan, host only): the tuple (pitch, LUT replicas, crows_g, slab_g,
+    crows_c, slab_c, tiles), or None where the entry does not run that launch (the tile classes of
+    jbf_ragged_plan, or one rf_jbf_u8 call per image)."""
+    import numpy as np
+    lib = load_library()
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
+    ws = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
+    out = np.zeros(7, dtype=np.int32)
+    args = (sizes.shape[0], hs.ctypes.data, ws.ctypes.data, int(joint_cn), int(src_cn), int(d),
+            float(sigma_color), float(sigma_space), int(flags), out.ctypes.data, 1)
+    rc = lib.rf_debug_jbf_ragged_slab_plan(*args)
+    if rc == -1:
+        # -1 is "not this launch" and RF_E_BADARG alike: a workspace size of 0 (for n > 0) says refused
+        if sizes.shape[0] == 0 or lib.rf_jbf_ragged_workspace_bytes(*(args[:6] + (args[7], args[8]))) > 0:
+            return None
+        lib.rf_debug_jbf_ragged_slab_plan(*args)                         # (its message again)
+    if rc < 0:
+        check(rc, "rf_debug_jbf_ragged_slab_plan")
+    return tuple(int(v) for v in out)
 
 
 def require_gpu():

@@ -17,6 +17,8 @@
 //   jbf_slab_kernel    radius 53..468: the same 64x64 outputs with the disk's tap rows taken in slabs
 //                      (row pitch 208 .. 1008; the grey loop; a colour src in one pass of the colour
 //                      loop, or one pass per channel of the grey loop where that leaves no slab).
+//                      Its kRagged instantiation serves rf_jbf_ragged_u8 at these radii: every image's
+//                      64x64 tiles in one launch, from the same 32-byte records.
 //   jbf_tiled2_kernel  64 x TH tiles with 8-byte texels and a clamped/full LUT: used when the
 //                      LDS out-of-range probe fails, and by the tuning harness.
 //   jbf_generic_kernel untiled, any radius, global-memory gathers (fallback + cross-check).
@@ -379,7 +381,7 @@ struct alignas(16) JbfTileRec {
 };
 static_assert(sizeof(JbfTileRec) == 32, "the workspace holds 32 bytes per tile");
 
-// The tiles argument of jbf_tile64_kernel: tiles per image row (uniform launch: every image is
+// The tiles argument of jbf_tile64_kernel and jbf_slab_kernel: tiles per image row (uniform launch: every image is
 // h x w), or the tile records (ragged launch; h, w, tiles_per_img, y_base, x_base are unused).
 template <bool kRagged>
 struct JbfTilesArg {
@@ -904,6 +906,14 @@ bool tile64_choose(const JbfTables &t, int nz, int src_cn, int flags, Tile64Shap
     return false;
 }
 
+// What a launch of jbf_slab_kernel (radius 53..468, below) runs at: row pitch, LUT replicas, rows
+// per band and per slab with 4-byte texels (crows_g, slab_g) and with 6-byte texels (crows_c,
+// slab_c; crows_c = 0: one grey pass per channel).
+struct SlabShape {
+    int tlw, grep, crows_g, slab_g, crows_c, slab_c;
+};
+bool slab_choose(const JbfTables &t, int nz, int src_cn, SlabShape *out);
+
 // ---- ragged form (rf_jbf_ragged_u8) ------------------------------------------------------------
 // The tile classes of a ragged call in launch order: {tile rows, row pitch}; tile columns = 4096 / rows.
 constexpr int kRaggedClasses = 4;
@@ -912,9 +922,12 @@ constexpr int kRaggedPitch144[kRaggedClasses] = {144, 208, 336, 136};
 
 // What a ragged call launches: the shape (once per call) and, per tile class, the records of all
 // images' tiles in image order.  tile64_areas decides per image, as for a uniform launch.
+// Radius 53..468 (slab): one launch of jbf_slab_kernel over recs[0], every image's 64x64 tiles.
 struct RaggedPlan {
-    bool tiled = false;  // false: the entry falls back to one uniform call per image
+    bool tiled = false;  // neither tiled nor slab: the entry falls back to one uniform call per image
+    bool slab = false;
     Tile64Shape shape{};
+    SlabShape slab_shape{};
     std::vector<JbfTileRec> recs[kRaggedClasses];
 };
 
@@ -922,16 +935,19 @@ void plan_ragged(const JbfTables &t, int n, const int *heights, const int *width
                  int flags, int tune, RaggedPlan *plan)
 {
     const int nz = t.lut_len < 256 * t.joint_cn ? t.lut_len - 1 : t.lut_len;
-    plan->tiled = !(flags & RF_JBF_FORCE_GENERIC) && tune == 0 &&
-                  tile64_choose(t, nz, src_cn, flags, &plan->shape);
-    if (!plan->tiled)
+    if ((flags & RF_JBF_FORCE_GENERIC) || tune != 0)
+        return;
+    plan->tiled = tile64_choose(t, nz, src_cn, flags, &plan->shape);
+    // no 64-row-tile shape holds the radius: tap-row slabs, as the uniform entry chooses them
+    plan->slab = !plan->tiled && slab_choose(t, nz, src_cn, &plan->slab_shape);
+    if (!plan->tiled && !plan->slab)
         return;
     const Tile64Shape &s = plan->shape;
     unsigned long long first = 0;
     for (int i = 0; i < n; i++) {
         const int h = heights[i], w = widths[i];
-        Tile64Areas a{h, w, 0, 0, 0};  // the wide pitch has 64x64 tiles alone
-        if (s.tlw == 144)
+        Tile64Areas a{h, w, 0, 0, 0};  // the wide pitch and the slabs have 64x64 tiles alone
+        if (plan->tiled && s.tlw == 144)
             a = tile64_areas(t, nz, s.grep, s.crep, src_cn, flags, h, w);
         // {y_base, rows, x_base, cols} of each class's area, as launch_tile64_rows hands them on
         const int area[kRaggedClasses][4] = {{0, a.rows_main, 0, a.cols_main},
@@ -1015,12 +1031,15 @@ int launch_ragged(const JbfTables &t, int nz, const RaggedPlan &plan, const uint
 // whole halo staged, i.e. a half to an eighth of the lanes busy) is gone: slabs run 7.3 G taps/s at
 // every radius (0.95 of the radius-33 rate) where the bands ran 6.7 at radius 54, 3.7 at radius 70.
 // ------------------------------------------------------------------------------------------
-template <int GREP, int TLW>
+// kRagged (rf_jbf_ragged_u8): the workgroup's image, size and tile origin come from its 32-byte
+// record, as in jbf_tile64_kernel; bands, slabs and pitch depend on the tables only and stay per launch.
+template <int GREP, int TLW, bool kRagged = false>
 __global__ __launch_bounds__(1024) void jbf_slab_kernel(
     const uint8_t *__restrict__ joint, const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
     int h, int w, int jcn, int scn, int radius, int border, const float *__restrict__ lut, int nz,
-    const int *__restrict__ hwtab, const float *__restrict__ swsym, int sw_len, int tiles_x,
-    int tiles_per_img, int flags, int crows_g, int slab_g, int crows_c, int slab_c)
+    const int *__restrict__ hwtab, const float *__restrict__ swsym, int sw_len,
+    typename JbfTilesArg<kRagged>::type tiles_x, int tiles_per_img, int flags, int crows_g, int slab_g,
+    int crows_c, int slab_c)
 {
     // crows_g / slab_g: rows per band and per slab with 4-byte texels (grey src, or a 3-channel src
     // whose tile turns out grey); crows_c / slab_c with 6-byte texels (colour src, one pass: main
@@ -1035,11 +1054,24 @@ __global__ __launch_bounds__(1024) void jbf_slab_kernel(
     if (tid == 0)
         *flag_word = 3;
     const int tile_id = xcd_contiguous_tile((int)blockIdx.x, (int)gridDim.x);
-    const int img_idx = tile_id / tiles_per_img;
-    const int t_in_img = tile_id - img_idx * tiles_per_img;
-    const int tile_y0 = (t_in_img / tiles_x) * 64;
-    const int tile_x0 = (t_in_img % tiles_x) * 64;
-    const size_t img = (size_t)img_idx * h * w;
+    int tile_y0, tile_x0;
+    size_t img;
+    if constexpr (kRagged) {
+        // one record per workgroup: the same words in every lane (scalar loads, scalar registers) -
+        // h and the tile's origin bound the band and slab loops, whose bounds are scalar-load addresses
+        const JbfTileRec *rec = tiles_x + tile_id;
+        img = (size_t)rec->first;
+        h = rec->h;
+        w = rec->w;
+        tile_y0 = rec->tile_y0;
+        tile_x0 = rec->tile_x0;
+    } else {
+        const int img_idx = tile_id / tiles_per_img;
+        const int t_in_img = tile_id - img_idx * tiles_per_img;
+        tile_y0 = (t_in_img / tiles_x) * 64;
+        tile_x0 = (t_in_img % tiles_x) * 64;
+        img = (size_t)img_idx * h * w;
+    }
     const int r4 = (radius + 3) & ~3;
     const int tx = tid % QW, ty = tid / QW;
     float *lut_g = reinterpret_cast<float *>(smem + kT64Lds - nz * GREP * 4);
@@ -1155,6 +1187,33 @@ void slab_fits(const JbfTables &t, int nz, int grep, int tlw, int texel_bytes, i
     X(68, 208) X(84, 240) X(100, 272) X(116, 304) X(132, 336) X(164, 400) X(212, 496) X(276, 624) \
     X(372, 816) X(kJbfMaxTiledR4, 1008)
 
+// The shape a call of radius 53..468 runs at; it depends on the tables, not on the image sizes.
+// The narrowest pitch that holds r4; 16 LUT replicas unless 8 leave a taller band; a colour src
+// takes the 6-byte rows that fit beside the same replicas.  False: outside the radii, or nothing fits.
+bool slab_choose(const JbfTables &t, int nz, int src_cn, SlabShape *out)
+{
+    if (t.r4 <= 52 || t.r4 > kJbfMaxTiledR4)
+        return false;
+    SlabShape s{};
+#define RF_PITCH(R4_, TLW_) \
+    if (!s.tlw && t.r4 <= R4_) \
+        s.tlw = TLW_;
+    RF_SLAB_PITCHES(RF_PITCH)
+#undef RF_PITCH
+    for (int g : {16, 8}) {
+        int cr, sl;
+        slab_fits(t, nz, g, s.tlw, 4, &cr, &sl);
+        if (cr > s.crows_g)
+            s.crows_g = cr, s.slab_g = sl, s.grep = g;
+    }
+    if (s.crows_g == 0)
+        return false;
+    if (src_cn == 3)  // a colour tile in one pass: 6-byte texels, same replicas
+        slab_fits(t, nz, s.grep, s.tlw, 6, &s.crows_c, &s.slab_c);
+    *out = s;
+    return true;
+}
+
 template <int GREP, int TLW>
 int launch_slab(const JbfTables &t, int nz, int crows, int slab_rows, int crows_c, int slab_c,
                 const uint8_t *joint, const uint8_t *src, uint8_t *dst, int n, int h, int w, int jcn,
@@ -1170,6 +1229,25 @@ int launch_slab(const JbfTables &t, int nz, int crows, int slab_rows, int crows_
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(1024), kT64Lds, stream, joint, src, dst, h,
                        w, jcn, scn, t.radius, border, t.d_lut, nz, t.d_hw, t.d_swsym, t.sw_len,
                        tiles_x, tiles_x * tiles_y, flags, crows, slab_rows, crows_c, slab_c);
+    return RF_OK;
+}
+
+// A ragged call at these radii: every image's 64x64 tiles in one launch.
+template <int GREP, int TLW>
+int launch_slab_ragged(const JbfTables &t, int nz, const SlabShape &s, const uint8_t *joint,
+                       const uint8_t *src, uint8_t *dst, const JbfTileRec *d_recs, size_t ntiles,
+                       int jcn, int scn, int border, int flags, hipStream_t stream)
+{
+    if (ntiles == 0)
+        return RF_OK;
+    if (ntiles > (size_t)0x7fffffff)
+        return fail(RF_E_UNSUPPORTED, "rf_jbf_ragged_u8: too many tiles for one launch");
+    auto kern = jbf_slab_kernel<GREP, TLW, true>;
+    RF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kT64Lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(1024), kT64Lds, stream, joint, src, dst, 0,
+                       0, jcn, scn, t.radius, border, t.d_lut, nz, t.d_hw, t.d_swsym, t.sw_len,
+                       d_recs, 0, flags, s.crows_g, s.slab_g, s.crows_c, s.slab_c);
     return RF_OK;
 }
 
@@ -1258,36 +1336,22 @@ extern "C" int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst,
                 done = true;
             }
             // radius 53..468: tap-row slabs (jbf_slab_kernel) at the narrowest pitch that holds r4
-            if (!done && t.r4 > 52 && t.r4 <= kJbfMaxTiledR4) {
-                int tlw = 0;
-#define RF_PITCH(R4_, TLW_) \
-    if (!tlw && t.r4 <= R4_) \
-        tlw = TLW_;
-                RF_SLAB_PITCHES(RF_PITCH)
-#undef RF_PITCH
-                int crows = 0, slab = 0, rep = 0, crows_c = 0, slab_c = 0;
-                for (int g : {16, 8}) {
-                    int cr, sl;
-                    slab_fits(t, nz, g, tlw, 4, &cr, &sl);
-                    if (cr > crows)
-                        crows = cr, slab = sl, rep = g;
-                }
-                if (crows > 0 && src_cn == 3)  // a colour tile in one pass: 6-byte texels, same replicas
-                    slab_fits(t, nz, rep, tlw, 6, &crows_c, &slab_c);
-                if (crows > 0) {
+            SlabShape slab;
+            if (!done && slab_choose(t, nz, src_cn, &slab)) {
 #define RF_SLAB(R4_, TLW_)                                                                        \
-    if (tlw == TLW_)                                                                              \
-        rc = rep == 16 ? launch_slab<16, TLW_>(t, nz, crows, slab, crows_c, slab_c, joint, src, dst, \
-                                               n, h, w, jcn_kernel, src_cn, border, flags, stream) \
-                       : launch_slab<8, TLW_>(t, nz, crows, slab, crows_c, slab_c, joint, src, dst, \
-                                              n, h, w, jcn_kernel, src_cn, border, flags, stream);
-                    RF_SLAB_PITCHES(RF_SLAB)
+    if (slab.tlw == TLW_)                                                                         \
+        rc = slab.grep == 16                                                                      \
+                 ? launch_slab<16, TLW_>(t, nz, slab.crows_g, slab.slab_g, slab.crows_c,          \
+                                         slab.slab_c, joint, src, dst, n, h, w, jcn_kernel,       \
+                                         src_cn, border, flags, stream)                           \
+                 : launch_slab<8, TLW_>(t, nz, slab.crows_g, slab.slab_g, slab.crows_c,           \
+                                        slab.slab_c, joint, src, dst, n, h, w, jcn_kernel, src_cn, \
+                                        border, flags, stream);
+                RF_SLAB_PITCHES(RF_SLAB)
 #undef RF_SLAB
-#undef RF_SLAB_PITCHES
-                    if (rc != RF_OK)
-                        return rc;
-                    done = true;
-                }
+                if (rc != RF_OK)
+                    return rc;
+                done = true;
             }
         }
     }
@@ -1334,7 +1398,8 @@ extern "C" int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst,
 
 // ------------------------------------------------------------------------------------------
 // Ragged form: images of different sizes packed one after another, one launch per tile class
-// over all images (radius <= 52), else rf_jbf_u8 once per image.
+// over all images (radius <= 52), one launch of the slab kernel over all images' 64x64 tiles
+// (radius 53..468), else rf_jbf_u8 once per image.
 // ------------------------------------------------------------------------------------------
 namespace rf {
 namespace {
@@ -1422,6 +1487,36 @@ extern "C" int rf_debug_jbf_ragged_plan(int n, const int *heights, const int *wi
     return launches;
 }
 
+extern "C" int rf_debug_jbf_ragged_slab_plan(int n, const int *heights, const int *widths,
+                                             int joint_cn, int src_cn, int d, double sigma_color,
+                                             double sigma_space, int flags, int *out, int cap)
+{
+    using namespace rf;
+    const char *who = "rf_debug_jbf_ragged_slab_plan";
+    size_t px, tiles;
+    if (cap < 0 || (cap > 0 && !out))
+        return fail(RF_E_BADARG, "%s: bad cap=%d", who, cap);
+    if (int bad = ragged_check(who, n, heights, widths, joint_cn, src_cn, d, sigma_space,
+                               RF_BORDER_DEFAULT, flags, &px, &tiles))
+        return bad;
+    std::vector<float> lut;
+    const JbfTables t = jbf_host_tables(jbf_radius(d, jbf_sigma(sigma_space)),
+                                        jbf_table_cn(joint_cn, flags), jbf_sigma(sigma_color),
+                                        jbf_sigma(sigma_space), lut);
+    RaggedPlan plan;
+    plan_ragged(t, n, heights, widths, src_cn, flags | jbf_debug_flags(),
+                debug_get(kDbgJbfTune) & 0xf, &plan);
+    if (!plan.slab)
+        return -1;
+    if (cap > 0) {
+        const SlabShape &s = plan.slab_shape;
+        const int record[7] = {s.tlw, s.grep, s.crows_g, s.slab_g, s.crows_c, s.slab_c,
+                               (int)std::min<size_t>(plan.recs[0].size(), 0x7fffffff)};
+        std::copy(record, record + 7, out);
+    }
+    return 1;
+}
+
 extern "C" int rf_jbf_ragged_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst, int n,
                                 const int *heights, const int *widths, int joint_cn, int src_cn,
                                 int d, double sigma_color, double sigma_space, int border, int flags,
@@ -1457,8 +1552,8 @@ extern "C" int rf_jbf_ragged_u8(const uint8_t *joint, const uint8_t *src, uint8_
     RaggedPlan plan;
     JbfTables t;
     TablesHold hold{t};
-    // (no tile shape holds r4 > 52: such a call needs no tables here, rf_jbf_u8 fetches its own)
-    if (!(flags & RF_JBF_FORCE_GENERIC) && tune == 0 && ((radius + 3) & ~3) <= 52) {
+    // (nothing tiled holds r4 > 468: such a call needs no tables here, rf_jbf_u8 fetches its own)
+    if (!(flags & RF_JBF_FORCE_GENERIC) && tune == 0 && ((radius + 3) & ~3) <= kJbfMaxTiledR4) {
         int rc = get_tables(radius, table_cn, sc, ss, stream, &t);
         if (rc != RF_OK)
             return rc;
@@ -1469,8 +1564,8 @@ extern "C" int rf_jbf_ragged_u8(const uint8_t *joint, const uint8_t *src, uint8_
         if (oob_ok)
             plan_ragged(t, n, heights, widths, src_cn, flags, tune, &plan);
     }
-    if (!plan.tiled) {
-        // every other route (slab kernel, generic kernel, failed LDS probe, a tuning override):
+    if (!plan.tiled && !plan.slab) {
+        // every other route (generic kernel, failed LDS probe, a tuning override):
         // the uniform entry once per image - the same bytes with n launches
         size_t first = 0;
         for (int i = 0; i < n; i++) {
@@ -1499,6 +1594,24 @@ extern "C" int rf_jbf_ragged_u8(const uint8_t *joint, const uint8_t *src, uint8_
     RF_HIP_CHECK(hipStreamSynchronize(stream));
     const int nz = t.lut_len < 256 * table_cn ? t.lut_len - 1 : t.lut_len;
     int rc = RF_OK;
+    if (plan.slab) {
+        const SlabShape &shp = plan.slab_shape;
+#define RF_SLAB(R4_, TLW_)                                                                        \
+    if (shp.tlw == TLW_)                                                                          \
+        rc = shp.grep == 16                                                                       \
+                 ? launch_slab_ragged<16, TLW_>(t, nz, shp, joint, src, dst, d_recs[0],           \
+                                                plan.recs[0].size(), jcn_kernel, src_cn, border,  \
+                                                flags, stream)                                    \
+                 : launch_slab_ragged<8, TLW_>(t, nz, shp, joint, src, dst, d_recs[0],            \
+                                               plan.recs[0].size(), jcn_kernel, src_cn, border,   \
+                                               flags, stream);
+        RF_SLAB_PITCHES(RF_SLAB)
+#undef RF_SLAB
+        if (rc != RF_OK)
+            return rc;
+        RF_HIP_CHECK(hipGetLastError());
+        return RF_OK;
+    }
 #define RF_T64(G_, C_, W_)                                                                        \
     if (plan.shape.grep == G_ && plan.shape.crep == C_ && plan.shape.tlw == W_)                   \
         rc = src_cn == 3 ? launch_ragged<3, G_, C_, W_>(t, nz, plan, joint, src, dst, d_recs,      \
@@ -1512,3 +1625,4 @@ extern "C" int rf_jbf_ragged_u8(const uint8_t *joint, const uint8_t *src, uint8_
     RF_HIP_CHECK(hipGetLastError());
     return RF_OK;
 }
+#undef RF_SLAB_PITCHES

@@ -217,8 +217,8 @@ def _jbf_ragged_workspace(need, device, torch):
 def joint_bilateral_ragged_u8(joints, srcs, d, sigma_color, sigma_space, border=_ffi.BORDER_DEFAULT,
                               flags=0, grey_as_bgr=False, sizes=None, out=None):
     """joint_bilateral_u8 over images of different sizes in one call (rf_jbf_ragged_u8: radius <= 52
-    runs the tiles of all images in one launch per tile shape; a larger radius takes one launch
-    per image).  joints / srcs: lists of n CUDA uint8 tensors [H_i, W_i, C] (equal C within a
+    runs the tiles of all images in one launch per tile shape, radius 53..468 in one launch of
+    tap-row slabs; a larger radius takes one launch per image).  joints / srcs: lists of n CUDA uint8 tensors [H_i, W_i, C] (equal C within a
     list; image i of both has the same H_i, W_i), or, with sizes = [n,2] (h, w), the images
     already packed one after another as contiguous CUDA uint8 tensors [total pixels, C].
     out: the packed result buffer [total pixels, src C], if the caller has one.

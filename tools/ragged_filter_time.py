@@ -4,7 +4,8 @@
 64 synthetic grey CNN-like maps of the three common IIW shapes (341x512, 512x341, 384x512) in a
 seeded order whose equal-shape runs are 1 to 4 images long (a sorted IIW listing: no long run of
 one shape), device-resident, BF(CNN, CNN) with grey_as_bgr at the paper's two bilateral recipes,
-c20 s22 (radius 33) and c15 s28 (radius 42).  Two paths, in steps of 16 images (batch.py's step)
+c20 s22 (radius 33) and c15 s28 (radius 42), and at two wider sigma_spatial of the slab kernel,
+c20 s36 (radius 54) and c20 s66 (radius 99).  Two paths, in steps of 16 images (batch.py's step)
 and over the whole list at once:
     runs    one ops.joint_bilateral_u8 call per run of equal shapes (batch.group_by_shape), the way
             batch.filter_files takes a step whose images differ in shape without the ragged entry
@@ -18,7 +19,7 @@ calls and kernel launches per pass (from the launch plan).
 Each parameter set runs in a child process under its own time limit; a child that fails ends the
 run.  Prints one JSON line per parameter set.
 
-    python tools/ragged_filter_time.py [--reps 9] [--passes 3] [--limit 300]
+    python tools/ragged_filter_time.py [--reps 9] [--passes 3] [--limit 300] [--cases c20s36,c20s66]
 """
 import argparse
 import json
@@ -31,7 +32,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CASES = {"c20s22": (20.0, 22.0), "c15s28": (15.0, 28.0)}
+CASES = {"c20s22": (20.0, 22.0), "c15s28": (15.0, 28.0), "c20s36": (20.0, 36.0), "c20s66": (20.0, 66.0)}
 SHAPES = ((341, 512), (512, 341), (384, 512))
 STEP = 16
 
@@ -65,7 +66,11 @@ def case(name, reps, passes):
 
     def launches_of(sizes):
         plan = _ffi.jbf_ragged_plan(sizes, 1, 1, -1, sc, ss, _ffi.JBF_GREY_AS_BGR)
-        return len(sizes) if plan is None else len(plan)
+        if plan is not None:
+            return len(plan)
+        # no tile class: one slab launch over all images, or one launch per image
+        slab = _ffi.jbf_ragged_slab_plan(sizes, 1, 1, -1, sc, ss, _ffi.JBF_GREY_AS_BGR)
+        return len(sizes) if slab is None else 1
 
     for step_name, step in (("step16", STEP), ("one_call", len(shapes))):
         steps = [list(range(i, min(i + step, len(shapes)))) for i in range(0, len(shapes), step)]
@@ -116,10 +121,14 @@ def main():
     ap.add_argument("--passes", type=int, default=3, help="passes over the list per timed span")
     ap.add_argument("--limit", type=int, default=300, help="seconds a parameter set may take")
     ap.add_argument("--case", choices=sorted(CASES), help="run one parameter set in this process")
+    ap.add_argument("--cases", default=",".join(CASES), help="comma-separated parameter sets to run")
     args = ap.parse_args()
     if args.case:
         return case(args.case, args.reps, args.passes)
-    for name in CASES:     # each GPU step in a fresh process under its own limit; a failure ends the run
+    names = [c for c in args.cases.split(",") if c]
+    if any(c not in CASES for c in names):
+        ap.error("--cases: choose from %s" % ", ".join(CASES))
+    for name in names:     # each GPU step in a fresh process under its own limit; a failure ends the run
         rc = subprocess.call(["timeout", "-k", "10", str(args.limit), sys.executable,
                               os.path.abspath(__file__), "--case", name, "--reps", str(args.reps),
                               "--passes", str(args.passes)])
