@@ -63,6 +63,15 @@
  *   "gf_cw_chan_run"     guided filter, colour src, passes of an iterated call that hand their result on as
  *                        planes: n + 1 = the column walk takes an XCD's (block, channel) items in runs of n
  *                        blocks per channel (0 = the library's choice, 64; 1 = channel fastest); identical bytes
+ *   "jbf_no_msad"        joint bilateral, 3-channel joint: every wave runs the asm tap loop that masks the
+ *                        src byte out of the tap texel (v_and_b32 + v_sad_u8).  By default a wave none of
+ *                        whose centre pixels has a zero joint channel runs the masked-SAD form (v_msad_u8 on
+ *                        the unmasked texel, one VALU instruction per step less) and only the other waves
+ *                        this one; identical bytes.  There is no switch the other way round: the
+ *                        masked-SAD form is wrong for a centre with a zero channel.  The masked-SAD form
+ *                        exists for the default grey loop (gathers two steps ahead) and the colour loop, in
+ *                        the tile and the slab kernel; under "jbf_lookahead1" (the round-4 grey loop) and
+ *                        "jbf_compiler_loop" every wave keeps the mask, whatever this option says.
  *
  * The grey-guide form of the guided filter (rf_gf_ex_u8 with RF_GF_GREY_AS_BGR) has no stage 1 for
  * "gf_guide_cache" and "gf_exact": while either is set, such a call returns RF_E_UNSUPPORTED.  Every

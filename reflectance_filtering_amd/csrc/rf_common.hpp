@@ -96,6 +96,7 @@ enum DebugOption {
     kDbgGfExactAllFlagged, // guided filter, exact-row form: treat every row as failing the test (exercises the list path)
     kDbgGfCwChanRun,       // guided filter, colour src, planar passes: n + 1 = runs of n pairs per channel in the column walk's item order (0: the library's 64; 1: channel fastest)
     kDbgGfExact,           // guided filter: exact-row stage 2 (off by default: measured slower, profiles/r06_gf_exact.md)
+    kDbgJbfNoMsad,         // joint bilateral: every wave takes the tap loop with the mask (none the masked-SAD form)
     kDbgCount
 };
 int debug_get(int id);

@@ -51,6 +51,7 @@ constexpr int kJbfMaxTiledR4 = 468;  // radius (rounded up to 4) the slab kernel
 // rf_debug_option() as the kernels see them
 constexpr int kJbfStageOnly = 0x1000, kJbfCompilerLoop = 0x2000, kJbfTile64Only = 0x4000;
 constexpr int kJbfLookahead1 = 0x8000;  // grey asm loop with its gathers one column step ahead (round-4 form)
+constexpr int kJbfNoMsad = 0x10000;     // every wave takes the tap loop with the mask (none the masked-SAD form)
 
 // the test / benchmark switches (rf_debug_option) as they travel to the kernels: private flag bits
 int jbf_debug_flags()
@@ -58,7 +59,8 @@ int jbf_debug_flags()
     return (debug_get(kDbgJbfStageOnly) ? kJbfStageOnly : 0) |
            (debug_get(kDbgJbfCompilerLoop) ? kJbfCompilerLoop : 0) |
            (debug_get(kDbgJbfTile64Only) ? kJbfTile64Only : 0) |
-           (debug_get(kDbgJbfLookahead1) ? kJbfLookahead1 : 0);
+           (debug_get(kDbgJbfLookahead1) ? kJbfLookahead1 : 0) |
+           (debug_get(kDbgJbfNoMsad) ? kJbfNoMsad : 0);
 }
 
 // Four consecutive pixels (cn interleaved bytes each, any alignment) -> four packed dwords.
@@ -526,6 +528,9 @@ __global__ __launch_bounds__(1024) void jbf_tile64_kernel(
         } else if (j1 || j1_late)
             jbf_tap_loop_grey4_la2<GREP, TLW, true>(lut_lane_addr, swsym, tile_lane_addr, jc, ty,
                                                     radius, r4, sw_len, hwtab, sum1, wsum);
+        else if (!(flags & kJbfNoMsad) && jbf_wave_takes_msad(jc))  // (per wave: no centre with a zero channel)
+            jbf_tap_loop_grey4_la2<GREP, TLW, false, false, true>(lut_lane_addr, swsym, tile_lane_addr, jc,
+                                                                  ty, radius, r4, sw_len, hwtab, sum1, wsum);
         else
             jbf_tap_loop_grey4_la2<GREP, TLW>(lut_lane_addr, swsym, tile_lane_addr, jc, ty, radius,
                                               r4, sw_len, hwtab, sum1, wsum);
@@ -571,6 +576,11 @@ __global__ __launch_bounds__(1024) void jbf_tile64_kernel(
                                                      lds_addr(tile4) + (uint32_t)tx * 4u,
                                                      lds_addr(plane_b) + (uint32_t)tx * 2u, jc, 0u,
                                                      ty, radius, r4, sw_len, hwtab, sum, wsum);
+            else if (!(flags & kJbfNoMsad) && jbf_wave_takes_msad(jc))
+                jbf_tap_loop_rgb6<CREP, TLW, false, true>(lut_lane_addr, swsym,
+                                                          lds_addr(tile4) + (uint32_t)tx * 4u,
+                                                          lds_addr(plane_b) + (uint32_t)tx * 2u, jc, ty,
+                                                          radius, r4, sw_len, hwtab, sum, wsum);
             else
                 jbf_tap_loop_rgb6<CREP, TLW>(lut_lane_addr, swsym,
                                              lds_addr(tile4) + (uint32_t)tx * 4u,
@@ -630,6 +640,11 @@ __global__ __launch_bounds__(1024) void jbf_tile64_kernel(
                                                          lds_addr(tile4) + (uint32_t)tx * 4u,
                                                          lds_addr(plane_b) + (uint32_t)tx * 2u, jc, 0u,
                                                          ty, radius, r4, sw_len, hwtab, sum, wsum);
+                else if (!(flags & kJbfNoMsad) && jbf_wave_takes_msad(jc))
+                    jbf_tap_loop_rgb6<CREP, TLW, false, true>(lut_lane_addr, swsym,
+                                                              lds_addr(tile4) + (uint32_t)tx * 4u,
+                                                              lds_addr(plane_b) + (uint32_t)tx * 2u, jc,
+                                                              ty, radius, r4, sw_len, hwtab, sum, wsum);
                 else
                     jbf_tap_loop_rgb6<CREP, TLW>(lut_lane_addr, swsym,
                                                  lds_addr(tile4) + (uint32_t)tx * 4u,
@@ -1117,6 +1132,8 @@ __global__ __launch_bounds__(1024) void jbf_slab_kernel(
                     wsum[p] = 0.f;
                 }
             }
+            // per wave, for all its slabs: the masked-SAD form of the loops unless a centre has a zero channel
+            const bool msad = !(flags & kJbfNoMsad) && jbf_wave_takes_msad(jc, active);
             for (int i0 = -radius; i0 <= radius; i0 += slab_rows) {
                 const int i1 = min(i0 + slab_rows - 1, radius);
                 const int tlh = crows + (i1 - i0);
@@ -1136,10 +1153,20 @@ __global__ __launch_bounds__(1024) void jbf_slab_kernel(
                 }
                 __syncthreads();
                 if (active) {
-                    if (rgb6)
+                    if (rgb6 && msad)
+                        jbf_tap_loop_rgb6<GREP, TLW, true, true>(lut_lane_addr, swsym, tile_lane_addr,
+                                                                 lds_addr(plane_b) + (uint32_t)tx * 2u, jc, ty,
+                                                                 radius, r4, sw_len, hwtab, sum3, wsum, i0, i1,
+                                                                 -i0);
+                    else if (rgb6)
                         jbf_tap_loop_rgb6<GREP, TLW, true>(lut_lane_addr, swsym, tile_lane_addr,
                                                            lds_addr(plane_b) + (uint32_t)tx * 2u, jc, ty,
                                                            radius, r4, sw_len, hwtab, sum3, wsum, i0, i1, -i0);
+                    else if (msad)
+                        jbf_tap_loop_grey4_la2<GREP, TLW, false, true, true>(lut_lane_addr, swsym,
+                                                                             tile_lane_addr, jc, ty, radius, r4,
+                                                                             sw_len, hwtab, sum1, wsum, i0, i1,
+                                                                             -i0);
                     else
                         jbf_tap_loop_grey4_la2<GREP, TLW, false, true>(lut_lane_addr, swsym, tile_lane_addr,
                                                                        jc, ty, radius, r4, sw_len, hwtab,

@@ -471,6 +471,23 @@ __device__ __forceinline__ void jbf_tap_loop_grey4(uint32_t lut_lane_addr, uint3
 #undef RF_G4_TNOUT_3
 }
 
+// Which form of the SAD a wave's tap loop takes (jbf_tap_loop_grey4_la2 / jbf_tap_loop_rgb6, MSAD): the
+// masked SAD serves a wave only if no lane of it owns a centre with a zero among its joint bytes 0..2
+// (v_msad_u8 would leave that channel's difference out).  Known before the loop, reduced over the wave:
+// the result is wave-uniform, the branch on it a scalar one.  A lane outside EXEC has no say, and
+// neither has one the caller says runs no tap loop (`counts` false: the slab kernel asks with all its
+// lanes, those beyond its rows hold a clamped centre).
+__device__ __forceinline__ bool jbf_wave_takes_msad(const uint32_t (&jc)[kPix], bool counts = true)
+{
+    uint32_t z = 0u;
+#pragma unroll
+    for (int p = 0; p < kPix; p++) {
+        const uint32_t v = jc[p] | 0xff000000u;
+        z |= (v - 0x01010101u) & ~v & 0x80808080u;  // bit 7 of a byte set <=> one of v's bytes is zero
+    }
+    return __ballot(counts && z != 0u) == 0ull;
+}
+
 // jbf_tap_loop_grey4 with the gathers TWO column steps ahead of their use (round 5).  In the form above
 // a column's four LUT gathers are issued in the step before the one that multiplies by them, and the
 // step ends in s_waitcnt lgkmcnt(0): a wave has 8 instructions of its own between issue and wait, the
@@ -486,7 +503,13 @@ __device__ __forceinline__ void jbf_tap_loop_grey4(uint32_t lut_lane_addr, uint3
 // rows whose texels are what the LDS tile holds at the moment, tile row of tap row i for the lane's output
 // row = ty + i + row_bias - and ADDS to sum / wsum: slabs taken in increasing i keep every pixel's taps in
 // row-major order, so any radius runs through this loop with the bytes of one pass over the whole disk.
-template <int LUTREP, int TLW, bool J1 = false, bool SLAB = false>
+// MSAD (3-channel joint only, never with J1): the SADs are v_msad_u8 with the tap texel as S0 and the
+// centre as the reference S1 - the hardware leaves out the bytes whose REFERENCE byte is zero, and byte 3
+// of every jc[] is - so the tap texel goes in unmasked: no v_and_b32, no mask register, 25 instead of 26
+// VALU instructions per step.  A zero in one of the centre's own channels would drop that channel's
+// difference too: the caller picks this form per wave, only where no lane of the wave has such a centre
+// (jbf_wave_takes_msad), and the form with the mask otherwise.  Identical bytes.
+template <int LUTREP, int TLW, bool J1 = false, bool SLAB = false, bool MSAD = false>
 __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
                                                        const float *__restrict__ swsym,
                                                        uint32_t tile_lane_addr,
@@ -503,8 +526,10 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
     static_assert(LUTREP == 32 || LUTREP == 16 || LUTREP == 8 || LUTREP == 4, "LUT replicas");
     static_assert(Q4 + 1 <= 255, "ds_read2_b32 offsets are 8 bits (the largest one here: Q4 + 1)");
     static_assert(TLW % 4 == 0, "column-interleaved planes");
-    uint32_t mask = 0x00ffffffu;
-    asm volatile("" : "+v"(mask));  // keep the mask in a VGPR (a literal operand is full-pipe)
+    static_assert(!(MSAD && J1), "the single-channel form has no masked SAD");
+    [[maybe_unused]] uint32_t mask = 0x00ffffffu;
+    if constexpr (!MSAD)
+        asm volatile("" : "+v"(mask));  // keep the mask in a VGPR (a literal operand is full-pipe)
 
     // A tap row of half-width hw serves the lane's four outputs from the 2 hw + 4 columns -hw .. hw + 3.
     // The row starts at the EVEN column -hws (hws = hw rounded up to even) and runs whole groups of four
@@ -572,12 +597,13 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
 #pragma unroll
     for (int c = 0; c < 2; c++) {
         const uint32_t tx = c == 0 ? tp[0].x : tp[0].y;
-        const uint32_t tj = tx & mask;
+        const uint32_t tj = MSAD ? tx : tx & mask;
 #pragma unroll
         for (int p = 0; p < kPix; p++) {
             const uint32_t a =
-                J1 ? (tj > jc[p] ? tj - jc[p] : jc[p] - tj) + lut_lane_addr
-                   : __builtin_amdgcn_sad_u8(tj, jc[p], 0u) * (LUTREP * 4u) + lut_lane_addr;
+                J1     ? (tj > jc[p] ? tj - jc[p] : jc[p] - tj) + lut_lane_addr
+                : MSAD ? __builtin_amdgcn_msad_u8(tj, jc[p], 0u) * (LUTREP * 4u) + lut_lane_addr
+                       : __builtin_amdgcn_sad_u8(tj, jc[p], 0u) * (LUTREP * 4u) + lut_lane_addr;
             asm volatile("ds_read_b32 %0, %1" : "=v"(gg[c][p]) : "v"(a));
         }
         sv[c] = (float)(tx >> 24);
@@ -612,13 +638,13 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
     // column U (its src value converted two steps ago); the wait that leaves this step's four gathers in
     // flight.  SADn / ADRn: the instruction that forms output n's table index and the one that turns it
     // into an LDS address (J1: one v_sad_u32 does both).
-#define RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, SAD0, SAD1, SAD2, SAD3, ADR0, ADR1, ADR2, \
-                     ADR3)                                                                       \
+#define RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, F, SAD0, SAD1, SAD2, SAD3, ADR0, ADR1,   \
+                     ADR2, ADR3)                                                                 \
     {                                                                                            \
         float w0_, w1_, w2_, w3_;                                                                \
-        uint32_t tj_;                                                                            \
+        [[maybe_unused]] uint32_t tj_;                                                           \
         asm volatile(RF_L2_READ(U)                                                               \
-                     "v_and_b32 %[tj], %[mask], %[t2]\n\t"                                       \
+                     RF_L2_AND_##F                                                               \
                      SAD0 "v_mul_f32 %[w0], %[wv0], %[g0]\n\t"                                   \
                      SAD1 "v_mul_f32 %[w1], %[wv1], %[g1]\n\t"                                   \
                      SAD2 "v_mul_f32 %[w2], %[wv2], %[g2]\n\t"                                   \
@@ -642,29 +668,41 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
                      "v_add_f32 %[s2_], %[s2_], %[w2]\n\t"                                       \
                      "v_add_f32 %[s3], %[s3], %[w3]\n\t"                                         \
                      WAITTXT                                                                     \
-                     : RF_L2_TNOUT(U)[tj] "=&v"(tj_), [a0] "=&v"(GB[0]), [a1] "=&v"(GB[1]),      \
+                     : RF_L2_TNOUT(U) RF_L2_TJOUT_##F [a0] "=&v"(GB[0]), [a1] "=&v"(GB[1]),      \
                        [a2] "=&v"(GB[2]), [a3] "=&v"(GB[3]), [w0] "=&v"(w0_), [w1] "=&v"(w1_),   \
                        [w2] "=&v"(w2_), [w3] "=&v"(w3_), [s2] "=&v"(sv[((U) + 2) & 3]),          \
                        [ws0] "+v"(wsum[0]), [ws1] "+v"(wsum[1]), [ws2] "+v"(wsum[2]),            \
                        [ws3] "+v"(wsum[3]), [s0] "+v"(sum[0][0]), [s1] "+v"(sum[1][0]),          \
                        [s2_] "+v"(sum[2][0]), [s3] "+v"(sum[3][0])                               \
-                     : [ta] "v"(TA), [o0] "n"(O0), [o1] "n"(O1), [mask] "v"(mask),               \
+                     : [ta] "v"(TA), [o0] "n"(O0), [o1] "n"(O1), RF_L2_MASKIN_##F                \
                        [t2] "v"(RF_L2_TQ((U) + 2)), [jc0] "v"(jc[0]), [jc1] "v"(jc[1]),          \
                        [jc2] "v"(jc[2]), [jc3] "v"(jc[3]), [wv0] "s"(wv[4 - (U)]),               \
                        [wv1] "s"(wv[5 - (U)]), [wv2] "s"(wv[6 - (U)]), [wv3] "s"(wv[7 - (U)]),   \
                        [g0] "v"(GA[0]), [g1] "v"(GA[1]), [g2] "v"(GA[2]), [g3] "v"(GA[3]),       \
                        [sh] "n"(SHIFT), [la] "v"(lut_lane_addr), [s] "v"(sv[(U)]));              \
     }
+    // F = AND: the joint bytes of the tap texel masked into tj first; F = MSAD: no such instruction, no
+    // tj and no mask operand - the masked SAD takes the texel itself (S0) against the centre (S1)
+#define RF_L2_AND_AND "v_and_b32 %[tj], %[mask], %[t2]\n\t"
+#define RF_L2_AND_MSAD
+#define RF_L2_TJOUT_AND [tj] "=&v"(tj_),
+#define RF_L2_TJOUT_MSAD
+#define RF_L2_MASKIN_AND [mask] "v"(mask),
+#define RF_L2_MASKIN_MSAD
+#define RF_L2_ADR(N) "v_lshl_add_u32 %[a" #N "], %[a" #N "], %[sh], %[la]\n\t"
 #define RF_L2_STEP(U, GA, GB, TA, O0, O1, MID, WAITTXT)                                           \
-    RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, "v_sad_u8 %[a0], %[tj], %[jc0], 0\n\t",      \
+    RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, AND, "v_sad_u8 %[a0], %[tj], %[jc0], 0\n\t", \
                  "v_sad_u8 %[a1], %[tj], %[jc1], 0\n\t", "v_sad_u8 %[a2], %[tj], %[jc2], 0\n\t",  \
-                 "v_sad_u8 %[a3], %[tj], %[jc3], 0\n\t",                                         \
-                 "v_lshl_add_u32 %[a0], %[a0], %[sh], %[la]\n\t",                                \
-                 "v_lshl_add_u32 %[a1], %[a1], %[sh], %[la]\n\t",                                \
-                 "v_lshl_add_u32 %[a2], %[a2], %[sh], %[la]\n\t",                                \
-                 "v_lshl_add_u32 %[a3], %[a3], %[sh], %[la]\n\t")
+                 "v_sad_u8 %[a3], %[tj], %[jc3], 0\n\t", RF_L2_ADR(0), RF_L2_ADR(1), RF_L2_ADR(2), \
+                 RF_L2_ADR(3))
+#define RF_L2_STEP_MSAD(U, GA, GB, TA, O0, O1, MID, WAITTXT)                                      \
+    RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, MSAD,                                       \
+                 "v_msad_u8 %[a0], %[t2], %[jc0], 0\n\t", "v_msad_u8 %[a1], %[t2], %[jc1], 0\n\t", \
+                 "v_msad_u8 %[a2], %[t2], %[jc2], 0\n\t", "v_msad_u8 %[a3], %[t2], %[jc3], 0\n\t", \
+                 RF_L2_ADR(0), RF_L2_ADR(1), RF_L2_ADR(2), RF_L2_ADR(3))
 #define RF_L2_STEP_J1(U, GA, GB, TA, O0, O1, MID, WAITTXT)                                        \
-    RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, "v_sad_u32 %[a0], %[tj], %[jc0], %[la]\n\t", \
+    RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, AND,                                        \
+                 "v_sad_u32 %[a0], %[tj], %[jc0], %[la]\n\t",                                    \
                  "v_sad_u32 %[a1], %[tj], %[jc1], %[la]\n\t",                                    \
                  "v_sad_u32 %[a2], %[tj], %[jc2], %[la]\n\t",                                    \
                  "v_sad_u32 %[a3], %[tj], %[jc3], %[la]\n\t", "", "", "", "")
@@ -735,6 +773,8 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
     }
     if constexpr (J1) {
         RF_L2_ROW_LOOP(RF_L2_STEP_J1)
+    } else if constexpr (MSAD) {
+        RF_L2_ROW_LOOP(RF_L2_STEP_MSAD)
     } else {
         RF_L2_ROW_LOOP(RF_L2_STEP)
     }
@@ -749,7 +789,15 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
 #undef RF_L2_LOAD_WINDOW
 #undef RF_L2_HAND_OVER
 #undef RF_L2_STEP_J1
+#undef RF_L2_STEP_MSAD
 #undef RF_L2_STEP
+#undef RF_L2_ADR
+#undef RF_L2_AND_AND
+#undef RF_L2_AND_MSAD
+#undef RF_L2_TJOUT_AND
+#undef RF_L2_TJOUT_MSAD
+#undef RF_L2_MASKIN_AND
+#undef RF_L2_MASKIN_MSAD
 #undef RF_L2_STEP_X
 #undef RF_L2_READ
 #undef RF_L2_READ_0
@@ -772,7 +820,9 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
 // burst of nine, here each full-pipe instruction is followed by a simple one (v_mul/v_add).
 // SLAB: tap rows i_first .. i_last only, tile row of tap row i = ty + i + row_bias, sums ADDED to (see
 // jbf_tap_loop_grey4_la2).
-template <int LUTREP, int TLW, bool SLAB = false>
+// MSAD: v_msad_u8 on the unmasked tap texel, 43 instructions per step, chosen per wave (see
+// jbf_tap_loop_grey4_la2).
+template <int LUTREP, int TLW, bool SLAB = false, bool MSAD = false>
 __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
                                                   const float *__restrict__ swsym,
                                                   uint32_t tile_lane_addr,
@@ -788,8 +838,9 @@ __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
     constexpr int Q4 = TLW / 4;
     constexpr int SHIFT = LUTREP == 32 ? 7 : LUTREP == 16 ? 6 : LUTREP == 8 ? 5 : 4;
     static_assert(LUTREP == 32 || LUTREP == 16 || LUTREP == 8 || LUTREP == 4, "LUT replicas");
-    uint32_t mask = 0x00ffffffu;
-    asm volatile("" : "+v"(mask));  // keep the mask in a VGPR (a literal operand is full-pipe)
+    [[maybe_unused]] uint32_t mask = 0x00ffffffu;
+    if constexpr (!MSAD)
+        asm volatile("" : "+v"(mask));  // keep the mask in a VGPR (a literal operand is full-pipe)
 
     // Rows start at the even column -hws and run whole groups of four, as in jbf_tap_loop_grey4_la2.
     // Steps 0, 1 of a group read columns 2, 3 of the group through the address pair (ta, tb), steps 2, 3
@@ -838,10 +889,12 @@ __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(tq[0]), "+v"(tq[1]), "+v"(tqb[0]), "+v"(tqb[1]), "+s"(ws8));
     {
-        const uint32_t tj = tq[0] & mask;
+        const uint32_t tj = MSAD ? tq[0] : tq[0] & mask;
 #pragma unroll
         for (int p = 0; p < kPix; p++) {
-            const uint32_t a = __builtin_amdgcn_sad_u8(tj, jc[p], 0u) * (LUTREP * 4u) + lut_lane_addr;
+            const uint32_t a = (MSAD ? __builtin_amdgcn_msad_u8(tj, jc[p], 0u)
+                                     : __builtin_amdgcn_sad_u8(tj, jc[p], 0u)) * (LUTREP * 4u) +
+                               lut_lane_addr;
             asm volatile("ds_read_b32 %0, %1" : "=v"(gg[0][p]) : "v"(a));
         }
     }
@@ -851,22 +904,27 @@ __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
     // Column step U: texel (both planes) of column +2 from TA/TB + offset, SAD + gathers of column
     // +1, accumulation of column +0.  GA = gathers consumed, GB = gathers issued (their registers
     // hold alpha, then the LDS address, then the LUT value).
-#define RF_C6_STEP(U, GA, GB, TA, TB, OFFT, EXTRA_ASM, EXTRA_OPERANDS)                           \
+    // F = AND: v_and_b32 into tj, then v_sad_u8 on tj; F = MSAD: v_msad_u8 on the texel itself.
+#define RF_C6_AND_AND "v_and_b32 %[tj], %[mask], %[t1]\n\t"
+#define RF_C6_AND_MSAD
+#define RF_C6_TJOUT_AND [tj] "=&v"(tj_),
+#define RF_C6_TJOUT_MSAD
+#define RF_C6_MASKIN_AND [mask] "v"(mask),
+#define RF_C6_MASKIN_MSAD
+#define RF_C6_SAD_AND(N) "v_sad_u8 %[a" #N "], %[tj], %[jc" #N "], 0\n\t"
+#define RF_C6_SAD_MSAD(N) "v_msad_u8 %[a" #N "], %[t1], %[jc" #N "], 0\n\t"
+#define RF_C6_STEP(F, U, GA, GB, TA, TB, OFFT, EXTRA_ASM, EXTRA_OPERANDS)                        \
     {                                                                                            \
         float w0_, w1_, w2_, w3_, s0_, s1_, s2_, m0_, m1_, m2_, m3_;                             \
-        uint32_t tj_;                                                                            \
+        [[maybe_unused]] uint32_t tj_;                                                           \
         EXTRA_ASM /* (step 3: the next window's scalar load; the step ends in a full wait) */    \
         asm volatile("ds_read_b32 %[tn], %[ta] offset:%[off4]\n\t"                               \
                      "ds_read_u16 %[tnb], %[tb] offset:%[off2]\n\t"                              \
-                     "v_and_b32 %[tj], %[mask], %[t1]\n\t"                                       \
-                     "v_sad_u8 %[a0], %[tj], %[jc0], 0\n\t"                                      \
-                     "v_mul_f32 %[w0], %[wv0], %[g0]\n\t"                                        \
-                     "v_sad_u8 %[a1], %[tj], %[jc1], 0\n\t"                                      \
-                     "v_mul_f32 %[w1], %[wv1], %[g1]\n\t"                                        \
-                     "v_sad_u8 %[a2], %[tj], %[jc2], 0\n\t"                                      \
-                     "v_mul_f32 %[w2], %[wv2], %[g2]\n\t"                                        \
-                     "v_sad_u8 %[a3], %[tj], %[jc3], 0\n\t"                                      \
-                     "v_mul_f32 %[w3], %[wv3], %[g3]\n\t"                                        \
+                     RF_C6_AND_##F                                                               \
+                     RF_C6_SAD_##F(0) "v_mul_f32 %[w0], %[wv0], %[g0]\n\t"                       \
+                     RF_C6_SAD_##F(1) "v_mul_f32 %[w1], %[wv1], %[g1]\n\t"                       \
+                     RF_C6_SAD_##F(2) "v_mul_f32 %[w2], %[wv2], %[g2]\n\t"                       \
+                     RF_C6_SAD_##F(3) "v_mul_f32 %[w3], %[wv3], %[g3]\n\t"                       \
                      "v_cvt_f32_ubyte3 %[s0], %[t0]\n\t"                                         \
                      "v_add_f32 %[ws0], %[ws0], %[w0]\n\t"                                       \
                      "v_cvt_f32_ubyte0 %[s1], %[tb0]\n\t"                                        \
@@ -908,7 +966,7 @@ __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
                      "v_add_f32 %[c32], %[c32], %[m3]\n\t"                                       \
                      "s_waitcnt lgkmcnt(0)"                                                      \
                      : [tn] "=&v"(tq[((U) + 2) & 3]), [tnb] "=&v"(tqb[((U) + 2) & 3]),           \
-                       [tj] "=&v"(tj_), [a0] "=&v"(GB[0]), [a1] "=&v"(GB[1]), [a2] "=&v"(GB[2]), \
+                       RF_C6_TJOUT_##F [a0] "=&v"(GB[0]), [a1] "=&v"(GB[1]), [a2] "=&v"(GB[2]),  \
                        [a3] "=&v"(GB[3]), [w0] "=&v"(w0_), [w1] "=&v"(w1_), [w2] "=&v"(w2_),     \
                        [w3] "=&v"(w3_), [s0] "=&v"(s0_), [s1] "=&v"(s1_), [s2] "=&v"(s2_),       \
                        [m0] "=&v"(m0_), [m1] "=&v"(m1_), [m2] "=&v"(m2_), [m3] "=&v"(m3_),       \
@@ -920,7 +978,7 @@ __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
                        [c12] "+v"(sum[1][2]), [c22] "+v"(sum[2][2]), [c32] "+v"(sum[3][2])       \
                        EXTRA_OPERANDS                                                            \
                      : [ta] "v"(TA), [tb] "v"(TB), [off4] "n"((OFFT) * 4), [off2] "n"((OFFT) * 2), \
-                       [mask] "v"(mask), [t1] "v"(tq[((U) + 1) & 3]), [t0] "v"(tq[(U)]),         \
+                       RF_C6_MASKIN_##F [t1] "v"(tq[((U) + 1) & 3]), [t0] "v"(tq[(U)]),          \
                        [tb0] "v"(tqb[(U)]), [jc0] "v"(jc[0]), [jc1] "v"(jc[1]), [jc2] "v"(jc[2]), \
                        [jc3] "v"(jc[3]), [wv0] "s"(wv[4 - (U)]), [wv1] "s"(wv[5 - (U)]),         \
                        [wv2] "s"(wv[6 - (U)]), [wv3] "s"(wv[7 - (U)]), [g0] "v"(GA[0]),          \
@@ -935,45 +993,61 @@ __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
         asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(wn8) : "s"(wp_));                      \
     }
 
-    for (int i = i_lo; i <= i_hi; i++) {
-        uint32_t ta_next, tb_next, ta2_next, tb2_next, wa_next;
-        int ngroups_next;
-        row_addr(i < i_hi ? i + 1 : i, ta_next, tb_next, ta2_next, tb2_next, wa_next, ngroups_next);
-        for (int gq = 0; gq < ngroups - 1; gq++) {
-            float wv[8];
-            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];
-            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];
-            RF_C6_STEP(0, gg[0], gg[1], ta, tb, 0, RF_C6_NOASM, )
-            RF_C6_STEP(1, gg[1], gg[0], ta, tb, Q4, RF_C6_NOASM, )
-            RF_C6_STEP(2, gg[0], gg[1], ta2, tb2, 1, RF_C6_NOASM, )
-            wa_addr -= 4;
-            RF_C6_STEP(3, gg[1], gg[0], ta2, tb2, Q4 + 1, RF_C6_LOAD_WINDOW(wa_addr),
-                       RF_C6_COMMA_W)
-            ws8 = wn8;
-            ta += 4;
-            tb += 2;
-            ta2 += 4;
-            tb2 += 2;
-        }
-        {
-            float wv[8];
-            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];
-            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];
-            RF_C6_STEP(0, gg[0], gg[1], ta, tb, 0, RF_C6_NOASM, )
-            RF_C6_STEP(1, gg[1], gg[0], ta, tb, Q4, RF_C6_NOASM, )
-            // the columns past the end of this row carry no weight: fetch the next row's first two
-            RF_C6_STEP(2, gg[0], gg[1], ta2_next, tb2_next, 0, RF_C6_NOASM, )
-            RF_C6_STEP(3, gg[1], gg[0], ta2_next, tb2_next, Q4, RF_C6_LOAD_WINDOW(wa_next),
-                       RF_C6_COMMA_W)
-            ws8 = wn8;
-        }
-        ta = ta_next;
-        tb = tb_next;
-        ta2 = ta2_next;
-        tb2 = tb2_next;
-        wa_addr = wa_next;
-        ngroups = ngroups_next;
+#define RF_C6_ROW_LOOP(F)                                                                           \
+    for (int i = i_lo; i <= i_hi; i++) {                                                            \
+        uint32_t ta_next, tb_next, ta2_next, tb2_next, wa_next;                                     \
+        int ngroups_next;                                                                           \
+        row_addr(i < i_hi ? i + 1 : i, ta_next, tb_next, ta2_next, tb2_next, wa_next,               \
+                 ngroups_next);                                                                     \
+        for (int gq = 0; gq < ngroups - 1; gq++) {                                                  \
+            float wv[8];                                                                            \
+            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];                         \
+            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];                         \
+            RF_C6_STEP(F, 0, gg[0], gg[1], ta, tb, 0, RF_C6_NOASM, )                                \
+            RF_C6_STEP(F, 1, gg[1], gg[0], ta, tb, Q4, RF_C6_NOASM, )                               \
+            RF_C6_STEP(F, 2, gg[0], gg[1], ta2, tb2, 1, RF_C6_NOASM, )                              \
+            wa_addr -= 4;                                                                           \
+            RF_C6_STEP(F, 3, gg[1], gg[0], ta2, tb2, Q4 + 1, RF_C6_LOAD_WINDOW(wa_addr),            \
+                       RF_C6_COMMA_W)                                                               \
+            ws8 = wn8;                                                                              \
+            ta += 4;                                                                                \
+            tb += 2;                                                                                \
+            ta2 += 4;                                                                               \
+            tb2 += 2;                                                                               \
+        }                                                                                           \
+        {                                                                                           \
+            float wv[8];                                                                            \
+            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];                         \
+            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];                         \
+            RF_C6_STEP(F, 0, gg[0], gg[1], ta, tb, 0, RF_C6_NOASM, )                                \
+            RF_C6_STEP(F, 1, gg[1], gg[0], ta, tb, Q4, RF_C6_NOASM, )                               \
+            /* the columns past the end of this row carry no weight: the next row's first two */    \
+            RF_C6_STEP(F, 2, gg[0], gg[1], ta2_next, tb2_next, 0, RF_C6_NOASM, )                    \
+            RF_C6_STEP(F, 3, gg[1], gg[0], ta2_next, tb2_next, Q4, RF_C6_LOAD_WINDOW(wa_next),      \
+                       RF_C6_COMMA_W)                                                               \
+            ws8 = wn8;                                                                              \
+        }                                                                                           \
+        ta = ta_next;                                                                               \
+        tb = tb_next;                                                                               \
+        ta2 = ta2_next;                                                                             \
+        tb2 = tb2_next;                                                                             \
+        wa_addr = wa_next;                                                                          \
+        ngroups = ngroups_next;                                                                     \
     }
+    if constexpr (MSAD) {
+        RF_C6_ROW_LOOP(MSAD)
+    } else {
+        RF_C6_ROW_LOOP(AND)
+    }
+#undef RF_C6_ROW_LOOP
+#undef RF_C6_AND_AND
+#undef RF_C6_AND_MSAD
+#undef RF_C6_TJOUT_AND
+#undef RF_C6_TJOUT_MSAD
+#undef RF_C6_MASKIN_AND
+#undef RF_C6_MASKIN_MSAD
+#undef RF_C6_SAD_AND
+#undef RF_C6_SAD_MSAD
 #undef RF_C6_LOAD_WINDOW
 #undef RF_C6_COMMA_W
 #undef RF_C6_NOASM
