@@ -216,6 +216,37 @@ int rf_colorize_srgb_u8(const uint8_t *bgr, const float *r, uint8_t *refl_out, u
                         void *stream);
 
 /*
+ * rf_colorize_srgb_u8 over images of different sizes in one call: the percentile, the `max > 1`
+ * test and the NaN rule stay per image.
+ *   bgr, r, refl_out, shading_out  the n images tightly packed one after another: image i starts at
+ *                pixel sum over j < i of heights[j] * widths[j] (offsets are formed in 64 bits);
+ *                either output may be NULL, not both
+ *   heights, widths, k_refl, k_shading  n entries each, HOST memory: every size > 0, every image
+ *                with 3 * h * w < 2^32 (RF_E_UNSUPPORTED otherwise: the histogram counters are 32 bits
+ *                wide), k_refl[i] < 3 * h_i * w_i and k_shading[i] < h_i * w_i the ranks of image i
+ *   workspace    device scratch, 16-byte aligned, of at least rf_colorize_ragged_workspace_bytes(n,
+ *                heights, widths) bytes: 40 bytes per image rounded up to 256 (the image table) plus
+ *                what rf_colorize_workspace_bytes(n) asks for; 0 = arguments the call refuses.  It may
+ *                be reused call after call: a call clears everything it reads.
+ * The bytes written for image i are, byte for byte, those of rf_colorize_srgb_u8(n = 1, heights[i],
+ * widths[i], k_refl[i], k_shading[i], ...) on that image alone; n == 0 is RF_OK whatever the
+ * pointers are.  A workgroup takes one chunk of consecutive pixels of one image - one chunk length
+ * per call, chosen from the summed pixel count - so the 18 launches of the uniform entry serve the
+ * whole list.  The image table is staged in the workspace by one copy on `stream`, and for that copy
+ * the call SYNCHRONISES THE STREAM once; it is refused (RF_E_UNSUPPORTED) on a stream that is being
+ * captured into a graph.  rf_colorize_srgb_u8 above synchronises nothing and stays capturable.
+ * Every refusal (NULL pointers, n < 0, bad sizes or ranks - the message names the image -, more
+ * workgroups than one grid takes, RF_E_WORKSPACE for a workspace that is too small) is decided
+ * before any device work.
+ */
+size_t rf_colorize_ragged_workspace_bytes(int n, const int *heights, const int *widths);
+int rf_colorize_ragged_srgb_u8(const uint8_t *bgr, const float *r, uint8_t *refl_out,
+                               uint8_t *shading_out, int n, const int *heights, const int *widths,
+                               const unsigned long long *k_refl, const unsigned long long *k_shading,
+                               const double *srgb_steps, void *workspace, size_t workspace_bytes,
+                               void *stream);
+
+/*
  * CV_32F variants of the two filters (never reached by the reference's CLIs, whose images come
  * from cv2.imread as uint8; provided so that callers which stop quantising between stages keep
  * the cv2.ximgproc semantics).  Same layouts as the 8-bit entry points with float pixels.

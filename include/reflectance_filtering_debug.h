@@ -72,6 +72,11 @@
  *                        exists for the default grey loop (gathers two steps ahead) and the colour loop, in
  *                        the tile and the slab kernel; under "jbf_lookahead1" (the round-4 grey loop) and
  *                        "jbf_compiler_loop" every wave keeps the mask, whatever this option says.
+ *   "colorize_chunk_px"  ragged colourise (rf_colorize_ragged_srgb_u8): pixels per workgroup chunk, a
+ *                        multiple of 256 that replaces the plan rule (0 = the rule; anything else is
+ *                        refused with RF_E_BADARG by the entry and the plan query); identical bytes.
+ *                        Lets a test with tiny images run many chunks per image and chunks of more
+ *                        than 2048 pixels, and tools/decompose_list_time.py time other chunk lengths.
  *
  * The grey-guide form of the guided filter (rf_gf_ex_u8 with RF_GF_GREY_AS_BGR) has no stage 1 for
  * "gf_guide_cache" and "gf_exact": while either is set, such a call returns RF_E_UNSUPPORTED.  Every
@@ -81,7 +86,8 @@
  * its parameter sets are cut into chunks and how many points a wave of each chunk takes) without
  * touching a device, so that tests can assert which lane mapping a call runs at, and
  * rf_debug_jbf_ragged_plan the tile classes rf_jbf_ragged_u8 launches, rf_debug_jbf_ragged_slab_plan
- * its one launch of tap-row slabs at radius 53..468.
+ * its one launch of tap-row slabs at radius 53..468, and rf_debug_colorize_ragged_plan the chunk
+ * length and grid of rf_colorize_ragged_srgb_u8.
  */
 #ifndef REFLECTANCE_FILTERING_DEBUG_H
 #define REFLECTANCE_FILTERING_DEBUG_H
@@ -142,6 +148,14 @@ int rf_debug_jbf_ragged_plan(int n, const int *heights, const int *widths, int j
 int rf_debug_jbf_ragged_slab_plan(int n, const int *heights, const int *widths, int joint_cn,
                                   int src_cn, int d, double sigma_color, double sigma_space, int flags,
                                   int *out, int cap);
+
+/* The launch plan of rf_colorize_ragged_srgb_u8 for images of these sizes: the ints {chunk_px,
+ * workgroups} - the pixels one workgroup takes and the grid of the histogram and write kernels -
+ * followed by each image's first workgroup (the running sum of ceil(h * w / chunk_px)), as many of
+ * these 2 + n ints as `cap` holds, at out.  Decided by the planning function the entry launches from
+ * (the "colorize_chunk_px" switch included).  Returns n (out may be NULL when cap is 0), or the
+ * entry's refusal code for sizes it refuses or a bad cap.  Host only: needs no device. */
+int rf_debug_colorize_ragged_plan(int n, const int *heights, const int *widths, int *out, int cap);
 
 #ifdef __cplusplus
 }

@@ -31,12 +31,13 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
            "rf_colorize_srgb_u8", "rf_whdr_f32", "rf_jbf_f32_workspace_bytes", "rf_jbf_f32",
            "rf_gf_f32_workspace_bytes", "rf_gf_f32", "rf_jbf_points_workspace_bytes",
            "rf_jbf_points_u8", "rf_jbf_points_ragged_workspace_bytes", "rf_jbf_points_ragged_u8",
-           "rf_whdr_points_u8", "rf_jbf_ragged_workspace_bytes", "rf_jbf_ragged_u8")
+           "rf_whdr_points_u8", "rf_jbf_ragged_workspace_bytes", "rf_jbf_ragged_u8",
+           "rf_colorize_ragged_workspace_bytes", "rf_colorize_ragged_srgb_u8")
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
                  "rf_debug_jbf_points_plan", "rf_debug_jbf_ragged_plan",
-                 "rf_debug_jbf_ragged_slab_plan")
+                 "rf_debug_jbf_ragged_slab_plan", "rf_debug_colorize_ragged_plan")
 # switches that leave work out (wrong results, timing experiments only); all others keep the bytes
 RESULT_CHANGING_OPTIONS = ("jbf_stage_only", "gf_exp_skip")
 
@@ -89,6 +90,10 @@ def load_library():
         lib.rf_colorize_workspace_bytes.restype = sz
         lib.rf_colorize_srgb_u8.argtypes = [vp, vp, vp, vp, ci, ci, ci, u64, u64, vp, vp, sz, vp]
         lib.rf_colorize_srgb_u8.restype = ci
+        lib.rf_colorize_ragged_workspace_bytes.argtypes = [ci, vp, vp]
+        lib.rf_colorize_ragged_workspace_bytes.restype = sz
+        lib.rf_colorize_ragged_srgb_u8.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]
+        lib.rf_colorize_ragged_srgb_u8.restype = ci
         lib.rf_jbf_f32_workspace_bytes.argtypes = [ci, ci]
         lib.rf_jbf_f32_workspace_bytes.restype = sz
         lib.rf_jbf_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, cd, cd, ci, vp, sz, vp]
@@ -129,6 +134,8 @@ def load_library():
         lib.rf_debug_jbf_ragged_plan.restype = ci
         lib.rf_debug_jbf_ragged_slab_plan.argtypes = [ci, vp, vp, ci, ci, ci, cd, cd, ci, vp, ci]
         lib.rf_debug_jbf_ragged_slab_plan.restype = ci
+        lib.rf_debug_colorize_ragged_plan.argtypes = [ci, vp, vp, vp, ci]
+        lib.rf_debug_colorize_ragged_plan.restype = ci
         # RF_DEBUG_OPTIONS="name=value,...": preset the test / benchmark switches of
         # include/reflectance_filtering_debug.h for a whole process (timing experiments only).
         # Every preset is announced on stderr - loudly for the switches that change results.
@@ -252,6 +259,23 @@ def jbf_ragged_slab_plan(sizes, joint_cn, src_cn, d, sigma_color, sigma_space, f
     if rc < 0:
         check(rc, "rf_debug_jbf_ragged_slab_plan")
     return tuple(int(v) for v in out)
+
+
+def colorize_ragged_plan(sizes):
+    """The launch plan of rf_colorize_ragged_srgb_u8 for images of these sizes ([n,2] (h, w))
+    (rf_debug_colorize_ragged_plan, host only): (chunk_px, workgroups, [first workgroup of each
+    image])."""
+    import numpy as np
+    lib = load_library()
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    n = sizes.shape[0]
+    hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
+    ws = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
+    out = np.zeros(n + 2, dtype=np.int32)
+    rc = lib.rf_debug_colorize_ragged_plan(n, hs.ctypes.data, ws.ctypes.data, out.ctypes.data, n + 2)
+    if rc < 0:
+        check(rc, "rf_debug_colorize_ragged_plan")
+    return int(out[0]), int(out[1]), [int(v) for v in out[2:]]
 
 
 def require_gpu():

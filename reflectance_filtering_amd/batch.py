@@ -6,10 +6,13 @@ The reference handles one image per invocation (/root/reference/filter_reflectan
 files shards embarrassingly: each rank (torchrun sets RANK/WORLD_SIZE/LOCAL_RANK) takes a
 contiguous slice of the sorted file list and works through it in steps of 16 files as a pipeline
 - a thread pool decodes the next step and encodes the previous one while the device filters the
-current one - grouping the images of a step by size, pushing each group through the
-device-resident batch operators (a bilateral step whose images differ in size goes through one
-ragged call instead, filter_reflectance.apply_filter_list) and writing the same output files the
-single-image tools would write.  No collective is involved.
+current one - and writes the same output files the single-image tools would write.  A step whose
+images all have one size goes through the device-resident batch operators as one batch.  A step
+whose images differ in size goes through the list forms, one call for the whole step: `decompose`
+through decompose_with_trained_CNN.decompose_packed (the device work of decompose_list: one CNN pass
+over the packed photos, one ragged colourise), a bilateral `filter` through
+filter_reflectance.apply_filter_list (one ragged call per pass); only a guided `filter` step is still
+cut into runs of equal size, one batch per run.  No collective is involved.
 
     python -m reflectance_filtering_amd.batch filter --filter_type=bilateral --sigma_color=20 \
         --sigma_spatial=22 --inputs 'out/*-r.png' --guidance 'photos/{stem}.png' --path_out out
@@ -216,18 +219,36 @@ def decompose_files(inputs, path_out, rank=None, world=None):
     mine = my_slice(inputs, rank, world)
     firsts = []
 
+    def add(jobs, f, r8, refl, shad):
+        base = os.path.splitext(os.path.basename(f))[0]
+        jobs.append((os.path.join(path_out, base + "-r.png"), r8))
+        jobs.append((os.path.join(path_out, base + "-r_colorized.png"), refl))
+        jobs.append((os.path.join(path_out, base + "-s_colorized.png"), shad))
+        firsts.append(os.path.join(path_out, base + "-r.png"))
+
+    def compute_ragged(loaded):
+        """A step whose images differ in shape: the device work of dc.decompose_list over the whole
+        step (one CNN pass, one ragged colourise) instead of one decompose_batch per run of equal
+        shapes, then three copies of the packed outputs to the host, split there: identical bytes."""
+        sizes, _, r8, refl, shad = dc.decompose_packed([torch.from_numpy(t[1]).cuda() for t in loaded])
+        r8, refl, shad = r8.cpu().numpy(), refl.cpu().numpy(), shad.cpu().numpy()
+        jobs, first = [], 0
+        for (f, _), (h, w) in zip(loaded, sizes.tolist()):
+            px = slice(first, first + h * w)
+            add(jobs, f, r8[px].reshape(h, w), refl[px].reshape(h, w, 3), shad[px].reshape(h, w))
+            first += h * w
+        return jobs
+
     def compute(loaded):
+        if len(set(t[1].shape for t in loaded)) > 1:
+            return compute_ragged(loaded)
         jobs = []
         for group in group_by_shape(loaded, lambda t: t[1].shape):
             images = torch.from_numpy(np.stack([t[1] for t in group])).cuda()
             _, r8, refl, shad = dc.decompose_batch(images)
             r8, refl, shad = r8.cpu().numpy(), refl.cpu().numpy(), shad.cpu().numpy()
             for i, (f, _) in enumerate(group):
-                base = os.path.splitext(os.path.basename(f))[0]
-                jobs.append((os.path.join(path_out, base + "-r.png"), r8[i]))
-                jobs.append((os.path.join(path_out, base + "-r_colorized.png"), refl[i]))
-                jobs.append((os.path.join(path_out, base + "-s_colorized.png"), shad[i]))
-                firsts.append(os.path.join(path_out, base + "-r.png"))
+                add(jobs, f, r8[i], refl[i], shad[i])
         return jobs
 
     pipeline(mine, lambda f: (f, iu.imread(f)), compute)

@@ -21,7 +21,10 @@
 //    step function with at most 255 steps on the power branch, so the host computes the 255 step
 //    positions once with numpy itself (image_utils.srgb_write_steps) and the kernel counts the
 //    steps at or below x: exact for whatever libm the host has.
-#include "rf_common.hpp"
+#include <vector>
+
+#include "reflectance_filtering_debug.h"
+#include "rf_jbf_common.hpp"
 
 namespace rf {
 namespace {
@@ -48,41 +51,77 @@ __device__ inline void pixel_values(const uint8_t *px, float r, double (&refl)[3
         refl[c] = __ddiv_rn((double)px[c], den);
 }
 
-__global__ void colorize_init_kernel(SelState *st, int n, unsigned long long k_refl,
-                                     unsigned long long k_shading)
+// what a call's first kernel leaves in one (image, target) state: everything the passes read
+__device__ __forceinline__ void init_state(SelState &s, unsigned long long k)
 {
-    const int i = blockIdx.x;  // (image, target)
-    SelState &s = st[i];
     if (threadIdx.x == 0) {
         s.prefix = 0;
-        s.k = (i % kTargets) == 0 ? k_refl : k_shading;
+        s.k = k;
         s.maxkey = 0;
     }
     s.hist[threadIdx.x] = 0;
 }
 
-// pass p = 0..7 looks at key byte 7-p of the values whose higher bytes equal the prefix
-__global__ __launch_bounds__(256) void colorize_hist_kernel(const uint8_t *__restrict__ bgr,
-                                                            const float *__restrict__ r,
-                                                            SelState *__restrict__ st, size_t npx,
-                                                            int pass)
+__global__ void colorize_init_kernel(SelState *st, int n, unsigned long long k_refl,
+                                     unsigned long long k_shading)
+{
+    const int i = blockIdx.x;  // (image, target)
+    init_state(st[i], (i % kTargets) == 0 ? k_refl : k_shading);
+}
+
+// One image of a ragged call (rf_colorize_ragged_srgb_u8): where its pixels start in the packed
+// buffers, how many it has, its two percentile ranks and the first of its workgroups in the
+// one-dimensional grid of the histogram and write kernels (ceil(npx / chunk_px) each, image order).
+struct ColImage {
+    unsigned long long first;  // pixels before the image
+    unsigned long long npx;
+    unsigned long long k_refl, k_shading;
+    unsigned int wg0;
+    unsigned int pad;
+};
+static_assert(sizeof(ColImage) == 40, "the workspace holds 40 bytes per image");
+
+__global__ void colorize_ragged_init_kernel(SelState *st, const ColImage *__restrict__ images)
+{
+    const int i = blockIdx.x;  // (image, target)
+    const ColImage &im = images[i / kTargets];
+    init_state(st[i], (i % kTargets) == 0 ? im.k_refl : im.k_shading);
+}
+
+// The image a workgroup of the ragged kernels works on: the last one with wg0 <= blockIdx.x.
+// Everything here depends on blockIdx.x alone, so the search runs on scalar loads.
+__device__ __forceinline__ int ragged_image(const ColImage *__restrict__ images, int n)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (images[mid].wg0 <= blockIdx.x)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// pass p = 0..7 looks at key byte 7-p of the values whose higher bytes equal the prefix.
+// One workgroup's share of one image: the pixels p0, p0 + step, ... below p1 of the image at b / rr,
+// counted into the image's two states st[0..1].
+__device__ __forceinline__ void hist_pixels(const uint8_t *__restrict__ b, const float *__restrict__ rr,
+                                            SelState *__restrict__ st, size_t p0, size_t p1,
+                                            size_t step, int pass)
 {
     __shared__ unsigned int hist[kTargets][256];
     __shared__ unsigned long long lmax[kTargets];
-    const int img = blockIdx.y;
     hist[0][threadIdx.x] = 0;
     hist[1][threadIdx.x] = 0;
     if (threadIdx.x < kTargets)
         lmax[threadIdx.x] = 0;
     __syncthreads();
-    const uint8_t *b = bgr + (size_t)img * npx * 3;
-    const float *rr = r + (size_t)img * npx;
     const int shift = 56 - 8 * pass;
-    const unsigned long long pre0 = st[img * kTargets + 0].prefix;
-    const unsigned long long pre1 = st[img * kTargets + 1].prefix;
+    const unsigned long long pre0 = st[0].prefix;
+    const unsigned long long pre1 = st[1].prefix;
     unsigned long long m0 = 0, m1 = 0;
-    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < npx;
-         p += (size_t)gridDim.x * blockDim.x) {
+    for (size_t p = p0; p < p1; p += step) {
         double refl[3], sh;
         pixel_values(b + p * 3, rr[p], refl, sh);
 #pragma unroll
@@ -112,10 +151,35 @@ __global__ __launch_bounds__(256) void colorize_hist_kernel(const uint8_t *__res
     for (int t = 0; t < kTargets; t++) {
         const unsigned int c = hist[t][threadIdx.x];
         if (c)
-            atomicAdd(&st[img * kTargets + t].hist[threadIdx.x], c);
+            atomicAdd(&st[t].hist[threadIdx.x], c);
     }
     if (pass == 0 && threadIdx.x < kTargets)
-        atomicMax(&st[img * kTargets + threadIdx.x].maxkey, lmax[threadIdx.x]);
+        atomicMax(&st[threadIdx.x].maxkey, lmax[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void colorize_hist_kernel(const uint8_t *__restrict__ bgr,
+                                                            const float *__restrict__ r,
+                                                            SelState *__restrict__ st, size_t npx,
+                                                            int pass)
+{
+    const int img = blockIdx.y;
+    hist_pixels(bgr + (size_t)img * npx * 3, r + (size_t)img * npx, st + img * kTargets,
+                (size_t)blockIdx.x * blockDim.x + threadIdx.x, npx, (size_t)gridDim.x * blockDim.x,
+                pass);
+}
+
+// The same pass over images of different sizes: workgroup blockIdx.x takes one chunk of chunk_px
+// consecutive pixels of one image.
+__global__ __launch_bounds__(256) void colorize_ragged_hist_kernel(
+    const uint8_t *__restrict__ bgr, const float *__restrict__ r, SelState *__restrict__ st,
+    const ColImage *__restrict__ images, int n, unsigned int chunk_px, int pass)
+{
+    const int img = ragged_image(images, n);
+    const ColImage &im = images[img];
+    const size_t c0 = (size_t)(blockIdx.x - im.wg0) * chunk_px;
+    const size_t c1 = c0 + chunk_px < im.npx ? c0 + chunk_px : (size_t)im.npx;
+    hist_pixels(bgr + im.first * 3, r + im.first, st + img * kTargets, c0 + threadIdx.x, c1, 256,
+                pass);
 }
 
 // one workgroup per (image, target): bucket that holds rank k, then clear the histogram
@@ -172,40 +236,143 @@ __device__ inline double normalise(double v, bool on, double pct)
     return v > 1.0 ? 1.0 : v;
 }
 
-__global__ __launch_bounds__(256) void colorize_write_kernel(
-    const uint8_t *__restrict__ bgr, const float *__restrict__ r, const SelState *__restrict__ st,
-    uint8_t *__restrict__ refl_out, uint8_t *__restrict__ shading_out, size_t npx,
-    const double *__restrict__ steps_g)
+// One workgroup's share of one image, as hist_pixels: the bytes of the pixels p0, p0 + step, ...
+// below p1 of the image at b / rr into refl_o / shading_o (the image's own outputs, or NULL).
+__device__ __forceinline__ void write_pixels(const uint8_t *__restrict__ b, const float *__restrict__ rr,
+                                             const SelState *__restrict__ st,
+                                             uint8_t *__restrict__ refl_o,
+                                             uint8_t *__restrict__ shading_o, size_t p0, size_t p1,
+                                             size_t step, const double *__restrict__ steps_g)
 {
     __shared__ double steps[256];
     steps[threadIdx.x] = threadIdx.x < 255 ? steps_g[threadIdx.x] : __longlong_as_double(0x7ff0000000000000LL);
     __syncthreads();
-    const int img = blockIdx.y;
-    const SelState &s0 = st[img * kTargets + 0];
-    const SelState &s1 = st[img * kTargets + 1];
+    const SelState &s0 = st[0];
+    const SelState &s1 = st[1];
     // np.max(img) > 1.  The values are non-negative, so the key of a NaN (exponent field all
     // ones, non-zero fraction) lies above that of +inf: np.max is NaN then, `NaN > 1` is false,
     // and the target is written without normalisation.
     const unsigned long long one = key_of(1.0), inf = key_of(__longlong_as_double(0x7ff0000000000000LL));
     const bool n0 = s0.maxkey > one && s0.maxkey <= inf;
     const bool n1 = s1.maxkey > one && s1.maxkey <= inf;
-    const double p0 = __longlong_as_double((long long)s0.prefix);
-    const double p1 = __longlong_as_double((long long)s1.prefix);
-    const uint8_t *b = bgr + (size_t)img * npx * 3;
-    const float *rr = r + (size_t)img * npx;
-    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < npx;
-         p += (size_t)gridDim.x * blockDim.x) {
+    const double pc0 = __longlong_as_double((long long)s0.prefix);
+    const double pc1 = __longlong_as_double((long long)s1.prefix);
+    for (size_t p = p0; p < p1; p += step) {
         double refl[3], sh;
         pixel_values(b + p * 3, rr[p], refl, sh);
-        if (refl_out) {
-            uint8_t *o = refl_out + ((size_t)img * npx + p) * 3;
+        if (refl_o) {
+            uint8_t *o = refl_o + p * 3;
 #pragma unroll
             for (int c = 0; c < 3; c++)
-                o[c] = srgb_byte(normalise(refl[c], n0, p0), steps);
+                o[c] = srgb_byte(normalise(refl[c], n0, pc0), steps);
         }
-        if (shading_out)
-            shading_out[(size_t)img * npx + p] = srgb_byte(normalise(sh, n1, p1), steps);
+        if (shading_o)
+            shading_o[p] = srgb_byte(normalise(sh, n1, pc1), steps);
     }
+}
+
+__global__ __launch_bounds__(256) void colorize_write_kernel(
+    const uint8_t *__restrict__ bgr, const float *__restrict__ r, const SelState *__restrict__ st,
+    uint8_t *__restrict__ refl_out, uint8_t *__restrict__ shading_out, size_t npx,
+    const double *__restrict__ steps_g)
+{
+    const size_t first = (size_t)blockIdx.y * npx;
+    write_pixels(bgr + first * 3, r + first, st + blockIdx.y * kTargets,
+                 refl_out ? refl_out + first * 3 : nullptr, shading_out ? shading_out + first : nullptr,
+                 (size_t)blockIdx.x * blockDim.x + threadIdx.x, npx, (size_t)gridDim.x * blockDim.x,
+                 steps_g);
+}
+
+__global__ __launch_bounds__(256) void colorize_ragged_write_kernel(
+    const uint8_t *__restrict__ bgr, const float *__restrict__ r, const SelState *__restrict__ st,
+    uint8_t *__restrict__ refl_out, uint8_t *__restrict__ shading_out,
+    const ColImage *__restrict__ images, int n, unsigned int chunk_px,
+    const double *__restrict__ steps_g)
+{
+    const int img = ragged_image(images, n);
+    const ColImage &im = images[img];
+    const size_t c0 = (size_t)(blockIdx.x - im.wg0) * chunk_px;
+    const size_t c1 = c0 + chunk_px < im.npx ? c0 + chunk_px : (size_t)im.npx;
+    write_pixels(bgr + im.first * 3, r + im.first, st + img * kTargets,
+                 refl_out ? refl_out + im.first * 3 : nullptr,
+                 shading_out ? shading_out + im.first : nullptr, c0 + threadIdx.x, c1, 256, steps_g);
+}
+
+// ---- the launch plan of the ragged entry (host) ----------------------------------------------
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// 256 threads per workgroup and a grid below 2^32 threads
+constexpr unsigned long long kColMaxWorkgroups = (1ull << 24) - 1;
+
+struct ColPlan {
+    unsigned int chunk_px;            // pixels of one workgroup's chunk, one value per call
+    unsigned long long workgroups;    // of the histogram and the write kernel
+    std::vector<ColImage> images;
+};
+
+// The workspace: [image table, rounded up to 256 bytes][n x 2 SelState]
+size_t ragged_table_bytes(int n) { return align256(sizeof(ColImage) * (size_t)n); }
+
+// The argument rules of the sizes and ranks (k_refl / k_shading may both be NULL: a query without
+// ranks) and the chunk rule: with T pixels in all, chunks of 2048 * ceil(T / (2048 * 65536)) pixels -
+// 8 pixels per thread and at most 65536 + n workgroups, the two regimes of the uniform launch - or,
+// where that makes fewer than 1024 workgroups, of 256 * ceil(T / (256 * 1024)) pixels.  The debug
+// option "colorize_chunk_px" replaces the rule.  Touches no device.
+int plan_ragged(const char *who, int n, const int *heights, const int *widths,
+                const unsigned long long *k_refl, const unsigned long long *k_shading, ColPlan *plan)
+{
+    if (n < 0)
+        return fail(RF_E_BADARG, "%s: bad size n=%d", who, n);
+    if (n > 0 && (!heights || !widths))
+        return fail(RF_E_BADARG, "%s: NULL pointer", who);
+    plan->images.resize((size_t)n);
+    unsigned long long total = 0;
+    for (int i = 0; i < n; i++) {
+        if (heights[i] <= 0 || widths[i] <= 0)
+            return fail(RF_E_BADARG, "%s: bad size of image %d: h=%d w=%d", who, i, heights[i],
+                        widths[i]);
+        const unsigned long long npx = (unsigned long long)heights[i] * widths[i];
+        if (3 * npx >= (1ull << 32))
+            return fail(RF_E_UNSUPPORTED, "%s: image %d (%dx%d) holds 2^32 values or more: the "
+                                          "histogram counters are 32 bits wide", who, i, widths[i],
+                        heights[i]);
+        if (k_refl && (k_refl[i] >= 3 * npx || k_shading[i] >= npx))
+            return fail(RF_E_BADARG, "%s: percentile rank outside image %d", who, i);
+        plan->images[i] = ColImage{total, npx, k_refl ? k_refl[i] : 0, k_refl ? k_shading[i] : 0, 0, 0};
+        total += npx;
+    }
+    if (total > (1ull << 46))
+        return fail(RF_E_UNSUPPORTED, "%s: the images hold too many pixels", who);
+    auto count = [&](unsigned long long chunk) {
+        unsigned long long wgs = 0;
+        for (const ColImage &im : plan->images)
+            wgs += (im.npx + chunk - 1) / chunk;
+        return wgs;
+    };
+    auto ceil_div64 = [](unsigned long long a, unsigned long long b) { return (a + b - 1) / b; };
+    unsigned long long chunk = (unsigned long long)debug_get(kDbgColorizeChunkPx);
+    if (chunk != 0) {
+        if (chunk % 256 != 0)
+            return fail(RF_E_BADARG, "%s: debug option colorize_chunk_px = %llu is not a multiple of "
+                                     "256", who, chunk);
+    } else {
+        chunk = 2048 * std::max<unsigned long long>(1, ceil_div64(total, 2048ull * 65536));
+        if (count(chunk) < 1024)
+            chunk = 256 * std::max<unsigned long long>(1, ceil_div64(total, 256ull * 1024));
+    }
+    plan->chunk_px = (unsigned int)chunk;
+    plan->workgroups = 0;
+    for (ColImage &im : plan->images) {
+        if (plan->workgroups > kColMaxWorkgroups)
+            break;
+        im.wg0 = (unsigned int)plan->workgroups;
+        plan->workgroups += (im.npx + chunk - 1) / chunk;
+    }
+    if (plan->workgroups > kColMaxWorkgroups || (unsigned long long)n * kTargets > kColMaxWorkgroups)
+        return fail(RF_E_UNSUPPORTED, "%s: more workgroups than one grid takes (%llu)", who,
+                    kColMaxWorkgroups);
+    return RF_OK;
 }
 
 }  // namespace
@@ -256,6 +423,85 @@ extern "C" int rf_colorize_srgb_u8(const uint8_t *bgr, const float *r, uint8_t *
     }
     hipLaunchKernelGGL(colorize_write_kernel, dim3(bx, n), dim3(256), 0, stream, bgr, r, st, refl_out,
                        shading_out, npx, srgb_steps);
+    RF_HIP_CHECK(hipGetLastError());
+    return RF_OK;
+}
+
+extern "C" size_t rf_colorize_ragged_workspace_bytes(int n, const int *heights, const int *widths)
+{
+    using namespace rf;
+    ColPlan plan;
+    if (n <= 0 || plan_ragged("rf_colorize_ragged_workspace_bytes", n, heights, widths, nullptr,
+                              nullptr, &plan) != RF_OK)
+        return 0;
+    return ragged_table_bytes(n) + (size_t)n * kTargets * sizeof(SelState);
+}
+
+extern "C" int rf_debug_colorize_ragged_plan(int n, const int *heights, const int *widths, int *out,
+                                             int cap)
+{
+    using namespace rf;
+    if (cap < 0 || (cap > 0 && !out))
+        return fail(RF_E_BADARG, "rf_debug_colorize_ragged_plan: bad cap %d", cap);
+    ColPlan plan;
+    const int rc = plan_ragged("rf_debug_colorize_ragged_plan", n, heights, widths, nullptr, nullptr,
+                               &plan);
+    if (rc != RF_OK)
+        return rc;
+    if (cap > 0)
+        out[0] = (int)plan.chunk_px;
+    if (cap > 1)
+        out[1] = (int)plan.workgroups;
+    for (int i = 0; i < n && i + 2 < cap; i++)
+        out[i + 2] = (int)plan.images[i].wg0;
+    return n;
+}
+
+extern "C" int rf_colorize_ragged_srgb_u8(const uint8_t *bgr, const float *r, uint8_t *refl_out,
+                                          uint8_t *shading_out, int n, const int *heights,
+                                          const int *widths, const unsigned long long *k_refl,
+                                          const unsigned long long *k_shading,
+                                          const double *srgb_steps, void *workspace,
+                                          size_t workspace_bytes, void *stream_)
+{
+    using namespace rf;
+    const char *who = "rf_colorize_ragged_srgb_u8";
+    if (n == 0)
+        return RF_OK;
+    if (!bgr || !r || !srgb_steps || !workspace || !heights || !widths || !k_refl || !k_shading ||
+        (!refl_out && !shading_out))
+        return fail(RF_E_BADARG, "%s: NULL pointer", who);
+    ColPlan plan;
+    const int rc = plan_ragged(who, n, heights, widths, k_refl, k_shading, &plan);
+    if (rc != RF_OK)
+        return rc;
+    const size_t off_states = ragged_table_bytes(n);
+    const size_t need = off_states + (size_t)n * kTargets * sizeof(SelState);
+    if (workspace_bytes < need)
+        return fail(RF_E_WORKSPACE, "%s: workspace %zu B < %zu B", who, workspace_bytes, need);
+    if ((uintptr_t)workspace % 16 != 0)
+        return fail(RF_E_BADARG, "%s: the workspace must be 16-byte aligned", who);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (stream_is_capturing(stream))
+        return fail(RF_E_UNSUPPORTED, "%s: synchronises its stream and cannot be captured into a "
+                                      "graph", who);
+    // the host table must outlive the copy: the copy is waited for before the launches (this is
+    // the call's one synchronisation of `stream`)
+    RF_HIP_CHECK(hipMemcpyAsync(workspace, plan.images.data(), sizeof(ColImage) * (size_t)n,
+                                hipMemcpyHostToDevice, stream));
+    RF_HIP_CHECK(hipStreamSynchronize(stream));
+    const ColImage *images = reinterpret_cast<const ColImage *>(workspace);
+    SelState *st = reinterpret_cast<SelState *>(static_cast<char *>(workspace) + off_states);
+    const dim3 grid((unsigned int)plan.workgroups);
+    hipLaunchKernelGGL(colorize_ragged_init_kernel, dim3(n * kTargets), dim3(256), 0, stream, st,
+                       images);
+    for (int pass = 0; pass < 8; pass++) {
+        hipLaunchKernelGGL(colorize_ragged_hist_kernel, grid, dim3(256), 0, stream, bgr, r, st, images,
+                           n, plan.chunk_px, pass);
+        hipLaunchKernelGGL(colorize_pick_kernel, dim3(n * kTargets), dim3(256), 0, stream, st, pass);
+    }
+    hipLaunchKernelGGL(colorize_ragged_write_kernel, grid, dim3(256), 0, stream, bgr, r, st, refl_out,
+                       shading_out, images, n, plan.chunk_px, srgb_steps);
     RF_HIP_CHECK(hipGetLastError());
     return RF_OK;
 }

@@ -97,6 +97,7 @@ enum DebugOption {
     kDbgGfCwChanRun,       // guided filter, colour src, planar passes: n + 1 = runs of n pairs per channel in the column walk's item order (0: the library's 64; 1: channel fastest)
     kDbgGfExact,           // guided filter: exact-row stage 2 (off by default: measured slower, profiles/r06_gf_exact.md)
     kDbgJbfNoMsad,         // joint bilateral: every wave takes the tap loop with the mask (none the masked-SAD form)
+    kDbgColorizeChunkPx,   // ragged colourise: pixels per workgroup chunk (a multiple of 256; 0 = the plan rule)
     kDbgCount
 };
 int debug_get(int id);

@@ -155,6 +155,32 @@ def decompose_batch(images, weights=None):
     return r, r8, refl, shad
 
 
+def decompose_packed(images, weights=None):
+    """The device work of decompose_list with the results left packed, photo after photo: a list of
+    CUDA uint8 BGR tensors [H_i,W_i,3] -> (sizes int64 [n,2] (h, w), r float32 [total pixels], r_u8
+    [total pixels], reflectance bytes [total pixels, 3], shading bytes [total pixels]).  One pack,
+    one pass of the packed photos through the per-pixel network as one image [1, 1, total pixels, 3],
+    one ragged colourise (ops.colorize_ragged_srgb_u8: percentile and `max > 1` test per photo)."""
+    torch = _ffi.require_gpu()
+    bgr, sizes = ops.pack_images(images, "images", torch)
+    if bgr.shape[1] != 3:
+        raise ValueError("images must have 3 channels")
+    r, r8 = ops.cnn_reflectance_u8(bgr.view(1, 1, -1, 3), weights=weights)
+    r, r8 = r.view(-1), r8.view(-1)
+    refl, shad, _, _ = ops.colorize_ragged_srgb_u8(bgr, r, sizes=sizes)
+    return sizes, r, r8, refl, shad
+
+
+def decompose_list(images, weights=None):
+    """decompose_batch for photos of different sizes: a list of CUDA uint8 BGR tensors [H_i,W_i,3] ->
+    (list of r float32 [H_i,W_i], list of r_u8 [H_i,W_i], list of reflectance bytes [H_i,W_i,3], list
+    of shading bytes [H_i,W_i]), each bit for bit (r) and byte for byte what decompose_batch makes of
+    that photo alone; the views of one kind share one packed tensor (decompose_packed)."""
+    sizes, r, r8, refl, shad = decompose_packed(images, weights=weights)
+    grey = lambda t: [v.squeeze(-1) for v in ops.split_packed(t.view(-1, 1), sizes)]
+    return grey(r), grey(r8), ops.split_packed(refl, sizes), grey(shad)
+
+
 def decompose_image(filename_in, path_out, caffemodel=None):
     """Predict reflectance intensity for one image file and write `<base>-r.png`,
     `<base>-r_colorized.png`, `<base>-s_colorized.png`

@@ -12,13 +12,15 @@ _GF_CACHE_PER_DEVICE = 4
 _GF_CACHE_BYTES_PER_DEVICE = 64 << 30     # ... and at most this much scratch kept per device
 _cnn_consts = {}
 _jbf_ragged_workspaces = {}
+_colorize_ragged_workspaces = {}
 
 
 def release_workspaces():
-    """Drop the cached guided-filter and ragged-bilateral scratch buffers and CNN constants
-    (device memory)."""
+    """Drop the cached guided-filter, ragged-bilateral and ragged-colourise scratch buffers and CNN
+    constants (device memory)."""
     _gf_workspaces.clear()
     _jbf_ragged_workspaces.clear()
+    _colorize_ragged_workspaces.clear()
     _cnn_consts.clear()
     _steps_dev.clear()
 
@@ -199,19 +201,24 @@ def split_packed(packed, sizes):
     return views
 
 
-def _jbf_ragged_workspace(need, device, torch):
-    """The tile-record scratch of joint_bilateral_ragged_u8 for the CURRENT stream of `device`, cached
+def _stream_workspace(cache, need, device, torch):
+    """A scratch buffer of at least `need` bytes for the CURRENT stream of `device`, cached in `cache`
     per (device, stream) and grown on demand (work on one stream is ordered, so the next call's
-    copy cannot overtake the kernels still reading the records); release_workspaces() drops it."""
+    copy cannot overtake the kernels still reading the buffer)."""
     dev = device.index if device.index is not None else torch.cuda.current_device()
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _jbf_ragged_workspaces.get(key)
+    ws = cache.get(key)
     if ws is None or ws.numel() < need:
-        if len(_jbf_ragged_workspaces) >= 16:       # streams come and go
-            _jbf_ragged_workspaces.clear()
+        if len(cache) >= 16:                        # streams come and go
+            cache.clear()
         ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=device)
-        _jbf_ragged_workspaces[key] = ws
+        cache[key] = ws
     return ws
+
+
+def _jbf_ragged_workspace(need, device, torch):
+    """The tile-record scratch of joint_bilateral_ragged_u8; release_workspaces() drops it."""
+    return _stream_workspace(_jbf_ragged_workspaces, need, device, torch)
 
 
 def joint_bilateral_ragged_u8(joints, srcs, d, sigma_color, sigma_space, border=_ffi.BORDER_DEFAULT,
@@ -405,6 +412,17 @@ def cnn_reflectance_u8(bgr, weights=None, want_float=True, want_u8=True):
 _steps_dev = {}
 
 
+def _srgb_steps(dev, torch):
+    """iu.srgb_write_steps() on `dev`, uploaded once per device."""
+    from . import image_utils as iu
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    steps = _steps_dev.get(key)
+    if steps is None:
+        steps = torch.from_numpy(iu.srgb_write_steps()).to(dev)
+        _steps_dev[key] = steps
+    return steps
+
+
 def colorize_srgb_u8(images, r, want_reflectance=True, want_shading=True):
     """Device form of iu.colorize(r, image) followed by iu.imwrite(..., sRGB=True) of both
     results (/root/reference/decompose_with_trained_CNN.py:121-128): returns the uint8 bytes of
@@ -421,11 +439,7 @@ def colorize_srgb_u8(images, r, want_reflectance=True, want_shading=True):
         raise ValueError("r must be a contiguous CUDA float32 tensor [N,H,W] matching images")
     n, h, w, _ = images.shape
     dev = images.device
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    steps = _steps_dev.get(key)
-    if steps is None:
-        steps = torch.from_numpy(iu.srgb_write_steps()).to(dev)
-        _steps_dev[key] = steps
+    steps = _srgb_steps(dev, torch)
     refl = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev) if want_reflectance else None
     shad = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if want_shading else None
     if n == 0 or (refl is None and shad is None):
@@ -439,6 +453,75 @@ def colorize_srgb_u8(images, r, want_reflectance=True, want_shading=True):
                                  _ffi.current_stream_ptr(torch))
     _ffi.check(rc, "rf_colorize_srgb_u8")
     return refl, shad
+
+
+def colorize_ragged_srgb_u8(images, r, sizes=None, want_reflectance=True, want_shading=True):
+    """colorize_srgb_u8 over photos of different sizes in one call (rf_colorize_ragged_srgb_u8): the
+    percentile, the `max > 1` test and the NaN rule stay per image.  images: a list of n CUDA uint8
+    tensors [H_i, W_i, 3] and r a list of CUDA float32 tensors [H_i, W_i], or, with sizes = [n,2]
+    (h, w), the images already packed one after another as contiguous CUDA tensors: images uint8
+    [total pixels, 3], r float32 [total pixels].  Returns (packed reflectance bytes [total pixels, 3]
+    or None, packed shading bytes [total pixels] or None, list of reflectance views [H_i, W_i, 3],
+    list of shading views [H_i, W_i]); image i is, byte for byte, colorize_srgb_u8(images[i][None],
+    r[i][None]).  Synchronises the current stream."""
+    from . import image_utils as iu
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    if sizes is None:
+        r = list(r)
+        images, sizes = pack_images(images, "images", torch)
+        if len(r) != sizes.shape[0]:
+            raise ValueError("images and r must hold the same number of images")
+        for t, (h, w) in zip(r, sizes.tolist()):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+                    and t.is_contiguous() and tuple(t.shape) == (h, w)):
+                raise ValueError("r must be contiguous CUDA float32 tensors [H,W] matching images")
+        r = torch.cat([t.view(-1) for t in r])
+    else:
+        sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+        if sizes.shape[0] == 0:
+            raise ValueError("sizes is empty")
+        if sizes.min() <= 0:
+            raise ValueError("image sizes must be positive")
+        npx = int((sizes[:, 0] * sizes[:, 1]).sum())
+        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8
+                and images.dim() == 2 and images.is_contiguous() and images.shape[0] == npx):
+            raise ValueError("images must be a contiguous CUDA uint8 tensor [%d, 3]: the pixels of "
+                             "all images" % npx)
+        if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32
+                and r.is_contiguous() and tuple(r.shape) == (npx,)):
+            raise ValueError("r must be a contiguous CUDA float32 tensor [%d]: the pixels of all "
+                             "images" % npx)
+    if images.shape[1] != 3:
+        raise ValueError("images must have 3 channels")
+    if r.device != images.device:
+        raise ValueError("images and r must be on the same device")
+    if sizes.max() >= 2 ** 31:
+        raise ValueError("image too large")
+    dev = images.device
+    n, npx = sizes.shape[0], images.shape[0]
+    refl = torch.empty((npx, 3), dtype=torch.uint8, device=dev) if want_reflectance else None
+    shad = torch.empty((npx,), dtype=torch.uint8, device=dev) if want_shading else None
+    if refl is None and shad is None:
+        return None, None, [], []
+    steps = _srgb_steps(dev, torch)
+    hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
+    wds = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
+    counts = (sizes[:, 0] * sizes[:, 1]).tolist()
+    k_refl = np.array([iu.percentile_rank(3 * c) for c in counts], dtype=np.uint64)
+    k_shad = np.array([iu.percentile_rank(c) for c in counts], dtype=np.uint64)
+    need = lib.rf_colorize_ragged_workspace_bytes(n, hs.ctypes.data, wds.ctypes.data)
+    # need == 0: the entry says why
+    ws = _stream_workspace(_colorize_ragged_workspaces, need, dev, torch)
+    rc = lib.rf_colorize_ragged_srgb_u8(images.data_ptr(), r.data_ptr(),
+                                        refl.data_ptr() if refl is not None else None,
+                                        shad.data_ptr() if shad is not None else None, n,
+                                        hs.ctypes.data, wds.ctypes.data, k_refl.ctypes.data,
+                                        k_shad.ctypes.data, steps.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), _ffi.current_stream_ptr(torch))
+    _ffi.check(rc, "rf_colorize_ragged_srgb_u8")
+    return (refl, shad, split_packed(refl, sizes) if refl is not None else [],
+            [v.squeeze(-1) for v in split_packed(shad.view(-1, 1), sizes)] if shad is not None else [])
 
 
 def _chk_images_f32(t, name, torch):
