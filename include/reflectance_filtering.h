@@ -151,6 +151,43 @@ int rf_gf_ex_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, int n, i
                 void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * rf_gf_ex_u8 over images of different sizes in one call (a list of reflectance maps through
+ * GF(CNN, CNN) or GF(CNN, flat)).
+ *   guide, src, dst  the n images tightly packed one after another: image i starts at pixel
+ *                  sum over j < i of heights[j] * widths[j] (offsets are formed in 64 bits) and is
+ *                  heights[i] rows of widths[i] pixels.  Overlap is judged on the summed pixel count:
+ *                  dst may equal src, may not partially overlap it and may not overlap guide; guide
+ *                  may equal src (a map that guides itself).
+ *   heights, widths  n ints each, HOST memory: every entry must be > 0 (RF_E_BADARG otherwise, and
+ *                  for a NULL array)
+ *   workspace      device scratch, 16-byte aligned, of at least rf_gf_ragged_workspace_bytes(n,
+ *                  heights, widths, guide_cn, src_cn, radius, flags) bytes; 0 = arguments the call
+ *                  refuses.  A NULL, misaligned or smaller workspace is RF_E_BADARG.
+ * The bytes written for image i are, byte for byte, what rf_gf_ex_u8(n = 1, heights[i], widths[i], ...)
+ * writes with the same other arguments; channel, flag, radius and overlap rules and refusals are
+ * rf_gf_ex_u8's (the debug options it refuses with a grey guide included); n == 0 is RF_OK whatever
+ * the pointers are.
+ * Ragged route - src_cn == 1, radius 1..128, every image below 2^28 pixels: stage 1, the row walk and
+ * the column walk run ONCE per pass over all images (three launches per pass, on `stream` alone), each
+ * workgroup finding its image through a table in the workspace: 48 bytes per image, 16 bytes per work
+ * item (stage 1: strip x segment; row walk: 64-row block; column walk: 16-column block, in 8 equal
+ * runs), rounded up to 256, followed by the row states (32 * ceil(w / 16) * h bytes per image) and
+ * alpha/beta (16 bytes per pixel) of the WHOLE list: a long list is split by the caller.  The table is
+ * staged by one copy, for which the call SYNCHRONISES THE STREAM once.
+ * Fallback route - src_cn == 3, radius 0, radius above 128 (and the debug options that select another
+ * stage-2 form): rf_gf_ex_u8 once per image on a workspace sized for the most demanding image: the
+ * same bytes with n calls and no synchronisation.
+ * Either way the call is refused (RF_E_UNSUPPORTED) on a stream that is being captured into a graph,
+ * before anything is enqueued.
+ */
+size_t rf_gf_ragged_workspace_bytes(int n, const int *heights, const int *widths, int guide_cn,
+                                    int src_cn, int radius, int flags);
+int rf_gf_ragged_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, int n,
+                    const int *heights, const int *widths, int guide_cn, int src_cn, int radius,
+                    double eps, int iterations, int flags, void *workspace, size_t workspace_bytes,
+                    void *stream);
+
+/*
  * 1x1 CNN reflectance predictor on uint8 BGR images.
  * Replaces  caffe.Net(network_definition.prototxt, TEST, weights=learned_weights.caffemodel),
  * blobs['images'] <- imgCV2_to_caffeBlob(image), forward(), blobs['reflectance_intensity']

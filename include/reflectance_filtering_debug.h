@@ -86,8 +86,9 @@
  * its parameter sets are cut into chunks and how many points a wave of each chunk takes) without
  * touching a device, so that tests can assert which lane mapping a call runs at, and
  * rf_debug_jbf_ragged_plan the tile classes rf_jbf_ragged_u8 launches, rf_debug_jbf_ragged_slab_plan
- * its one launch of tap-row slabs at radius 53..468, and rf_debug_colorize_ragged_plan the chunk
- * length and grid of rf_colorize_ragged_srgb_u8.
+ * its one launch of tap-row slabs at radius 53..468, rf_debug_colorize_ragged_plan the chunk
+ * length and grid of rf_colorize_ragged_srgb_u8, and rf_debug_gf_ragged_plan the route and grids of
+ * rf_gf_ragged_u8.
  */
 #ifndef REFLECTANCE_FILTERING_DEBUG_H
 #define REFLECTANCE_FILTERING_DEBUG_H
@@ -156,6 +157,15 @@ int rf_debug_jbf_ragged_slab_plan(int n, const int *heights, const int *widths, 
  * (the "colorize_chunk_px" switch included).  Returns n (out may be NULL when cap is 0), or the
  * entry's refusal code for sizes it refuses or a bad cap.  Host only: needs no device. */
 int rf_debug_colorize_ragged_plan(int n, const int *heights, const int *widths, int *out, int cap);
+
+/* The route of rf_gf_ragged_u8 for these arguments and, on the ragged route, its launches: the six
+ * ints {launches per pass (3), workgroups of stage 1, of the row walk, of the column walk, left halo
+ * and output columns of a stage-1 strip}, as many of them as `cap` holds, at out.  Decided by the
+ * planning function the entry launches from (the debug switches included).  Returns 1 on the ragged
+ * route, 0 where the entry calls rf_gf_ex_u8 once per image (and for n == 0; out is left alone), or the
+ * entry's refusal code for arguments it refuses or a bad cap.  Host only: needs no device. */
+int rf_debug_gf_ragged_plan(int n, const int *heights, const int *widths, int guide_cn, int src_cn,
+                            int radius, int flags, int *out, int cap);
 
 #ifdef __cplusplus
 }

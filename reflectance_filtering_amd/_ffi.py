@@ -32,12 +32,14 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
            "rf_gf_f32_workspace_bytes", "rf_gf_f32", "rf_jbf_points_workspace_bytes",
            "rf_jbf_points_u8", "rf_jbf_points_ragged_workspace_bytes", "rf_jbf_points_ragged_u8",
            "rf_whdr_points_u8", "rf_jbf_ragged_workspace_bytes", "rf_jbf_ragged_u8",
-           "rf_colorize_ragged_workspace_bytes", "rf_colorize_ragged_srgb_u8")
+           "rf_colorize_ragged_workspace_bytes", "rf_colorize_ragged_srgb_u8",
+           "rf_gf_ragged_workspace_bytes", "rf_gf_ragged_u8")
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
                  "rf_debug_jbf_points_plan", "rf_debug_jbf_ragged_plan",
-                 "rf_debug_jbf_ragged_slab_plan", "rf_debug_colorize_ragged_plan")
+                 "rf_debug_jbf_ragged_slab_plan", "rf_debug_colorize_ragged_plan",
+                 "rf_debug_gf_ragged_plan")
 # switches that leave work out (wrong results, timing experiments only); all others keep the bytes
 RESULT_CHANGING_OPTIONS = ("jbf_stage_only", "gf_exp_skip")
 
@@ -79,6 +81,10 @@ def load_library():
         lib.rf_gf_u8.restype = ci
         lib.rf_gf_ex_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, vp, sz, vp]
         lib.rf_gf_ex_u8.restype = ci
+        lib.rf_gf_ragged_workspace_bytes.argtypes = [ci, vp, vp, ci, ci, ci, ci]
+        lib.rf_gf_ragged_workspace_bytes.restype = sz
+        lib.rf_gf_ragged_u8.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, ci, cd, ci, ci, vp, sz, vp]
+        lib.rf_gf_ragged_u8.restype = ci
         lib.rf_cnn_reflectance_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
         lib.rf_cnn_reflectance_u8.restype = ci
         lib.rf_cnn_pack_weights.argtypes = [vp, vp, vp]
@@ -136,6 +142,8 @@ def load_library():
         lib.rf_debug_jbf_ragged_slab_plan.restype = ci
         lib.rf_debug_colorize_ragged_plan.argtypes = [ci, vp, vp, vp, ci]
         lib.rf_debug_colorize_ragged_plan.restype = ci
+        lib.rf_debug_gf_ragged_plan.argtypes = [ci, vp, vp, ci, ci, ci, ci, vp, ci]
+        lib.rf_debug_gf_ragged_plan.restype = ci
         # RF_DEBUG_OPTIONS="name=value,...": preset the test / benchmark switches of
         # include/reflectance_filtering_debug.h for a whole process (timing experiments only).
         # Every preset is announced on stderr - loudly for the switches that change results.
@@ -276,6 +284,26 @@ def colorize_ragged_plan(sizes):
     if rc < 0:
         check(rc, "rf_debug_colorize_ragged_plan")
     return int(out[0]), int(out[1]), [int(v) for v in out[2:]]
+
+
+def gf_ragged_plan(sizes, guide_cn, src_cn, radius, flags=0):
+    """The route of rf_gf_ragged_u8 for images of these sizes ([n,2] (h, w)) (rf_debug_gf_ragged_plan,
+    host only): None where the entry calls rf_gf_ex_u8 once per image, else the dict {launches (per
+    pass), stage1, rowstate, colwalk (the three grids), hl, out_w (the stage-1 strip)}."""
+    import numpy as np
+    lib = load_library()
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
+    ws = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
+    out = np.zeros(6, dtype=np.int32)
+    rc = lib.rf_debug_gf_ragged_plan(sizes.shape[0], hs.ctypes.data, ws.ctypes.data, int(guide_cn),
+                                     int(src_cn), int(radius), int(flags), out.ctypes.data, 6)
+    if rc < 0:
+        check(rc, "rf_debug_gf_ragged_plan")
+    if rc == 0:
+        return None
+    return dict(zip(("launches", "stage1", "rowstate", "colwalk", "hl", "out_w"),
+                    (int(v) for v in out)))
 
 
 def require_gpu():

@@ -11,8 +11,9 @@ images all have one size goes through the device-resident batch operators as one
 whose images differ in size goes through the list forms, one call for the whole step: `decompose`
 through decompose_with_trained_CNN.decompose_packed (the device work of decompose_list: one CNN pass
 over the packed photos, one ragged colourise), a bilateral `filter` through
-filter_reflectance.apply_filter_list (one ragged call per pass); only a guided `filter` step is still
-cut into runs of equal size, one batch per run.  No collective is involved.
+filter_reflectance.apply_filter_list (one ragged call per pass), and so does a guided `filter` step
+whose sources are all grey (one ragged call for all passes); only a guided step with a colour source
+is still cut into runs of equal size, one batch per run.  No collective is involved.
 
     python -m reflectance_filtering_amd.batch filter --filter_type=bilateral --sigma_color=20 \
         --sigma_spatial=22 --inputs 'out/*-r.png' --guidance 'photos/{stem}.png' --path_out out
@@ -153,9 +154,10 @@ def filter_files(filter_type, inputs, guidance_pattern, sigma_color, sigma_spati
         return name
 
     def compute_ragged(loaded):
-        """A bilateral step whose images differ in shape: one ragged call per pass over the whole
-        step (fr.apply_filter_list) instead of one launch per run of equal shapes.  The grey
-        reductions of `compute` below, judged over the step: identical bytes."""
+        """A bilateral step whose images differ in shape - or a guided one whose sources are all
+        grey: one ragged call over the whole step (fr.apply_filter_list; one per pass for the
+        bilateral filter) instead of one launch per run of equal shapes.  The grey reductions of
+        `compute` below, judged over the step: identical bytes."""
         grey_src = all(_is_grey(t[1]) for t in loaded)
         grey_gui = grey_src and all(_is_grey(t[2]) for t in loaded)
         cut = lambda a, grey: np.ascontiguousarray(a[..., :1]) if grey else a
@@ -170,7 +172,8 @@ def filter_files(filter_type, inputs, guidance_pattern, sigma_color, sigma_spati
         return jobs
 
     def compute(loaded):
-        if filter_type == "bilateral" and len(set(t[1].shape for t in loaded)) > 1:
+        if len(set(t[1].shape for t in loaded)) > 1 and (
+                filter_type == "bilateral" or all(_is_grey(t[1]) for t in loaded)):
             return compute_ragged(loaded)
         jobs = []
         for group in group_by_shape(loaded, lambda t: t[1].shape):

@@ -69,6 +69,17 @@ inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
     return a0 < b0 + nb && b0 < a0 + na;
 }
 
+// Is `stream` being captured into a graph?  (the ragged entries synchronise it and refuse then)
+inline bool stream_is_capturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return cs != hipStreamCaptureStatusNone;
+}
+
 // Test / benchmark switches behind rf_debug_option() (include/reflectance_filtering_debug.h).
 // All zero unless a test or tool sets them; none of them changes the bytes of a result except
 // kDbgJbfStageOnly, which leaves dst unwritten, and kDbgGfExpSkip, which leaves kernels out.

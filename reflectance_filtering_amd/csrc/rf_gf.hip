@@ -439,14 +439,19 @@ __device__ unsigned long long g_s1_stamps[16];
 //  additions would otherwise miss by one register; the three-channel kernel for three)
 // GREY: the guide is one byte per pixel standing for three equal channels (QuantGrey; plain stage 1
 // only, MODE = kS1Full and no exact rows).
-template <int SCN, int SPX, int MODE, bool EXACT = false, bool GREY = false>
+// RAGGED (rf_gf_ragged_u8; one src channel, plain stage 1): a 1-D grid of items (image, strip, segment)
+// from rag.items; h, w, seg_rows and the image's first pixel come from its record in rag.img.  The
+// strip geometry (hl, out_w) depends on the radius alone and stays launch-wide.
+template <int SCN, int SPX, int MODE, bool EXACT = false, bool GREY = false, bool RAGGED = false>
 __global__ __launch_bounds__(stage1_threads(SCN, GREY))
     __attribute__((amdgpu_waves_per_eu(SCN == 1 ? 4 : 3))) void gf_stage1_kernel(
     const uint8_t *__restrict__ guide, const uint8_t *__restrict__ src, float *__restrict__ ab,
     int h, int w, int radius, float eps_f, int eps_small, int seg_rows,
     const int *__restrict__ colour, float *__restrict__ gs, int ab_groups, int hl, int out_w,
-    const GfExactOut xo, const uint8_t *__restrict__ src_planar)
+    const GfExactOut xo, const uint8_t *__restrict__ src_planar, const GfRagged rag)
 {
+    static_assert(!RAGGED || (SCN == 1 && SPX == 1 && MODE == kS1Full && !EXACT),
+                  "ragged lists: one src channel, plain stage 1");
     // src_planar (three-channel kernel, later passes of an iterated call): the src channels as three
     // planes [img][3][h][w] - what the previous pass's column walk left - instead of interleaved
     static_assert(!EXACT || MODE == kS1Full, "exact rows: plain stage 1 only");
@@ -456,7 +461,23 @@ __global__ __launch_bounds__(stage1_threads(SCN, GREY))
     // and kACW - hl - out_w >= radius (rf_gf_u8 picks them, see gf_strip_geometry)
     // ab_groups: plane groups (src channels) an image has in ab - SPX, or 3 when a grey 3-channel
     // image is read from its one-byte-per-pixel intermediate (SPX = 1, see rf_gf_u8)
-    if (wrong_variant<SCN>(colour, blockIdx.z))
+    // the workgroup's strip, segment and image; pix0 = first pixel of its image
+    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+    size_t pix0;
+    if constexpr (RAGGED) {
+        const GfRagItem it = rag.items[blockIdx.x];
+        const GfRagImg *ri = rag.img + it.img;
+        h = ri->h;
+        w = ri->w;
+        seg_rows = ri->seg_rows;
+        bx = it.a;
+        by = it.b;
+        bz = it.img;
+        pix0 = (size_t)ri->px0;
+    } else {
+        pix0 = (size_t)blockIdx.z * ((size_t)h * w);
+    }
+    if (wrong_variant<SCN>(colour, bz))
         return;
     using Q = std::conditional_t<GREY, QuantGrey<SCN>, Quant<SCN, MODE != kS1Reuse>>;
     constexpr int NQ = Q::NQ;
@@ -469,14 +490,14 @@ __global__ __launch_bounds__(stage1_threads(SCN, GREY))
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int xs = blockIdx.x * out_w;
-    const int ys = blockIdx.y * seg_rows;
+    const int xs = bx * out_w;
+    const int ys = by * seg_rows;
     const int ye = min(ys + seg_rows, h);
     const size_t npx = (size_t)h * w;
-    const uint8_t *gimg = guide + (size_t)blockIdx.z * npx * kGCN;
-    const uint8_t *simg = src + (size_t)blockIdx.z * npx * SPX;
-    float *abimg = ab + (size_t)blockIdx.z * npx * (ab_groups * 4);
-    float *gsimg = MODE == kS1Full ? nullptr : gs + (size_t)blockIdx.z * npx * kGsFloats;
+    const uint8_t *gimg = guide + pix0 * kGCN;
+    const uint8_t *simg = src + pix0 * SPX;
+    float *abimg = ab + pix0 * (ab_groups * 4);
+    float *gsimg = MODE == kS1Full ? nullptr : gs + pix0 * kGsFloats;
     const int ks = 2 * radius + 1;
     const double scale = 1.0 / (double)(ks * ks);
     const double nbias = -(4503599627370496.0 * scale);
@@ -485,7 +506,7 @@ __global__ __launch_bounds__(stage1_threads(SCN, GREY))
     // a row's bytes are then (wave-uniform row pointer) + (32-bit lane offset): no 64-bit vector
     // arithmetic per load
     const bool planar = SCN == 3 && src_planar != nullptr;
-    const uint8_t *pimg = planar ? src_planar + (size_t)blockIdx.z * npx * 3 : nullptr;
+    const uint8_t *pimg = planar ? src_planar + pix0 * 3 : nullptr;
     uint32_t gx3[kACols], gxs[kACols];
 #pragma unroll
     for (int k = 0; k < kACols; k++) {
@@ -570,7 +591,7 @@ __global__ __launch_bounds__(stage1_threads(SCN, GREY))
     // twelve wave-iterations have no output column at all and are skipped - which waves those are
     // alternates with the workgroup's parity (t' = t rotated by two waves), so that the four SIMDs
     // of a CU see the same load.
-    const int tidp = (tid + ((blockIdx.x + blockIdx.y + blockIdx.z) & 1) * (kAThreads / 2)) & (kAThreads - 1);
+    const int tidp = (tid + ((bx + by + bz) & 1) * (kAThreads / 2)) & (kAThreads - 1);
     bool col_ok[kACols];
 #pragma unroll
     for (int k = 0; k < kACols; k++) {
@@ -1312,6 +1333,85 @@ extern "C" int rf_gf_f32(const float *guide, const float *src, float *dst, int n
                          void *workspace, size_t workspace_bytes, void *stream_);
 
 namespace {
+using namespace rf;
+// stage-1 strips of a w-column image (see the comment in gf_u8_entry): the left halo, the output
+// columns of a strip and how many strips cover the row.  hl and out_w depend on the radius, the
+// channel count and the guide kind - and on w only through the choice of the whole-wave halo, which is
+// taken where it costs no strip.
+struct StripGeom {
+    int hl, out_w, strips;
+};
+StripGeom gf_strip_geometry(int radius, int w, int scn, bool grey)
+{
+    const int acw = stage1_threads(scn, grey) * stage1_cols(scn, grey);
+    StripGeom g;
+    if (debug_get(kDbgGfS1LegacyStrips)) {
+        g.hl = radius;
+        g.out_w = acw - 2 * radius;
+    } else {
+        g.hl = (radius + 15) & ~15;
+        g.out_w = (acw - g.hl - radius) & ~15;
+        if (radius <= 64 && ceil_div(w, acw - 128) <= ceil_div(w, g.out_w)) {
+            g.hl = 64;
+            g.out_w = acw - 128;
+        }
+    }
+    g.strips = ceil_div(w, g.out_w);
+    return g;
+}
+
+// Rows per stage-1 segment of an h-row image whose rows of segments hold strips_k strips (the rule
+// and its measurements: the comment at part_setup in gf_u8_entry).  m_fill = images whose stage 1 is in
+// flight together, m_part = images of this launch.
+int gf_pick_seg(int h, int radius, int strips_k, int m_fill, int m_part, long long min_wgs, int cap,
+                int per_cu)
+{
+    int seg;
+    if (debug_get(kDbgGfS1MinWgs) > 0) {  // the round-4 rule, kept for A/B runs
+        min_wgs = debug_get(kDbgGfS1MinWgs);
+        const long long per_seg = std::max<long long>(1, (long long)strips_k * m_fill);
+        long long k = (min_wgs + per_seg - 1) / per_seg;          // segments per image
+        k = std::max<long long>(k, ceil_div(h, cap));
+        k = std::min<long long>(std::max<long long>(k, 1), h);
+        seg = ceil_div(h, (int)k);
+        seg = std::max(seg, std::min(h, std::max(3 * (2 * radius + 1) / 4, 32)));
+    } else {
+        const double warm = 0.2 * 2.0 * radius;
+        // time of k resident workgroups on one CU, in units of one workgroup alone
+        static const double crowd[5] = {0.0, 1.0, 2.0 / 1.38, 3.0 / 1.70, 4.0 / 1.87};
+        const long long slots = 256LL * per_cu;
+        double best = 0.0;
+        seg = h;
+        // (k runs over the segment counts that change the segment length: O(sqrt(h)) of them)
+        for (int k = std::max(1, ceil_div(h, cap)); k <= h;) {
+            const int sg = ceil_div(h, k);
+            const int k_next = sg > 1 ? (h - 1) / (sg - 1) + 1 : h + 1;
+            // full rounds of resident workgroups, then the rest on ceil(rest / 256) per CU: a
+            // launch a little over a whole round pays a whole workgroup's length for the rest
+            // (4 colour images at 4K: 800 workgroups on 768 places 2.47 ms, 640 on them 2.26)
+            // (two halves on two streams: the other half's kernels fill the tail of a launch,
+            //  so beyond one round the workgroups are priced as a fluid - at the C5 shard that
+            //  keeps round 4's three segments of 720 rows, 63.4 against 64.4 ms with 540)
+            const long long wgs = (long long)strips_k * m_fill * ceil_div(h, sg);
+            const long long full = wgs / slots, rest = wgs % slots;
+            const double t =
+                (m_fill > m_part && wgs > slots)
+                    ? (warm + sg) * (double)wgs / (double)slots * crowd[per_cu]
+                    : (warm + sg) * ((double)full * crowd[per_cu] +
+                                     (rest ? crowd[(int)((rest + 255) / 256)] : 0.0));
+            if (best == 0.0 || t < best * 0.999) {
+                best = t;
+                seg = sg;
+            }
+            k = std::max(k + 1, k_next);
+        }
+    }
+    seg = ceil_div(h, ceil_div(h, seg));  // equal segments: a launch ends with its longest one
+    if (debug_get(kDbgGfSegRows) > 0)
+        seg = std::min(h, debug_get(kDbgGfSegRows));
+    return seg;
+}
+
 // rf_gf_u8 and rf_gf_ex_u8 (`fn`: the entry point named in error messages)
 int gf_u8_entry(const char *fn, const uint8_t *guide, const uint8_t *src, uint8_t *dst, int n, int h,
                 int w, int guide_cn, int src_cn, int radius, double eps, int iterations, int flags,
@@ -1487,26 +1587,7 @@ int gf_u8_entry(const char *fn, const uint8_t *guide, const uint8_t *src, uint8_
     // is then one aligned 16-column block of the image); a halo of a whole wave on either side is
     // taken where it costs no strip (two of the strip's wave-iterations then have nothing to do, see
     // the kernel).  Debug option "gf_s1_legacy_strips": halo r on either side (rounds 1-5).
-    struct StripGeom {
-        int hl, out_w, strips;
-    };
-    auto strip_geometry = [&](int scn) {
-        const int acw = stage1_threads(scn, grey) * stage1_cols(scn, grey);
-        StripGeom g;
-        if (debug_get(kDbgGfS1LegacyStrips)) {
-            g.hl = radius;
-            g.out_w = acw - 2 * radius;
-        } else {
-            g.hl = (radius + 15) & ~15;
-            g.out_w = (acw - g.hl - radius) & ~15;
-            if (radius <= 64 && ceil_div(w, acw - 128) <= ceil_div(w, g.out_w)) {
-                g.hl = 64;
-                g.out_w = acw - 128;
-            }
-        }
-        g.strips = ceil_div(w, g.out_w);
-        return g;
-    };
+    auto strip_geometry = [&](int scn) { return gf_strip_geometry(radius, w, scn, grey); };
     const StripGeom geo3 = strip_geometry(3), geo1 = strip_geometry(1);
     const int strips3 = geo3.strips, strips1 = geo1.strips;
     const int xslots = std::max(strips1, strips3) * 8;  // exact rows: statistic slots per row
@@ -1614,50 +1695,7 @@ int gf_u8_entry(const char *fn, const uint8_t *guide, const uint8_t *src, uint8_
         // (profiles/r05_gf_seg_sweep.json; the measurements behind the earlier rules: HISTORY.md).
         // The 3-channel kernel (21 running sums, 3 workgroups per CU) is capped at 6 windows per segment.
         auto pick_seg = [&](int strips_k, long long min_wgs, int cap, int per_cu) {
-            int seg;
-            if (debug_get(kDbgGfS1MinWgs) > 0) {  // the round-4 rule, kept for A/B runs
-                min_wgs = debug_get(kDbgGfS1MinWgs);
-                const long long per_seg = std::max<long long>(1, (long long)strips_k * m_fill);
-                long long k = (min_wgs + per_seg - 1) / per_seg;          // segments per image
-                k = std::max<long long>(k, ceil_div(h, cap));
-                k = std::min<long long>(std::max<long long>(k, 1), h);
-                seg = ceil_div(h, (int)k);
-                seg = std::max(seg, std::min(h, std::max(3 * (2 * radius + 1) / 4, 32)));
-            } else {
-                const double warm = 0.2 * 2.0 * radius;
-                // time of k resident workgroups on one CU, in units of one workgroup alone
-                static const double crowd[5] = {0.0, 1.0, 2.0 / 1.38, 3.0 / 1.70, 4.0 / 1.87};
-                const long long slots = 256LL * per_cu;
-                double best = 0.0;
-                seg = h;
-                // (k runs over the segment counts that change the segment length: O(sqrt(h)) of them)
-                for (int k = std::max(1, ceil_div(h, cap)); k <= h;) {
-                    const int sg = ceil_div(h, k);
-                    const int k_next = sg > 1 ? (h - 1) / (sg - 1) + 1 : h + 1;
-                    // full rounds of resident workgroups, then the rest on ceil(rest / 256) per CU: a
-                    // launch a little over a whole round pays a whole workgroup's length for the rest
-                    // (4 colour images at 4K: 800 workgroups on 768 places 2.47 ms, 640 on them 2.26)
-                    // (two halves on two streams: the other half's kernels fill the tail of a launch,
-                    //  so beyond one round the workgroups are priced as a fluid - at the C5 shard that
-                    //  keeps round 4's three segments of 720 rows, 63.4 against 64.4 ms with 540)
-                    const long long wgs = (long long)strips_k * m_fill * ceil_div(h, sg);
-                    const long long full = wgs / slots, rest = wgs % slots;
-                    const double t =
-                        (m_fill > P.m && wgs > slots)
-                            ? (warm + sg) * (double)wgs / (double)slots * crowd[per_cu]
-                            : (warm + sg) * ((double)full * crowd[per_cu] +
-                                             (rest ? crowd[(int)((rest + 255) / 256)] : 0.0));
-                    if (best == 0.0 || t < best * 0.999) {
-                        best = t;
-                        seg = sg;
-                    }
-                    k = std::max(k + 1, k_next);
-                }
-            }
-            seg = ceil_div(h, ceil_div(h, seg));  // equal segments: a launch ends with its longest one
-            if (debug_get(kDbgGfSegRows) > 0)
-                seg = std::min(h, debug_get(kDbgGfSegRows));
-            return seg;
+            return gf_pick_seg(h, radius, strips_k, m_fill, P.m, min_wgs, cap, per_cu);
         };
         P.seg_rows1 = pick_seg(strips1, 960, h, 4);
         P.seg_rows3 = pick_seg(strips3, 1024, std::max(6 * (2 * radius + 1), 512), 3);
@@ -1678,6 +1716,7 @@ int gf_u8_entry(const char *fn, const uint8_t *guide, const uint8_t *src, uint8_
         const uint8_t *s0 = (it == 0 ? src : (const uint8_t *)dst) + (size_t)P.i0 * npx * src_cn;
         const dim3 ga3(strips3, ceil_div(h, seg_rows3), m), ga1(strips1, ceil_div(h, seg_rows1), m);
         const GfExactOut xo = {P.rows, P.xstat, nb, xslots};
+        const GfRagged no_rag = {nullptr, nullptr};
         // (the occupancy cap's dynamic-LDS pad can take a workgroup beyond the 64 KB a launch may use
         //  without asking: ask)
 #define RF_GF_S1_ATTR(K, PAD)                                                                      \
@@ -1694,19 +1733,19 @@ int gf_u8_entry(const char *fn, const uint8_t *guide, const uint8_t *src, uint8_
         if (src_cn == 3) {                                                                         \
             hipLaunchKernelGGL((gf_stage1_kernel<3, 3, MODE, EX, GR>), ga3, dim3(stage1_threads(3, GR)), pad3, \
                                st, g0, s0, ab, h, w, radius, eps_f, eps_small, seg_rows3, colour,  \
-                               gs, 3, geo3.hl, geo3.out_w, xo, it > 0 ? P.cmp3 : nullptr);         \
+                               gs, 3, geo3.hl, geo3.out_w, xo, it > 0 ? P.cmp3 : nullptr, no_rag); \
             if (cmp != nullptr)                                                                    \
                 hipLaunchKernelGGL((gf_stage1_kernel<1, 1, MODE, EX, GR>), ga1, dim3(stage1_threads(1, GR)), \
                                    pad1, st, g0, cmp, ab, h, w, radius, eps_f, eps_small,          \
-                                   seg_rows1, colour, gs, 3, geo1.hl, geo1.out_w, xo, nullptr);    \
+                                   seg_rows1, colour, gs, 3, geo1.hl, geo1.out_w, xo, nullptr, no_rag); \
             else                                                                                   \
                 hipLaunchKernelGGL((gf_stage1_kernel<1, 3, MODE, EX, GR>), ga1, dim3(stage1_threads(1, GR)), \
                                    pad1, st, g0, s0, ab, h, w, radius, eps_f, eps_small,           \
-                                   seg_rows1, colour, gs, 3, geo1.hl, geo1.out_w, xo, nullptr);    \
+                                   seg_rows1, colour, gs, 3, geo1.hl, geo1.out_w, xo, nullptr, no_rag); \
         } else {                                                                                   \
             hipLaunchKernelGGL((gf_stage1_kernel<1, 1, MODE, EX, GR>), ga1, dim3(stage1_threads(1, GR)), pad1, \
                                st, g0, s0, ab, h, w, radius, eps_f, eps_small, seg_rows1, colour,  \
-                               gs, 1, geo1.hl, geo1.out_w, xo, nullptr);                           \
+                               gs, 1, geo1.hl, geo1.out_w, xo, nullptr, no_rag);                   \
         }                                                                                          \
     } while (0)
         if (debug_get(kDbgGfExpSkip) & 1)
@@ -1897,6 +1936,289 @@ extern "C" int rf_gf_ex_u8(const uint8_t *guide, const uint8_t *src, uint8_t *ds
 {
     return gf_u8_entry("rf_gf_ex_u8", guide, src, dst, n, h, w, guide_cn, src_cn, radius, eps,
                        iterations, flags, workspace, workspace_bytes, stream_);
+}
+
+// ------------------------------------------------------------------------------------------
+// Ragged form (rf_gf_ragged_u8): images of different sizes packed one after another.
+//   ragged route    one src channel, radius 1..kGfMaxRadiusU8, every image below 2^28 pixels, none of
+//                   the switches that ask for another stage-2 form or a timing experiment: three
+//                   launches per pass over all images (stage 1, row states, column walk), addressed
+//                   through the table of rf_gf_fused.hpp, on the caller's stream alone
+//   fallback route  everything else: rf_gf_ex_u8 once per image
+// Workspace of the ragged route: [table, rounded up to 256 B][row states: double[4][nb_i][h_i] per
+// image][alpha/beta: 16 B per pixel]; table = one GfRagImg per image, then the GfRagItem records of
+// stage 1 (one per image, strip and segment; segment-major), of the row walk (one per image and 64-row
+// block) and of the column walk (8 runs of ceil(blocks / 8) records, one per image and 16-column
+// block in list order, the last run padded with img = -1).
+// ------------------------------------------------------------------------------------------
+namespace {
+struct GfRaggedPlan {
+    bool ragged = false;
+    size_t px = 0;             // pixels of all images
+    size_t state_doubles = 0;  // row states of all images
+    size_t table_bytes = 0;    // image records + item records, rounded up to 256
+    size_t bytes = 0;          // the workspace the route needs
+    int hl = 0, out_w = 0;     // stage-1 strip geometry (the radius's and the guide kind's)
+    int cw_per_xcd = 0;        // column-walk items per XCD run
+    std::vector<GfRagImg> img;
+    std::vector<GfRagItem> s1, rs, cw;
+};
+
+// The refusals of rf_gf_ex_u8 that need no pointers, for a list.  *px = pixels of all images.
+int gf_ragged_check(const char *who, int n, const int *heights, const int *widths, int guide_cn,
+                    int src_cn, int radius, int flags, size_t *px)
+{
+    *px = 0;
+    if (flags & ~RF_GF_GREY_AS_BGR)
+        return fail(RF_E_BADARG, "%s: unknown flag bits 0x%x", who, (unsigned)(flags & ~RF_GF_GREY_AS_BGR));
+    if (n < 0)
+        return fail(RF_E_BADARG, "%s: bad size n=%d", who, n);
+    if (!heights || !widths)
+        return fail(RF_E_BADARG, "%s: NULL size array", who);
+    for (int i = 0; i < n; i++) {
+        if (heights[i] <= 0 || widths[i] <= 0)
+            return fail(RF_E_BADARG, "%s: bad size of image %d: h=%d w=%d", who, i, heights[i],
+                        widths[i]);
+        *px += (size_t)heights[i] * widths[i];
+        if (*px > ((size_t)1 << 58))
+            return fail(RF_E_BADARG, "%s: the images hold too many pixels", who);
+    }
+    const bool grey = (flags & RF_GF_GREY_AS_BGR) != 0;
+    if (grey && guide_cn == 3)
+        return fail(RF_E_BADARG, "%s: RF_GF_GREY_AS_BGR takes a 1-channel guide (got 3 channels)", who);
+    if (grey && guide_cn != 1)
+        return fail(RF_E_UNSUPPORTED, "%s: RF_GF_GREY_AS_BGR takes a 1-channel guide (got %d)", who,
+                    guide_cn);
+    if (!grey && guide_cn != 3)
+        return fail(RF_E_UNSUPPORTED, "%s: guide must have 3 channels (got %d)", who, guide_cn);
+    if (src_cn != 1 && src_cn != 3)
+        return fail(RF_E_UNSUPPORTED, "%s: src channels must be 1 or 3 (got %d)", who, src_cn);
+    if (radius < 0 || radius > 4096)
+        return fail(RF_E_UNSUPPORTED, "%s: radius %d outside 0..4096", who, radius);
+    for (int i = 0; i < n; i++)
+        if (widths[i] >= (1 << 27))
+            return fail(RF_E_UNSUPPORTED, "%s: width %d of image %d beyond 2^27 - 1", who, widths[i], i);
+    if (grey && (debug_get(kDbgGfGuideCache) || debug_get(kDbgGfExact)))
+        return fail(RF_E_UNSUPPORTED, "%s: RF_GF_GREY_AS_BGR has no form for the debug options "
+                    "gf_guide_cache / gf_exact", who);
+    return RF_OK;
+}
+
+// The route of a checked list (n > 0) and, for the ragged route, its table.
+int gf_ragged_plan(const char *who, int n, const int *heights, const int *widths, int guide_cn,
+                   int src_cn, int radius, int flags, GfRaggedPlan *plan)
+{
+    const bool grey = (flags & RF_GF_GREY_AS_BGR) != 0;
+    bool ragged = src_cn == 1 && radius >= 1 && radius <= kGfMaxRadiusU8 &&
+                  gf_fused_launcher(radius) != nullptr &&  // (a development build holds one radius)
+                  !debug_get(kDbgGfTwoKernel) && !debug_get(kDbgGfChained) && !debug_get(kDbgGfExact) &&
+                  !debug_get(kDbgGfGuideCache) &&
+                  // (switches whose effect only the uniform entry implements: identical bytes either way)
+                  !debug_get(kDbgGfExpSkip) && !debug_get(kDbgGfS1Cap) && !debug_get(kDbgGfS1LegacyStrips);
+    for (int i = 0; i < n && ragged; i++)
+        ragged = (size_t)heights[i] * widths[i] < ((size_t)1 << 28);
+    plan->ragged = ragged;
+    if (!ragged) {
+        // rf_gf_ex_u8 once per image, on a workspace that holds the most demanding one
+        size_t need = 0;
+        for (int i = 0; i < n; i++)
+            need = std::max(need, rf_gf_workspace_bytes(1, heights[i], widths[i], guide_cn, src_cn, radius));
+        plan->bytes = need;
+        return RF_OK;
+    }
+    // strip geometry, one for the launch: the uniform rule on the list's strip count - the halo of a
+    // whole wave on either side where it costs the list no strip, else the widest strip the radius
+    // allows (strip widths cannot change a byte either)
+    StripGeom g0 = gf_strip_geometry(radius, 1, 1, grey);
+    {
+        const StripGeom gn = gf_strip_geometry(radius, 1 << 26, 1, grey);
+        long long s0 = 0, sn = 0;
+        for (int i = 0; i < n; i++) {
+            s0 += ceil_div(widths[i], g0.out_w);
+            sn += ceil_div(widths[i], gn.out_w);
+        }
+        if (sn < s0)
+            g0 = gn;
+    }
+    plan->hl = g0.hl;
+    plan->out_w = g0.out_w;
+    plan->img.resize((size_t)n);
+    size_t px0 = 0, st0 = 0, blocks = 0;
+    for (int i = 0; i < n; i++) {
+        const int h = heights[i], w = widths[i];
+        GfRagImg &I = plan->img[(size_t)i];
+        I = GfRagImg{};
+        I.px0 = px0;
+        I.st0 = st0;
+        I.h = h;
+        I.w = w;
+        I.nb = ceil_div(w, kSB);
+        I.strips = ceil_div(w, g0.out_w);
+        // rows per segment: the uniform rule for this image as if the list held nothing but images of
+        // its size - m_fill = list pixels / image pixels of them in flight together (segment lengths
+        // cannot change a byte: the window sums are exact integers in any order)
+        const size_t fill = std::max<size_t>(1, (plan->px + (size_t)h * w / 2) / ((size_t)h * w));
+        const int m_fill = (int)std::min<size_t>(fill, 1 << 20);
+        I.seg_rows = gf_pick_seg(h, radius, I.strips, m_fill, m_fill, 960, h, 4);
+        I.segs = ceil_div(h, I.seg_rows);
+        for (int sg = 0; sg < I.segs; sg++)
+            for (int st = 0; st < I.strips; st++)
+                plan->s1.push_back(GfRagItem{i, st, sg, 0});
+        for (int rb = 0; rb < ceil_div(h, kBRows); rb++)
+            plan->rs.push_back(GfRagItem{i, rb, 0, 0});
+        for (int b = 0; b < I.nb; b++)
+            plan->cw.push_back(GfRagItem{i, b, 0, 0});
+        px0 += (size_t)h * w;
+        st0 += (size_t)4 * I.nb * h;
+        blocks += (size_t)I.nb;
+    }
+    if (plan->s1.size() > 0x7fffffffu || plan->rs.size() > 0x7fffffffu || blocks + 8 > 0x7fffffffu)
+        return fail(RF_E_UNSUPPORTED, "%s: too many work items for one launch", who);
+    // column walk: each XCD (workgroup id mod 8) takes a contiguous run of ceil(blocks / 8) items in
+    // list order - balanced by count, not by walk length
+    plan->cw_per_xcd = (int)((blocks + 7) / 8);
+    plan->cw.resize((size_t)plan->cw_per_xcd * 8, GfRagItem{-1, 0, 0, 0});
+    plan->state_doubles = st0;
+    plan->table_bytes = (plan->img.size() * sizeof(GfRagImg) +
+                         (plan->s1.size() + plan->rs.size() + plan->cw.size()) * sizeof(GfRagItem) + 255) &
+                        ~(size_t)255;
+    plan->bytes = plan->table_bytes + plan->state_doubles * sizeof(double) + plan->px * 16;
+    return RF_OK;
+}
+}  // namespace
+
+extern "C" size_t rf_gf_ragged_workspace_bytes(int n, const int *heights, const int *widths,
+                                               int guide_cn, int src_cn, int radius, int flags)
+{
+    const char *who = "rf_gf_ragged_workspace_bytes";
+    GfRaggedPlan plan;
+    if (n <= 0 || gf_ragged_check(who, n, heights, widths, guide_cn, src_cn, radius, flags, &plan.px) != RF_OK ||
+        gf_ragged_plan(who, n, heights, widths, guide_cn, src_cn, radius, flags, &plan) != RF_OK)
+        return 0;
+    return plan.bytes;
+}
+
+extern "C" int rf_debug_gf_ragged_plan(int n, const int *heights, const int *widths, int guide_cn,
+                                       int src_cn, int radius, int flags, int *out, int cap)
+{
+    const char *who = "rf_debug_gf_ragged_plan";
+    if (cap < 0 || (cap > 0 && !out))
+        return fail(RF_E_BADARG, "%s: bad cap=%d", who, cap);
+    GfRaggedPlan plan;
+    if (int bad = gf_ragged_check(who, n, heights, widths, guide_cn, src_cn, radius, flags, &plan.px))
+        return bad;
+    if (n == 0)
+        return 0;
+    if (int bad = gf_ragged_plan(who, n, heights, widths, guide_cn, src_cn, radius, flags, &plan))
+        return bad;
+    if (!plan.ragged)
+        return 0;
+    const int record[6] = {3, (int)plan.s1.size(), (int)plan.rs.size(), 8 * plan.cw_per_xcd, plan.hl,
+                           plan.out_w};
+    std::copy(record, record + std::min(cap, 6), out);
+    return 1;
+}
+
+extern "C" int rf_gf_ragged_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, int n,
+                               const int *heights, const int *widths, int guide_cn, int src_cn,
+                               int radius, double eps, int iterations, int flags, void *workspace,
+                               size_t workspace_bytes, void *stream_)
+{
+    const char *who = "rf_gf_ragged_u8";
+    if (flags & ~RF_GF_GREY_AS_BGR)
+        return fail(RF_E_BADARG, "%s: unknown flag bits 0x%x", who, (unsigned)(flags & ~RF_GF_GREY_AS_BGR));
+    if (n == 0)  // an empty list is valid whatever the (possibly NULL) pointers are
+        return RF_OK;
+    if (!guide || !src || !dst)
+        return fail(RF_E_BADARG, "%s: NULL image pointer", who);
+    if (iterations < 1)
+        return fail(RF_E_BADARG, "%s: bad iterations=%d", who, iterations);
+    GfRaggedPlan plan;
+    if (int bad = gf_ragged_check(who, n, heights, widths, guide_cn, src_cn, radius, flags, &plan.px))
+        return bad;
+    const bool grey = (flags & RF_GF_GREY_AS_BGR) != 0;
+    const int gcn = grey ? 1 : 3;
+    if (ranges_overlap(dst, plan.px * src_cn, guide, plan.px * gcn))
+        return fail(RF_E_BADARG, "%s: dst must not overlap guide", who);
+    if (dst != src && ranges_overlap(dst, plan.px * src_cn, src, plan.px * src_cn))
+        return fail(RF_E_BADARG, "%s: dst may equal src but not partially overlap it", who);
+    if (int bad = gf_ragged_plan(who, n, heights, widths, guide_cn, src_cn, radius, flags, &plan))
+        return bad;
+    if (!workspace || workspace_bytes < plan.bytes || ((uintptr_t)workspace & 15))
+        return fail(RF_E_BADARG, "%s: workspace of %zu bytes, %zu needed (16-byte aligned)", who,
+                    workspace ? workspace_bytes : (size_t)0, plan.bytes);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (stream_is_capturing(stream))
+        return fail(RF_E_UNSUPPORTED, "%s: synchronises its stream and cannot be captured into a "
+                                      "graph", who);
+    if (!plan.ragged) {
+        size_t first = 0;
+        for (int i = 0; i < n; i++) {
+            const int rc = rf_gf_ex_u8(guide + first * gcn, src + first * src_cn, dst + first * src_cn,
+                                       1, heights[i], widths[i], guide_cn, src_cn, radius, eps,
+                                       iterations, flags, workspace, workspace_bytes, stream_);
+            if (rc != RF_OK)
+                return rc;
+            first += (size_t)heights[i] * widths[i];
+        }
+        return RF_OK;
+    }
+    // ---- the table: image records, then the item records of the three kernels, one copy --------
+    const size_t n_img = plan.img.size(), n_s1 = plan.s1.size(), n_rs = plan.rs.size(),
+                 n_cw = plan.cw.size();
+    std::vector<unsigned char> image(n_img * sizeof(GfRagImg) + (n_s1 + n_rs + n_cw) * sizeof(GfRagItem));
+    unsigned char *at = image.data();
+    __builtin_memcpy(at, plan.img.data(), n_img * sizeof(GfRagImg));
+    at += n_img * sizeof(GfRagImg);
+    __builtin_memcpy(at, plan.s1.data(), n_s1 * sizeof(GfRagItem));
+    at += n_s1 * sizeof(GfRagItem);
+    __builtin_memcpy(at, plan.rs.data(), n_rs * sizeof(GfRagItem));
+    at += n_rs * sizeof(GfRagItem);
+    __builtin_memcpy(at, plan.cw.data(), n_cw * sizeof(GfRagItem));
+    char *ws = static_cast<char *>(workspace);
+    const GfRagImg *d_img = reinterpret_cast<const GfRagImg *>(ws);
+    const GfRagItem *d_s1 = reinterpret_cast<const GfRagItem *>(ws + n_img * sizeof(GfRagImg));
+    const GfRagItem *d_rs = d_s1 + n_s1, *d_cw = d_rs + n_rs;
+    double *states = reinterpret_cast<double *>(ws + plan.table_bytes);
+    float *ab = reinterpret_cast<float *>(states + plan.state_doubles);
+    // the host image must outlive the copy: the copy is waited for before the launches (this is the
+    // call's one synchronisation of `stream`)
+    RF_HIP_CHECK(hipMemcpyAsync(workspace, image.data(), image.size(), hipMemcpyHostToDevice, stream));
+    RF_HIP_CHECK(hipStreamSynchronize(stream));
+    const float eps_f = (float)eps;
+    const int eps_small = eps < 1e-2;
+    const GfFusedLaunch fused_launch = gf_fused_launcher(radius);
+    const GfRagged rag_s1 = {d_img, d_s1};
+    const GfExactOut no_xo = {nullptr, nullptr, 0, 0};
+    for (int it = 0; it < iterations; it++) {
+        const uint8_t *s0 = it == 0 ? src : (const uint8_t *)dst;  // pass k reads the packed result of pass k - 1
+        if (grey)
+            hipLaunchKernelGGL((gf_stage1_kernel<1, 1, kS1Full, false, true, true>), dim3((unsigned)n_s1),
+                               dim3(stage1_threads(1, true)), 0, stream, guide, s0, ab, 0, 0, radius, eps_f,
+                               eps_small, 0, (const int *)nullptr, (float *)nullptr, 1, plan.hl,
+                               plan.out_w, no_xo, (const uint8_t *)nullptr, rag_s1);
+        else
+            hipLaunchKernelGGL((gf_stage1_kernel<1, 1, kS1Full, false, false, true>), dim3((unsigned)n_s1),
+                               dim3(stage1_threads(1, false)), 0, stream, guide, s0, ab, 0, 0, radius, eps_f,
+                               eps_small, 0, (const int *)nullptr, (float *)nullptr, 1, plan.hl,
+                               plan.out_w, no_xo, (const uint8_t *)nullptr, rag_s1);
+        GfFusedArgs fa = {};
+        fa.ab = ab;
+        fa.states = states;
+        fa.guide = guide;
+        fa.dst = dst;
+        fa.src_cn = 1;
+        fa.stream = stream;
+        fa.guide_cn = gcn;
+        fa.rag_rs = GfRagged{d_img, d_rs};
+        fa.rag_cw = GfRagged{d_img, d_cw};
+        fa.rs_items = (int)n_rs;
+        fa.cw_per_xcd = plan.cw_per_xcd;
+        fa.rag_ab_bytes = plan.px * 16;
+        fused_launch(fa);
+    }
+    RF_HIP_CHECK(hipGetLastError());
+    return RF_OK;
 }
 
 extern "C" size_t rf_gf_f32_workspace_bytes(int n, int h, int w, int guide_cn, int src_cn,

@@ -128,6 +128,33 @@ __device__ inline bool wrong_variant(const int *__restrict__ colour, int img)
     return colour != nullptr && (colour[img] != 0) != (SCN == 3);
 }
 
+// ------------------------------------------------------------------------------------------
+// Ragged addressing (rf_gf_ragged_u8: images of different sizes packed one after another, one
+// src channel).  The three kernels of a pass take their image from a table in the workspace instead
+// of from blockIdx and a launch-wide h, w, nb: one 16-byte record per work item names the image and
+// the item's place in it, one 48-byte record per image holds its first pixel, its size and where its
+// row states start.  Both are read with wave-uniform (scalar) loads in the kernel's prologue; after
+// it the bodies are the uniform ones.  Offsets INSIDE an image stay 32-bit (the host admits images
+// below 2^28 pixels and 2^27 columns), the per-image bases are 64-bit.
+// ------------------------------------------------------------------------------------------
+struct GfRagImg {
+    unsigned long long px0;  // first pixel of the image in guide, src, dst and alpha/beta
+    unsigned long long st0;  // first double of its row states ([4][nb][h])
+    int h, w, nb;            // rows, columns, 16-column blocks per row
+    int strips, seg_rows, segs;  // stage 1: strips per row of segments, rows per segment, segments
+    int pad[2];
+};
+static_assert(sizeof(GfRagImg) == 48, "table layout");
+// stage 1: a = strip, b = segment; row walk: a = 64-row block; column walk: a = 16-column block
+// (img < 0: a padding item of the column walk's per-XCD runs - the workgroup exits)
+struct GfRagItem {
+    int img, a, b, pad;
+};
+struct GfRagged {
+    const GfRagImg *img;     // nullptr (both): a uniform launch, geometry from the launch arguments
+    const GfRagItem *items;  // the launch's items, indexed by workgroup
+};
+
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F &&f)
 {
@@ -169,8 +196,10 @@ __global__ __launch_bounds__(256) void gf_rowstate_kernel(const float *__restric
                                                           int row_blocks, int np,
                                                           const int *__restrict__ colour, int src_np,
                                                           int nb, int streaming, const GfStateLayout lay,
-                                                          const GfExact xr)
+                                                          const GfExact xr, const GfRagged rag)
 {
+    // rag.items != nullptr (ragged list, one src channel, no exact rows): workgroup = one item
+    // (image, 64-row block); h, w, nb, the bases and the state layout come from the image's record
     // List mode (xr.on; exact rows): the workgroup's 64 lanes are the entries 64 rb .. 64 rb + 63 of the
     // plane group's list of flagged rows instead of 64 consecutive rows; workgroups past the end of
     // the list exit at once - on typical images a fraction of a percent of the rows is listed.
@@ -187,8 +216,29 @@ __global__ __launch_bounds__(256) void gf_rowstate_kernel(const float *__restric
     static_assert((NPER * NCH) % NBUF == 0, "the loop body is whole turns of the buffer ring");
     static_assert(KS + PAD <= 2 * F, "the window fills within the two peeled periods");
     const int ng = np / 4;                     // plane groups (src channels) per image
-    const int grp = blockIdx.x / row_blocks;   // plane group across the chunk of images
-    const int img = grp / ng, gq = grp - img * ng;
+    int img, gq, row0;
+    size_t pl0, st0;  // first float of the group's planes, first double of its states
+    GfStateLayout ly = lay;
+    if (rag.items != nullptr) {
+        const GfRagItem it = rag.items[blockIdx.x];
+        const GfRagImg *ri = rag.img + it.img;
+        h = ri->h;
+        w = ri->w;
+        nb = ri->nb;
+        img = 0;
+        gq = 0;
+        row0 = it.a * kBRows;
+        pl0 = (size_t)ri->px0 * 4;
+        st0 = (size_t)ri->st0;
+        ly = GfStateLayout{nb * h, h, 1};
+    } else {
+        const int grp = blockIdx.x / row_blocks;   // plane group across the chunk of images
+        img = grp / ng;
+        gq = grp - img * ng;
+        row0 = (blockIdx.x - grp * row_blocks) * kBRows;
+        pl0 = ((size_t)img * src_np + gq * 4) * h * w;
+        st0 = ((size_t)img * np + gq * 4) * nb * h;
+    }
     if (colour != nullptr && gq >= 1 && colour[img] == 0)
         return;  // grey 3-channel images only carry the 4 planes of their first channel
     __shared__ __align__(16) float tE[4][kBRows][20];  // pitch 20: 16-byte rows, conflict-free
@@ -196,7 +246,6 @@ __global__ __launch_bounds__(256) void gf_rowstate_kernel(const float *__restric
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // the wave's plane of the group
-    const int row0 = (blockIdx.x - grp * row_blocks) * kBRows;
     const int ig = img * ng + gq;
     const int listed = xr.on ? xr.count[ig] - row0 : 0;  // list entries from this workgroup's first one on
     if (xr.on && listed <= 0)
@@ -206,10 +255,8 @@ __global__ __launch_bounds__(256) void gf_rowstate_kernel(const float *__restric
     auto slot_row = [&](int r) __attribute__((always_inline)) {
         return xr.on ? rlist[min(r, listed - 1)] : min(row0 + r, h - 1);
     };
-    const float4 *S4 =
-        reinterpret_cast<const float4 *>(planes + ((size_t)img * src_np + gq * 4) * h * w);
-    double *ST = states + ((size_t)img * np + gq * 4) * nb * h + (size_t)wv * lay.sp +
-                 (size_t)slot_row(lane) * lay.sr;
+    const float4 *S4 = reinterpret_cast<const float4 *>(planes + pl0);
+    double *ST = states + st0 + (size_t)wv * ly.sp + (size_t)slot_row(lane) * ly.sr;
     const int total = w + 2 * R + PAD;  // steps
     // loader role: the workgroup fetches the chunk's 64 rows x 16 columns as 1024 float4 (all
     // four planes of a pixel), thread t the pixels t, t + 256, ...: 16 consecutive threads read
@@ -288,7 +335,7 @@ __global__ __launch_bounds__(256) void gf_rowstate_kernel(const float *__restric
                     const int c = 8 * hh + c8;
                     s += d[c8];
                     if (((c - PAD - KS + 1) & (kSB - 1)) == 0 && row_ok)
-                        ST[(size_t)((t0 + c - PAD - KS + 1) >> 4) * lay.sb] = s;
+                        ST[(size_t)((t0 + c - PAD - KS + 1) >> 4) * ly.sb] = s;
                 }
             }
 #pragma unroll
@@ -310,7 +357,7 @@ __global__ __launch_bounds__(256) void gf_rowstate_kernel(const float *__restric
                     fifo[tp] = e;
                     const int o = t0 + c - PAD - KS + 1;  // output column of this RowSum
                     if (o >= 0 && (o & (kSB - 1)) == 0 && row_ok)
-                        ST[(size_t)(o >> 4) * lay.sb] = s;
+                        ST[(size_t)(o >> 4) * ly.sb] = s;
                 }
             }
         }
@@ -516,8 +563,10 @@ __global__ __launch_bounds__(128, (R <= 64 ? 2 : 1)) void gf_colwalk_kernel(
     const uint8_t *__restrict__ guide, uint8_t *__restrict__ dst, int h, int w, int nb,
     int n_pairs, int spx, const int *__restrict__ colour, const GfChain xc,
     uint8_t *__restrict__ compact, const GfStateLayout lay, const GfExact xr,
-    uint8_t *__restrict__ compact3, int chan_group, int gcn)
+    uint8_t *__restrict__ compact3, int chan_group, int gcn, const GfRagged rag)
 {
+    // rag.items != nullptr (ragged list: spx = 1, row-walk form): n_pairs = 8 x the items of an XCD's
+    // run, workgroup = one item (image, column block); h, w, nb and the bases come from the image's record
     // gcn: guide bytes per pixel - 3, or 1 for a grey guide that stands for three equal channels
     // (a run-time value, uniform over the launch: one instantiation per radius serves both)
     using G = WalkGeom<R>;
@@ -590,9 +639,30 @@ __global__ __launch_bounds__(128, (R <= 64 ? 2 : 1)) void gf_colwalk_kernel(
         const int pair = (int)(blockIdx.x & 7) * per_xcd + pl;
         if (pl >= per_xcd || pair >= n_pairs)
             return;
-        b = pair % nb;
-        img = pair / nb;
+        if (CHAINED || EXACT || rag.items == nullptr) {
+            b = pair % nb;
+            img = pair / nb;
+        } else {
+            const GfRagItem it = rag.items[pair];
+            if (it.img < 0)
+                return;
+            const GfRagImg *ri = rag.img + it.img;
+            h = ri->h;
+            w = ri->w;
+            nb = ri->nb;
+            b = it.a;
+            // image 0 of a batch that starts at this image's first pixel (one src channel)
+            img = 0;
+            ab += (size_t)ri->px0 * 4;
+            states += (size_t)ri->st0;
+            guide += (size_t)ri->px0 * gcn;
+            dst += (size_t)ri->px0;
+        }
     }
+    // (h is the launch argument or the record's: the empty statement keeps it one plain scalar register
+    //  for what follows - without it the merged value costs the uniform launches a vector register)
+    if constexpr (!CHAINED && !EXACT)
+        asm("" : "+s"(h));
     const bool grey3 = spx == 3 && colour[img] == 0;  // three equal channels: channel 0 stands for all
     if (grey3 && s_ch > 0)
         return;  // (chained: nobody waits for a skipped channel's blocks, its neighbours skip too)
@@ -1073,6 +1143,12 @@ struct GfFusedArgs {
     uint8_t *compact3;  // not the last pass of an iterated call: colour images go here as three planes
     int chan_group;     // column walk: pairs per channel run in an XCD's item order (0: channel fastest)
     int guide_cn;       // guide bytes per pixel: 3, or 1 (RF_GF_GREY_AS_BGR: three equal channels)
+    // ragged list (rf_gf_ragged_u8; rag_rs.items != nullptr): the item records of the row walk and of
+    // the column walk, their counts (the column walk's per XCD) and the list's alpha/beta bytes; m, h,
+    // w, nb are unused
+    GfRagged rag_rs, rag_cw;
+    int rs_items, cw_per_xcd;
+    size_t rag_ab_bytes;
 };
 typedef void (*GfFusedLaunch)(const GfFusedArgs &);
 GfFusedLaunch gf_fused_launcher(int radius);  // nullptr outside 1 .. kGfFusedMaxRadius
@@ -1083,6 +1159,20 @@ void gf_fused_launch(const GfFusedArgs &a)
     const int row_blocks = (a.h + kBRows - 1) / kBRows;
     const int np = 4 * a.src_cn;
     const int pairs = a.m * a.nb;
+    const GfRagged no_rag = {nullptr, nullptr};
+    if (a.rag_rs.items != nullptr) {
+        // ragged list: the two walks over every image's items, on the caller's stream alone
+        const GfExact no_xr = {nullptr, nullptr, nullptr, 0, 0};
+        const int streaming = a.rag_ab_bytes > ((size_t)256 << 20) ? 1 : 0;
+        hipLaunchKernelGGL((gf_rowstate_kernel<R>), dim3((unsigned)a.rs_items), dim3(256), 0, a.stream,
+                           a.ab, a.states, 0, 0, 1, 4, (const int *)nullptr, 4, 0, streaming,
+                           GfStateLayout{0, 0, 1}, no_xr, a.rag_rs);
+        hipLaunchKernelGGL((gf_colwalk_kernel<R>), dim3(8u * (unsigned)a.cw_per_xcd), dim3(128), 0,
+                           a.stream, a.ab, a.states, a.guide, a.dst, 0, 0, 0, 8 * a.cw_per_xcd, 1,
+                           (const int *)nullptr, GfChain{nullptr, nullptr, nullptr}, (uint8_t *)nullptr,
+                           GfStateLayout{0, 0, 1}, no_xr, (uint8_t *)nullptr, 0, a.guide_cn, a.rag_cw);
+        return;
+    }
     if (a.chain.xst != nullptr) {
         // chained column walk: head sums (which also resets the tickets and advances the epoch),
         // then 8 queues of ceil(m / 8) * src_cn * nb tickets each
@@ -1096,7 +1186,7 @@ void gf_fused_launch(const GfFusedArgs &a)
                                    dim3(8u * (unsigned)((a.m + 7) / 8) * a.src_cn * a.nb), dim3(128),
                                    0, a.stream, a.ab, a.states, a.guide, a.dst, a.h, a.w, a.nb, pairs,
                                    a.src_cn, a.colour, a.chain, a.compact, a.lay, GfExact{nullptr, nullptr, nullptr, 0, 0},
-                                   a.compact3, 0, a.guide_cn);
+                                   a.compact3, 0, a.guide_cn, no_rag);
         }
         return;
     }
@@ -1104,7 +1194,7 @@ void gf_fused_launch(const GfFusedArgs &a)
     if (!(a.exp_skip & 2))
         hipLaunchKernelGGL((gf_rowstate_kernel<R>), dim3((unsigned)(a.m * a.src_cn * row_blocks)),
                            dim3(256), 0, a.stream, a.ab, a.states, a.h, a.w, row_blocks, np, a.colour,
-                           np, a.nb, streaming, a.lay, a.xr);
+                           np, a.nb, streaming, a.lay, a.xr, no_rag);
     if (a.exp_skip & 4)
         return;
     // items per XCD: its pairs x channels, rounded up to whole channel runs
@@ -1118,14 +1208,14 @@ void gf_fused_launch(const GfFusedArgs &a)
                                dim3(cw_grid), dim3(128), 0, a.stream,
                                a.ab, a.states, a.guide, a.dst, a.h, a.w, a.nb, pairs, a.src_cn, a.colour,
                                GfChain{nullptr, nullptr, nullptr}, a.compact, a.lay, a.xr, a.compact3, cgrp,
-                               a.guide_cn);
+                               a.guide_cn, no_rag);
             return;
         }
     }
     hipLaunchKernelGGL((gf_colwalk_kernel<R>), dim3(cw_grid),
                        dim3(128), 0, a.stream, a.ab, a.states, a.guide, a.dst, a.h, a.w, a.nb, pairs,
                        a.src_cn, a.colour, GfChain{nullptr, nullptr, nullptr}, a.compact, a.lay, a.xr,
-                       a.compact3, cgrp, a.guide_cn);
+                       a.compact3, cgrp, a.guide_cn, no_rag);
 }
 
 }  // namespace rf

@@ -48,16 +48,6 @@ inline int jbf_check_format(const char *who, int joint_cn, int src_cn, int borde
     return RF_OK;
 }
 
-inline bool stream_is_capturing(hipStream_t stream)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return cs != hipStreamCaptureStatusNone;
-}
-
 // Colour weights exp(i^2 * -0.5 / sigma_color^2) rounded to float, i = 0 .. 256*joint_cn - 1,
 // computed in double with libm's exp like jointBilateralFilter_8u.  Returns the number of entries
 // up to and including the first exact zero (the table is non-increasing: every later entry is 0).

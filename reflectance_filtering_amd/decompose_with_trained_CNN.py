@@ -124,8 +124,9 @@ def decompose_and_filter_list(images, sigma_color=20.0, sigma_spatial=22.0, weig
     [H_i,W_i,3] -> (list of r_u8 [H_i,W_i], list of filtered [H_i,W_i]), each byte for byte what
     decompose_and_filter_batch makes of that photo alone.  The network is per pixel, so the packed
     photos go through it once as one image [1, 1, total pixels, 3]; 'bilateral' then filters the
-    packed grey maps in one ragged call (ops.joint_bilateral_ragged_u8), 'guided' in one batch per
-    group of equal shapes (filter_reflectance.apply_filter_list)."""
+    packed grey maps in one ragged call (ops.joint_bilateral_ragged_u8), 'guided' through
+    filter_reflectance.apply_filter_list: one ragged call (ops.guided_filter_ragged_u8) for photos of
+    more than one shape at int(sigma_spatial) 1..128, else one batch per group of equal shapes."""
     from . import filter_reflectance as fr
     if filter_type not in ("bilateral", "guided"):
         raise ValueError("filter_type must be 'bilateral' or 'guided'.")

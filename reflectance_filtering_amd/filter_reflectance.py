@@ -72,6 +72,33 @@ def apply_filter_batch(filter_type, images, joints, sigma_color, sigma_spatial, 
     return out
 
 
+GF_RAGGED_MAX_RADIUS = 128        # the radii rf_gf_ragged_u8 runs as one launch set (kGfMaxRadiusU8)
+GF_RAGGED_MAX_BYTES = 1 << 30     # src bytes of one ragged guided call (as a shape group's)
+
+
+def guided_ragged_packs(sizes, max_bytes, workspace_cap):
+    """Consecutive runs of a list of (h, w) one-channel images, cut so that a run's bytes stay under
+    max_bytes and the workspace of its ragged guided call under workspace_cap.  The workspace is
+    bounded from above without asking the library: per image its record (48 B), an item record
+    (16 B) per stage-1 workgroup (at most ceil(w / 512) strips x h segments), 64-row block and
+    16-column block (+ 8 of padding), the row states (32 B per 16-column block and row) and
+    alpha/beta (16 B per pixel); 256 B of rounding per call."""
+    packs, cur, cur_bytes, cur_ws = [], [], 0, 256
+    for i, (h, w) in enumerate(sizes):
+        h, w = int(h), int(w)
+        nb = -(-w // 16)
+        ws = 48 + 16 * (-(-w // 512) * h + -(-h // 64) + nb + 8) + 32 * nb * h + 16 * h * w
+        if cur and (cur_bytes + h * w > max_bytes or cur_ws + ws > workspace_cap):
+            packs.append(cur)
+            cur, cur_bytes, cur_ws = [], 0, 256
+        cur.append(i)
+        cur_bytes += h * w
+        cur_ws += ws
+    if cur:
+        packs.append(cur)
+    return packs
+
+
 def _stack(images):
     import torch
     return torch.stack(list(images))
@@ -84,8 +111,11 @@ def apply_filter_list(filter_type, images, joints, sigma_color, sigma_spatial, i
     list of filtered images in the caller's order, each byte for byte what apply_filter_batch
     makes of that image alone.  'bilateral' packs the list and runs it as one ragged call per
     pass (ops.joint_bilateral_ragged_u8), the passes of ``iterations`` > 1 ping-ponging between
-    two packed buffers; 'guided' needs equal shapes and runs one batch per group of equal
-    shapes, wherever its members stand in the list."""
+    two packed buffers.  'guided' with a one-channel list of device tensors of more than one shape and
+    int(sigma_spatial) in 1..128 runs one ragged call for all passes (ops.guided_filter_ragged_u8),
+    a long list in packs of at most 2^30 bytes whose scratch stays under the guided filter's
+    workspace cap; any other guided list runs one batch per group of equal shapes, wherever its
+    members stand in the list."""
     _check_params(filter_type, sigma_color, sigma_spatial)
     if iterations < 1:
         raise ValueError("iterations must be >= 1")
@@ -100,6 +130,20 @@ def apply_filter_list(filter_type, images, joints, sigma_color, sigma_spatial, i
     if not images:
         return []
     torch = _ffi.require_gpu()
+    if (filter_type == "guided" and images[0].shape[2] == 1
+            and 1 <= int(sigma_spatial) <= GF_RAGGED_MAX_RADIUS
+            and len(set(tuple(im.shape[:2]) for im in images)) > 1
+            # the ragged op packs device tensors (ops.pack_images); whatever else a caller hands in
+            # stays with the stacked batches, which say what is wrong with it
+            and all(getattr(t, "is_cuda", False) for t in images + joints)):
+        out = []
+        cap = ops.gf_workspace_cap(images[0].device, torch)
+        for pack in guided_ragged_packs([im.shape[:2] for im in images], GF_RAGGED_MAX_BYTES, cap):
+            srcs = [images[i] for i in pack]
+            out.extend(ops.guided_filter_ragged_u8(srcs if same else [joints[i] for i in pack], srcs,
+                                                   int(sigma_spatial), sigma_color,
+                                                   iterations=iterations, grey_as_bgr=grey_as_bgr)[1])
+        return out
     if filter_type == "guided":
         from .batch import group_by_shape
         # (a flat key: group_by_shape takes its product as the bytes of an item)

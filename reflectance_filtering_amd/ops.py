@@ -13,12 +13,14 @@ _GF_CACHE_BYTES_PER_DEVICE = 64 << 30     # ... and at most this much scratch ke
 _cnn_consts = {}
 _jbf_ragged_workspaces = {}
 _colorize_ragged_workspaces = {}
+_gf_ragged_workspaces = {}
 
 
 def release_workspaces():
-    """Drop the cached guided-filter, ragged-bilateral and ragged-colourise scratch buffers and CNN
-    constants (device memory)."""
+    """Drop the cached guided-filter, ragged-bilateral, ragged-colourise and ragged-guided scratch
+    buffers and CNN constants (device memory)."""
     _gf_workspaces.clear()
+    _gf_ragged_workspaces.clear()
     _jbf_ragged_workspaces.clear()
     _colorize_ragged_workspaces.clear()
     _cnn_consts.clear()
@@ -358,6 +360,54 @@ def guided_filter_u8(guide, src, radius, eps, iterations=1, out=None, workspace=
                       workspace.numel(), _ffi.current_stream_ptr(torch))
     _ffi.check(rc, "rf_gf_u8")
     return out
+
+
+def gf_workspace_cap(device, torch):
+    """The bytes rf_gf_workspace_bytes caps a guided-filter workspace at on `device`: an eighth of its
+    memory, at least 6 and at most 32 GiB."""
+    total = torch.cuda.get_device_properties(device).total_memory
+    return min(max(6 << 30, total // 8), 32 << 30)
+
+
+def guided_filter_ragged_u8(guides, srcs, radius, eps, iterations=1, grey_as_bgr=False, sizes=None,
+                            out=None):
+    """guided_filter_u8 over images of different sizes in one call (rf_gf_ragged_u8: a 1-channel src
+    at radius 1..128 runs stage 1, the row walk and the column walk once per pass over all images;
+    anything else takes one rf_gf_ex_u8 call per image).  guides / srcs: lists of n CUDA uint8 tensors
+    [H_i, W_i, C] (equal C within a list; image i of both has the same H_i, W_i; `guides is srcs`
+    stays one pack: a list that guides itself), or, with sizes = [n,2] (h, w), the images already
+    packed one after another as contiguous CUDA uint8 tensors [total pixels, C].
+    out: the packed result buffer [total pixels, src C], if the caller has one; it may be the packed
+    srcs.  The scratch holds the whole list (18 bytes per pixel and more): a long list is split by
+    the caller (filter_reflectance.apply_filter_list does).
+    Returns (packed result [total pixels, src C], list of its [H_i, W_i, C] views); image i is, byte
+    for byte, guided_filter_u8(guides[i][None], srcs[i][None], ...)[0].  Synchronises the current
+    stream."""
+    flags = _ffi.GF_GREY_AS_BGR if grey_as_bgr else 0
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    guides, srcs, sizes = _packed_pair(guides, srcs, sizes, torch)
+    if sizes.size and sizes.max() >= 2 ** 31:
+        raise ValueError("image too large")
+    if out is None:
+        out = torch.empty_like(srcs)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8
+              and out.is_contiguous() and out.shape == srcs.shape):
+        raise ValueError("out must be a contiguous CUDA uint8 tensor shaped like the packed srcs")
+    n = sizes.shape[0]
+    if n == 0:
+        return out, []
+    hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
+    wds = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
+    need = lib.rf_gf_ragged_workspace_bytes(n, hs.ctypes.data, wds.ctypes.data, guides.shape[1],
+                                            srcs.shape[1], int(radius), flags)
+    ws = _stream_workspace(_gf_ragged_workspaces, need, srcs.device, torch)  # need == 0: the entry says why
+    rc = lib.rf_gf_ragged_u8(guides.data_ptr(), srcs.data_ptr(), out.data_ptr(), n, hs.ctypes.data,
+                             wds.ctypes.data, guides.shape[1], srcs.shape[1], int(radius), float(eps),
+                             int(iterations), flags, ws.data_ptr(), ws.numel(),
+                             _ffi.current_stream_ptr(torch))
+    _ffi.check(rc, "rf_gf_ragged_u8")
+    return out, split_packed(out, sizes)
 
 
 def _cnn_device_consts(torch, device, weights):
