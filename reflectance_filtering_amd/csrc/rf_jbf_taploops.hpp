@@ -499,6 +499,8 @@ __device__ __forceinline__ bool jbf_wave_takes_msad(const uint32_t (&jc)[kPix], 
 // the step within the group), the src byte converted when its texel is at hand for the SAD (two steps
 // before use) so that a texel pair is free for re-use after its second SAD: two pairs still suffice.
 // Same instructions per step, same arithmetic and order: identical bytes.
+// The loop runs two groups of four steps per iteration, the two weight windows in two SGPR octets that swap
+// roles from group to group (RF_L2_ROW_LOOP): no hand-over, one scalar offset for the window loads.
 // SLAB (round 6, jbf_slab_kernel): the loop runs the tap rows i_first .. i_last only - a slab of the disk's
 // rows whose texels are what the LDS tile holds at the moment, tile row of tap row i for the lane's output
 // row = ty + i + row_bias - and ADDS to sum / wsum: slabs taken in increasing i keep every pixel's taps in
@@ -524,7 +526,7 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
     constexpr int Q4 = TLW / 4;
     constexpr int SHIFT = LUTREP == 32 ? 7 : LUTREP == 16 ? 6 : LUTREP == 8 ? 5 : 4;
     static_assert(LUTREP == 32 || LUTREP == 16 || LUTREP == 8 || LUTREP == 4, "LUT replicas");
-    static_assert(Q4 + 1 <= 255, "ds_read2_b32 offsets are 8 bits (the largest one here: Q4 + 1)");
+    static_assert(Q4 + 2 <= 255, "ds_read2_b32 offsets are 8 bits (the largest one here: Q4 + 2)");
     static_assert(TLW % 4 == 0, "column-interleaved planes");
     static_assert(!(MSAD && J1), "the single-channel form has no masked SAD");
     [[maybe_unused]] uint32_t mask = 0x00ffffffu;
@@ -548,6 +550,9 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
         const int phase = (c0 >> 1) & 1;
         ta_out = lane_row0 + (uint32_t)((quad + (phase ? 2 * Q4 : 0)) * 4);
         tb_out = lane_row0 + (uint32_t)((quad + (phase ? 1 : 2 * Q4)) * 4);
+        // (>= r4 + 4 >= 8, and the row's last window starts at float r4 + 3 - hw >= 4 of the table row: the pair
+        //  loop's byte offset `woff` = 4 * index - 32 is never below 0 where a load uses it, see RF_L2_ROW_LOOP;
+        //  a table layout with less than 8 floats in front of a row's first window would break that)
         wa_out = (uint32_t)(ai * sw_len + (r4 + 8) + hws - 4);  // index of the first window's first weight
         ngroups_out = (hws + hw + 4 + 3) >> 2;
     };
@@ -558,9 +563,9 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
     // in 4.2 cycles, tools/microbench/pipe_overlap.hip), and two broadcast ds_read_b128 per group - 2 of
     // the 7 dwords an LDS return carried per step, 5 % of the launch - are gone.  Scalar loads share
     // lgkmcnt with the LDS and return out of order, so the window of the NEXT group, requested in step 0,
-    // needs a full wait: RF_L2_WAIT_WINDOW, placed where it is free.
+    // needs a full wait: RF_L2_MID3, placed where it is free.
     typedef float float8v __attribute__((ext_vector_type(8)));
-    float8v ws8, wn8;    // this group's window, the next group's
+    float8v w8a, w8b;    // the window of this group and that of the next one, in turns (RF_L2_ROW_LOOP)
     float gg[4][kPix];   // gg[u]: LUT values of the group's column u (in flight, then consumed at step u)
     float sv[4];         // sv[u]: src value of column u as float
     uint32_t ta, tb, wa_addr;
@@ -576,9 +581,12 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
     // The half-width of row i + 1 is needed during row i (its last group reads ahead into row i + 1).
     // A load the compiler issues gets its wait - a full one - at the first use, in the middle of a row
     // with four gathers in flight: one pipeline drain per row.  So the value is requested a row early
-    // by hand (hw_ahead, at the top of row i - 1) and taken over at the top of row i: every group has a
-    // full wait in the middle of its step 3 (RF_L2_WAIT_WINDOW), a row at least one group.
-    int hw_ahead;
+    // by hand (hw_ahead, at the top of row i - 1) and taken over for row i by the last group of row i - 1,
+    // behind the full wait that every group has in the middle of its step 3 (hw_cur: an s_mov inside that
+    // statement - a copy the compiler places at the row top instead reads a register whose load is still
+    // in flight along the path of the control-flow graph that skips both forms of the last group, which no
+    // wave takes and the machine-code check of tests/test_cabi.py walks all the same).
+    int hw_ahead, hw_cur;
     {
         const int *hp = SLAB ? hwtab + ((i_lo + 1 < i_hi ? i_lo + 1 : i_hi) + radius) : hwtab + 1;
         asm volatile("s_load_dword %0, %1, 0x0" : "=s"(hw_ahead) : "s"(hp));  // (waited for below)
@@ -591,9 +599,9 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
                  : "v"(ta), "v"(tb), "n"(Q4));
     {
         const float *wp = swsym + wa_addr;
-        asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(ws8) : "s"(wp));
+        asm volatile("s_load_dwordx8 %0, %2, 0x0" : "=&s"(w8a), "=s"(w8b) : "s"(wp));  // (w8b: only defined)
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tp[0]), "+v"(tp[1]), "+s"(ws8));
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tp[0]), "+v"(tp[1]), "+s"(w8a), "+s"(w8b));
 #pragma unroll
     for (int c = 0; c < 2; c++) {
         const uint32_t tx = c == 0 ? tp[0].x : tp[0].y;
@@ -608,208 +616,235 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
         }
         sv[c] = (float)(tx >> 24);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(gg[0][0]), "+v"(gg[0][1]), "+v"(gg[0][2]),
-                   "+v"(gg[0][3]), "+v"(gg[1][0]), "+v"(gg[1][1]), "+v"(gg[1][2]), "+v"(gg[1][3]));
+    // (the statements of the loop name every gather register and src value as in-out operands: those of
+    //  columns 2 and 3 are defined here, without an instruction)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\t"
+                 "s_mov_b32 %[hwc], %[hwa]"
+                 : "+v"(gg[0][0]), "+v"(gg[0][1]), "+v"(gg[0][2]), "+v"(gg[0][3]), "+v"(gg[1][0]),
+                   "+v"(gg[1][1]), "+v"(gg[1][2]), "+v"(gg[1][3]), "=v"(gg[2][0]), "=v"(gg[2][1]),
+                   "=v"(gg[2][2]), "=v"(gg[2][3]), "=v"(gg[3][0]), "=v"(gg[3][1]), "=v"(gg[3][2]),
+                   "=v"(gg[3][3]), "=v"(sv[2]), "=v"(sv[3]), [hwc] "=s"(hw_cur)
+                 : [hwa] "s"(hw_ahead));
 
-#define RF_L2_TQ(U) tp[((U) & 3) >> 1][(U) & 1]
-    // even steps read a texel pair of the NEXT group (or of the next row's first group): step 0 its
-    // columns (0, 1) into tp[0], step 2 its columns (2, 3) into tp[1].  Where a pair sits depends on the
-    // phase of its row: each of the two reads has its own address register (ta: columns (0, 1), tb:
-    // columns (2, 3)), set per row, and the ds_read2 offsets are the same for both phases - one v_add
-    // per group more, and no branch in the loop (at a join the compiler may move registers, and
-    // gathers are in flight at every group end; issuing the read twice under complementary EXEC masks
-    // was measured too: the three EXEC writes per read cost more than the shorter rows return)
-#define RF_L2_TNOUT(U) RF_L2_TNOUT_##U
-#define RF_L2_TNOUT_0 [tn] "=&v"(tp[0]),
-#define RF_L2_TNOUT_2 [tn] "=&v"(tp[1]),
-#define RF_L2_TNOUT_1
-#define RF_L2_TNOUT_3
-#define RF_L2_READ(U) RF_L2_READ_##U
-#define RF_L2_READ_0 "ds_read2_b32 %[tn], %[ta] offset0:%[o0] offset1:%[o1]\n\t"
-#define RF_L2_READ_2 RF_L2_READ_0
-#define RF_L2_READ_1 ""
-#define RF_L2_READ_3 ""
-    // Step U of a group, ONE statement (hipcc puts an s_nop at every boundary between asm statements:
-    // three per step cost 0.5 %): [texel pair]; SADs of column U + 2 interleaved with the weights of column
-    // U (GA = its gathered LUT values); src value of column U + 2; [MID: the group's full wait, step 3];
-    // gather addresses of column U + 2 interleaved with the weight sums of column U; the four gathers
-    // (clustered: an LDS instruction between VALU instructions costs their pairing); accumulation of
-    // column U (its src value converted two steps ago); the wait that leaves this step's four gathers in
-    // flight.  SADn / ADRn: the instruction that forms output n's table index and the one that turns it
-    // into an LDS address (J1: one v_sad_u32 does both).
-#define RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, F, SAD0, SAD1, SAD2, SAD3, ADR0, ADR1,   \
-                     ADR2, ADR3)                                                                 \
-    {                                                                                            \
-        float w0_, w1_, w2_, w3_;                                                                \
-        [[maybe_unused]] uint32_t tj_;                                                           \
-        asm volatile(RF_L2_READ(U)                                                               \
-                     RF_L2_AND_##F                                                               \
-                     SAD0 "v_mul_f32 %[w0], %[wv0], %[g0]\n\t"                                   \
-                     SAD1 "v_mul_f32 %[w1], %[wv1], %[g1]\n\t"                                   \
-                     SAD2 "v_mul_f32 %[w2], %[wv2], %[g2]\n\t"                                   \
-                     SAD3 "v_mul_f32 %[w3], %[wv3], %[g3]\n\t"                                   \
-                     "v_cvt_f32_ubyte3 %[s2], %[t2]\n\t"                                         \
-                     MID                                                                         \
-                     ADR0 "v_add_f32 %[ws0], %[ws0], %[w0]\n\t"                                  \
-                     ADR1 "v_add_f32 %[ws1], %[ws1], %[w1]\n\t"                                  \
-                     ADR2 "v_add_f32 %[ws2], %[ws2], %[w2]\n\t"                                  \
-                     ADR3 "v_add_f32 %[ws3], %[ws3], %[w3]\n\t"                                  \
-                     "ds_read_b32 %[a0], %[a0]\n\t"                                              \
-                     "ds_read_b32 %[a1], %[a1]\n\t"                                              \
-                     "ds_read_b32 %[a2], %[a2]\n\t"                                              \
-                     "ds_read_b32 %[a3], %[a3]\n\t"                                              \
-                     "v_mul_f32 %[w0], %[w0], %[s]\n\t"                                          \
-                     "v_mul_f32 %[w1], %[w1], %[s]\n\t"                                          \
-                     "v_mul_f32 %[w2], %[w2], %[s]\n\t"                                          \
-                     "v_mul_f32 %[w3], %[w3], %[s]\n\t"                                          \
-                     "v_add_f32 %[s0], %[s0], %[w0]\n\t"                                         \
-                     "v_add_f32 %[s1], %[s1], %[w1]\n\t"                                         \
-                     "v_add_f32 %[s2_], %[s2_], %[w2]\n\t"                                       \
-                     "v_add_f32 %[s3], %[s3], %[w3]\n\t"                                         \
-                     WAITTXT                                                                     \
-                     : RF_L2_TNOUT(U) RF_L2_TJOUT_##F [a0] "=&v"(GB[0]), [a1] "=&v"(GB[1]),      \
-                       [a2] "=&v"(GB[2]), [a3] "=&v"(GB[3]), [w0] "=&v"(w0_), [w1] "=&v"(w1_),   \
-                       [w2] "=&v"(w2_), [w3] "=&v"(w3_), [s2] "=&v"(sv[((U) + 2) & 3]),          \
-                       [ws0] "+v"(wsum[0]), [ws1] "+v"(wsum[1]), [ws2] "+v"(wsum[2]),            \
-                       [ws3] "+v"(wsum[3]), [s0] "+v"(sum[0][0]), [s1] "+v"(sum[1][0]),          \
-                       [s2_] "+v"(sum[2][0]), [s3] "+v"(sum[3][0])                               \
-                     : [ta] "v"(TA), [o0] "n"(O0), [o1] "n"(O1), RF_L2_MASKIN_##F                \
-                       [t2] "v"(RF_L2_TQ((U) + 2)), [jc0] "v"(jc[0]), [jc1] "v"(jc[1]),          \
-                       [jc2] "v"(jc[2]), [jc3] "v"(jc[3]), [wv0] "s"(wv[4 - (U)]),               \
-                       [wv1] "s"(wv[5 - (U)]), [wv2] "s"(wv[6 - (U)]), [wv3] "s"(wv[7 - (U)]),   \
-                       [g0] "v"(GA[0]), [g1] "v"(GA[1]), [g2] "v"(GA[2]), [g3] "v"(GA[3]),       \
-                       [sh] "n"(SHIFT), [la] "v"(lut_lane_addr), [s] "v"(sv[(U)]));              \
-    }
-    // F = AND: the joint bytes of the tap texel masked into tj first; F = MSAD: no such instruction, no
-    // tj and no mask operand - the masked SAD takes the texel itself (S0) against the centre (S1)
-#define RF_L2_AND_AND "v_and_b32 %[tj], %[mask], %[t2]\n\t"
-#define RF_L2_AND_MSAD
+    // Two column steps - half a group - are ONE statement (hipcc puts an s_nop at every boundary between
+    // asm statements that it has nothing else to put at: one statement per step cost 0.5 % against three,
+    // round 5).  A half starts with the read of a texel pair of the NEXT group (or of the next row's first
+    // group): half 0 its columns (0, 1) into tp[0], half 1 its columns (2, 3) into tp[1] - the pair lands
+    // in a 64-bit register whose halves the SADs of the OTHER half take as operands of their own, which is
+    // why a whole group cannot be one statement.  Where a pair sits depends on the phase of its row: each
+    // of the two reads has its own address register (ta: columns (0, 1), tb: columns (2, 3)), set per row,
+    // and the ds_read2 offsets are the same for both phases - no branch in the loop (issuing the read
+    // twice under complementary EXEC masks was measured too: the three EXEC writes per read cost more
+    // than the shorter rows return).
+    // Step X (a: the even one of the half, b: the odd one) of column U: SADs of column U + 2 interleaved
+    // with the weights of column U (g: its gathered LUT values); src value of column U + 2; [MID: the
+    // group's full wait, step 3]; gather addresses of column U + 2 interleaved with the weight sums of
+    // column U; the four gathers (clustered: an LDS instruction between VALU instructions costs their
+    // pairing); accumulation of column U (its src value converted two steps ago); the wait that leaves this
+    // step's four gathers in flight.  F = AND: the joint bytes of the tap texel masked into tj first;
+    // F = MSAD: no such instruction, no tj and no mask operand - the masked SAD takes the texel itself (S0)
+    // against the centre (S1); F = J1: one v_sad_u32 forms the table index and the LDS address at once.
+#define RF_L2_PRE_AND(X) "v_and_b32 %[tj], %[mask], %[t2" X "]\n\t"
+#define RF_L2_PRE_MSAD(X)
+#define RF_L2_PRE_J1(X) RF_L2_PRE_AND(X)
+#define RF_L2_SAD_AND(X, N) "v_sad_u8 %[a" X #N "], %[tj], %[jc" #N "], 0\n\t"
+#define RF_L2_SAD_MSAD(X, N) "v_msad_u8 %[a" X #N "], %[t2" X "], %[jc" #N "], 0\n\t"
+#define RF_L2_SAD_J1(X, N) "v_sad_u32 %[a" X #N "], %[tj], %[jc" #N "], %[la]\n\t"
+#define RF_L2_ADR_AND(X, N) "v_lshl_add_u32 %[a" X #N "], %[a" X #N "], %[sh], %[la]\n\t"
+#define RF_L2_ADR_MSAD(X, N) RF_L2_ADR_AND(X, N)
+#define RF_L2_ADR_J1(X, N)
 #define RF_L2_TJOUT_AND [tj] "=&v"(tj_),
 #define RF_L2_TJOUT_MSAD
+#define RF_L2_TJOUT_J1 RF_L2_TJOUT_AND
 #define RF_L2_MASKIN_AND [mask] "v"(mask),
 #define RF_L2_MASKIN_MSAD
-#define RF_L2_ADR(N) "v_lshl_add_u32 %[a" #N "], %[a" #N "], %[sh], %[la]\n\t"
-#define RF_L2_STEP(U, GA, GB, TA, O0, O1, MID, WAITTXT)                                           \
-    RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, AND, "v_sad_u8 %[a0], %[tj], %[jc0], 0\n\t", \
-                 "v_sad_u8 %[a1], %[tj], %[jc1], 0\n\t", "v_sad_u8 %[a2], %[tj], %[jc2], 0\n\t",  \
-                 "v_sad_u8 %[a3], %[tj], %[jc3], 0\n\t", RF_L2_ADR(0), RF_L2_ADR(1), RF_L2_ADR(2), \
-                 RF_L2_ADR(3))
-#define RF_L2_STEP_MSAD(U, GA, GB, TA, O0, O1, MID, WAITTXT)                                      \
-    RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, MSAD,                                       \
-                 "v_msad_u8 %[a0], %[t2], %[jc0], 0\n\t", "v_msad_u8 %[a1], %[t2], %[jc1], 0\n\t", \
-                 "v_msad_u8 %[a2], %[t2], %[jc2], 0\n\t", "v_msad_u8 %[a3], %[t2], %[jc3], 0\n\t", \
-                 RF_L2_ADR(0), RF_L2_ADR(1), RF_L2_ADR(2), RF_L2_ADR(3))
-#define RF_L2_STEP_J1(U, GA, GB, TA, O0, O1, MID, WAITTXT)                                        \
-    RF_L2_STEP_X(U, GA, GB, TA, O0, O1, MID, WAITTXT, AND,                                        \
-                 "v_sad_u32 %[a0], %[tj], %[jc0], %[la]\n\t",                                    \
-                 "v_sad_u32 %[a1], %[tj], %[jc1], %[la]\n\t",                                    \
-                 "v_sad_u32 %[a2], %[tj], %[jc2], %[la]\n\t",                                    \
-                 "v_sad_u32 %[a3], %[tj], %[jc3], %[la]\n\t", "", "", "", "")
+#define RF_L2_MASKIN_J1 RF_L2_MASKIN_AND
+#define RF_L2_WMUL(X, N) "v_mul_f32 %[w" #N "], %[wv" X #N "], %[g" X #N "]\n\t"
+#define RF_L2_WADD(N) "v_add_f32 %[ws" #N "], %[ws" #N "], %[w" #N "]\n\t"
+#define RF_L2_SMUL(X, N) "v_mul_f32 %[w" #N "], %[w" #N "], %[s" X "]\n\t"
+#define RF_L2_SADD(N) "v_add_f32 %[s" #N "], %[s" #N "], %[w" #N "]\n\t"
+#define RF_L2_GATHER(X, N) "ds_read_b32 %[a" X #N "], %[a" X #N "]\n\t"
+#define RF_L2_STEP_TXT(F, X, MID, WAITTXT)                                                                       \
+    RF_L2_PRE_##F(X)                                                                                             \
+    RF_L2_SAD_##F(X, 0) RF_L2_WMUL(X, 0)                                                                         \
+    RF_L2_SAD_##F(X, 1) RF_L2_WMUL(X, 1)                                                                         \
+    RF_L2_SAD_##F(X, 2) RF_L2_WMUL(X, 2)                                                                         \
+    RF_L2_SAD_##F(X, 3) RF_L2_WMUL(X, 3)                                                                         \
+    "v_cvt_f32_ubyte3 %[s2" X "], %[t2" X "]\n\t"                                                                \
+    MID                                                                                                          \
+    RF_L2_ADR_##F(X, 0) RF_L2_WADD(0)                                                                            \
+    RF_L2_ADR_##F(X, 1) RF_L2_WADD(1)                                                                            \
+    RF_L2_ADR_##F(X, 2) RF_L2_WADD(2)                                                                            \
+    RF_L2_ADR_##F(X, 3) RF_L2_WADD(3)                                                                            \
+    RF_L2_GATHER(X, 0) RF_L2_GATHER(X, 1) RF_L2_GATHER(X, 2) RF_L2_GATHER(X, 3)                                  \
+    RF_L2_SMUL(X, 0) RF_L2_SMUL(X, 1) RF_L2_SMUL(X, 2) RF_L2_SMUL(X, 3)                                          \
+    RF_L2_SADD(0) RF_L2_SADD(1) RF_L2_SADD(2) RF_L2_SADD(3)                                                      \
+    WAITTXT
+    // Half H of a group (steps 2 H and 2 H + 1).  WC = the octet that holds the group's window, WN = the
+    // one the next group's window is loaded into - both are in-out operands of EVERY statement, so that
+    // on every path each of the two C++ variables is only ever the output of a statement of this loop
+    // (where an SGPR tuple written by an asm statement meets a value of another origin at a join, the
+    // backend merges them in VGPRs and cannot give the result back to an "s" operand).  Half 0 starts with
+    // the load of the next window: a scalar load of 8 floats from the table in global memory (scalar
+    // cache), address = table + WOFF (an SGPR byte offset) + WIMM.
+#define RF_L2_MID3 "s_waitcnt lgkmcnt(0)\n\t"
+#define RF_L2_MID3_LAST "s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %[hwc], %[hwa]\n\t"
+#define RF_L2_WLOAD_0 "s_load_dwordx8 %[wn], %[wb], %[wo] offset:%[wi]\n\t"
+#define RF_L2_WLOAD_1
+#define RF_L2_HALF(F, H, WC, WN, TA, O0, O1, WOFF, WIMM, MIDB)                                                   \
+    {                                                                                                            \
+        float w0_, w1_, w2_, w3_;                                                                                \
+        [[maybe_unused]] uint32_t tj_;                                                                           \
+        asm volatile(RF_L2_WLOAD_##H                                                                             \
+                     "ds_read2_b32 %[tn], %[ta] offset0:%[o0] offset1:%[o1]\n\t"                                 \
+                     RF_L2_STEP_TXT(F, "a", "", "s_waitcnt lgkmcnt(4)\n\t")                                      \
+                     RF_L2_STEP_TXT(F, "b", MIDB, "s_waitcnt lgkmcnt(4)")                                        \
+                     : [tn] "=&v"(tp[H]), RF_L2_TJOUT_##F                                                        \
+                       [aa0] "+v"(gg[(2 * (H) + 2) & 3][0]), [aa1] "+v"(gg[(2 * (H) + 2) & 3][1]),               \
+                       [aa2] "+v"(gg[(2 * (H) + 2) & 3][2]), [aa3] "+v"(gg[(2 * (H) + 2) & 3][3]),               \
+                       [ab0] "+v"(gg[(2 * (H) + 3) & 3][0]), [ab1] "+v"(gg[(2 * (H) + 3) & 3][1]),               \
+                       [ab2] "+v"(gg[(2 * (H) + 3) & 3][2]), [ab3] "+v"(gg[(2 * (H) + 3) & 3][3]),               \
+                       [ga0] "+v"(gg[2 * (H)][0]), [ga1] "+v"(gg[2 * (H)][1]),                                   \
+                       [ga2] "+v"(gg[2 * (H)][2]), [ga3] "+v"(gg[2 * (H)][3]),                                   \
+                       [gb0] "+v"(gg[2 * (H) + 1][0]), [gb1] "+v"(gg[2 * (H) + 1][1]),                           \
+                       [gb2] "+v"(gg[2 * (H) + 1][2]), [gb3] "+v"(gg[2 * (H) + 1][3]),                           \
+                       [w0] "=&v"(w0_), [w1] "=&v"(w1_), [w2] "=&v"(w2_), [w3] "=&v"(w3_),                       \
+                       [s2a] "=&v"(sv[(2 * (H) + 2) & 3]), [s2b] "=&v"(sv[(2 * (H) + 3) & 3]),                   \
+                       [ws0] "+v"(wsum[0]), [ws1] "+v"(wsum[1]), [ws2] "+v"(wsum[2]),                            \
+                       [ws3] "+v"(wsum[3]), [s0] "+v"(sum[0][0]), [s1] "+v"(sum[1][0]),                          \
+                       [s2] "+v"(sum[2][0]), [s3] "+v"(sum[3][0]), [wc] "+s"(WC), [wn] "+s"(WN),                 \
+                       [hwc] "+s"(hw_cur)                                                                        \
+                     : [ta] "v"(TA), [o0] "n"(O0), [o1] "n"(O1), RF_L2_MASKIN_##F                                \
+                       [t2a] "v"(tp[1 - (H)][0]), [t2b] "v"(tp[1 - (H)][1]), [jc0] "v"(jc[0]),                   \
+                       [jc1] "v"(jc[1]), [jc2] "v"(jc[2]), [jc3] "v"(jc[3]),                                     \
+                       [wva0] "s"(WC[4 - 2 * (H)]), [wva1] "s"(WC[5 - 2 * (H)]),                                 \
+                       [wva2] "s"(WC[6 - 2 * (H)]), [wva3] "s"(WC[7 - 2 * (H)]),                                 \
+                       [wvb0] "s"(WC[3 - 2 * (H)]), [wvb1] "s"(WC[4 - 2 * (H)]),                                 \
+                       [wvb2] "s"(WC[5 - 2 * (H)]), [wvb3] "s"(WC[6 - 2 * (H)]),                                 \
+                       [sh] "n"(SHIFT), [la] "v"(lut_lane_addr), [sa] "v"(sv[2 * (H)]),                          \
+                       [sb] "v"(sv[2 * (H) + 1]), [wb] "s"(swsym), [wo] "s"(WOFF),                               \
+                       [wi] "n"(WIMM), [hwa] "s"(hw_ahead));                                                     \
+    }
     // (The last step of a row waits like any other: four gathers stay in flight across the row loop's
     //  back edge, where the compiler writes code of its own - the next row's addresses.  That it moves
     //  none of the registers in flight there is checked on the machine code, along every path of the
     //  control-flow graph: tests/test_cabi.py.  A variant of this loop once got such a v_mov; a full wait
     //  at the row end, which this loop had until the check walked branches, costs 0.3 %.)
-    // the window changes hands after the group: the empty statement is ordered behind step 3 and its full
-    // wait (both are volatile) and keeps the copy behind itself.  (Load and hand-over are statements of
-    // their own, outside any branch: where an SGPR tuple written by an asm statement meets a value of
-    // another origin at a join, the backend merges them in VGPRs and cannot give the result back to an
-    // "s" operand.)
-#define RF_L2_HAND_OVER                                                                          \
-    asm volatile("" : "+s"(wn8));                                                                \
-    ws8 = wn8;
-    // the next group's window: a scalar load of 8 floats from the table in global memory (scalar cache)
-#define RF_L2_LOAD_WINDOW(IDX)                                                                   \
-    {                                                                                            \
-        const float *wp_ = swsym + (IDX);                                                        \
-        asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(wn8) : "s"(wp_));                      \
-    }
-    // one group of four steps; NA / NB = address registers of the texel pairs read ahead (this row's next
+    // One group of four steps; NA / NB = address registers of the texel pairs read ahead (this row's next
     // group or the next row's first one), PA / PB their ds_read2 offsets; the group's full wait - for the
-    // weight window requested before step 0 - sits in the middle of step 3, where nothing is in flight but
-    // the gathers of step 2, a whole step old (step 3 reads no texel pair)
-#define RF_L2_GROUP(STEP, NA, NB, PA, PB)                                                         \
-    {                                                                                            \
-        STEP(0, gg[0], gg[2], NA, PA, PB, "", "s_waitcnt lgkmcnt(4)")                            \
-        STEP(1, gg[1], gg[3], NA, 0, 0, "", "s_waitcnt lgkmcnt(4)")                              \
-        STEP(2, gg[2], gg[0], NB, PA, PB, "", "s_waitcnt lgkmcnt(4)")                            \
-        STEP(3, gg[3], gg[1], NB, 0, 0, "s_waitcnt lgkmcnt(0)\n\t", "s_waitcnt lgkmcnt(4)")      \
+    // weight window requested at its top - sits in the middle of step 3, where nothing is in flight but
+    // the gathers of step 2, a whole step old (step 3 reads no texel pair).
+#define RF_L2_GROUP(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM, MID3)                                                 \
+    RF_L2_HALF(F, 0, WC, WN, NA, PA, PB, WOFF, WIMM, "")                                                         \
+    RF_L2_HALF(F, 1, WC, WN, NB, PA, PB, WOFF, WIMM, MID3)
+    // The two octets swap roles from group to group: a group in role A multiplies from w8a and loads the
+    // next window into w8b, one in role B the other way round - no copy hands the window on.  Which octet
+    // holds the current window is a state of the control flow (`in_b`, tested once per row): the loop body
+    // is a PAIR of groups, A then B, a row that starts in role B runs one lone B group first, and the last
+    // group of a row - the one that reads ahead into the next row through ta_next / tb_next and loads its
+    // first window - exists in both roles, so rows with an odd number of groups need neither a padding
+    // group nor a copy and the next row simply starts in the other role.  Inside a pair the second group's
+    // ds_read2 offsets are the first group's plus one dword and ta / tb advance once, by 8 bytes.  The
+    // windows of a row descend by 16 bytes per group: woff = byte offset of the current window - 32, one
+    // s_sub per pair; the loads take woff + 16 and woff + 0 (never below 0 where used: a row's last
+    // window starts at float r4 + 3 - hw >= 4 of its table row).
+#define RF_L2_ROW_LOOP(F)                                                                                        \
+    for (int i = i_lo; i <= i_hi; i++) {                                                                         \
+        uint32_t ta_next, tb_next, wa_next;                                                                      \
+        int ngroups_next;                                                                                        \
+        row_addr(i < i_hi ? i + 1 : i, __builtin_amdgcn_readfirstlane(hw_cur), ta_next,                          \
+                 tb_next, wa_next, ngroups_next);                                                                \
+        {                                                                                                        \
+            const int *hp_ = hwtab + ((i + 2 < i_hi ? i + 2 : i_hi) + radius);                                   \
+            /* (in-out: the register stays hw_ahead's from row to row - a register that is free at               \
+                the row top the compiler takes for that row's address arithmetic, and the machine-code           \
+                check sees the load of the row before still in flight there along the path that skips            \
+                both forms of the last group) */                                                                 \
+            asm volatile("s_load_dword %0, %1, 0x0" : "+s"(hw_ahead) : "s"(hp_));                                \
+        }                                                                                                        \
+        const uint32_t woff_next = wa_next * 4u;                                                                 \
+        int m = ngroups - 1; /* groups before the row's last one */                                              \
+        const int b_first = in_b;                                                                                \
+        const int single_b = b_first & (int)(m == 0);                                                            \
+        if (!single_b) {                                                                                         \
+            if (b_first) {                                                                                       \
+                RF_L2_GROUP(F, w8b, w8a, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                \
+                ta += 4;                                                                                         \
+                tb += 4;                                                                                         \
+                woff -= 16;                                                                                      \
+                m--;                                                                                             \
+            }                                                                                                    \
+            for (int k = m >> 1; k > 0; k--) {                                                                   \
+                RF_L2_GROUP(F, w8a, w8b, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                \
+                RF_L2_GROUP(F, w8b, w8a, ta, tb, 2, Q4 + 2, woff, 0, RF_L2_MID3)                                 \
+                ta += 8;                                                                                         \
+                tb += 8;                                                                                         \
+                woff -= 32;                                                                                      \
+            }                                                                                                    \
+            if (m & 1) {                                                                                         \
+                RF_L2_GROUP(F, w8a, w8b, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                \
+            }                                                                                                    \
+        }                                                                                                        \
+        /* (two ifs, the second one on a value the compiler cannot see through: an if / else with a              \
+            statement of this loop in either arm is structurized into two ifs with the state BEFORE the          \
+            first arm kept alive for the second, which costs a copy of every register of the loop) */            \
+        int last_a = ((single_b | m) & 1) ^ 1;                                                                   \
+        if (!last_a) {                                                                                           \
+            RF_L2_GROUP(F, w8b, w8a, ta_next, tb_next, 0, Q4, woff_next, 0, RF_L2_MID3_LAST)                     \
+        }                                                                                                        \
+        asm volatile("" : "+s"(last_a));                                                                         \
+        in_b = __builtin_amdgcn_readfirstlane(last_a);                                                           \
+        if (in_b) {                                                                                              \
+            RF_L2_GROUP(F, w8a, w8b, ta_next, tb_next, 0, Q4, woff_next, 0, RF_L2_MID3_LAST)                     \
+        }                                                                                                        \
+        ta = ta_next;                                                                                            \
+        tb = tb_next;                                                                                            \
+        woff = woff_next - 32u;                                                                                  \
+        ngroups = ngroups_next;                                                                                  \
     }
-#define RF_L2_ROW_LOOP(STEP)                                                                      \
-    for (int i = i_lo; i <= i_hi; i++) {                                                          \
-        uint32_t ta_next, tb_next, wa_next;                                                       \
-        int ngroups_next;                                                                         \
-        asm volatile("" : "+s"(hw_ahead)); /* behind the full waits of the row before */           \
-        row_addr(i < i_hi ? i + 1 : i, __builtin_amdgcn_readfirstlane(hw_ahead), ta_next,         \
-                 tb_next, wa_next, ngroups_next);                                                 \
-        {                                                                                         \
-            const int *hp_ = hwtab + ((i + 2 < i_hi ? i + 2 : i_hi) + radius);                    \
-            asm volatile("s_load_dword %0, %1, 0x0" : "=s"(hw_ahead) : "s"(hp_));                 \
-        }                                                                                         \
-        for (int gq = 0; gq < ngroups - 1; gq++) {                                                \
-            float wv[8];                                                                          \
-            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];                       \
-            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];                       \
-            wa_addr -= 4;                                                                         \
-            RF_L2_LOAD_WINDOW(wa_addr)                                                            \
-            RF_L2_GROUP(STEP, ta, tb, 1, Q4 + 1)                                                 \
-            RF_L2_HAND_OVER                                                                       \
-            ta += 4;                                                                              \
-            tb += 4;                                                                              \
-        }                                                                                         \
-        {                                                                                         \
-            float wv[8];                                                                          \
-            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];                       \
-            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];                       \
-            RF_L2_LOAD_WINDOW(wa_next)                                                            \
-            RF_L2_GROUP(STEP, ta_next, tb_next, 0, Q4)                                           \
-            RF_L2_HAND_OVER                                                                       \
-        }                                                                                         \
-        ta = ta_next;                                                                             \
-        wa_addr = wa_next;                                                                        \
-        ngroups = ngroups_next;                                                                   \
-        tb = tb_next;                                                                             \
-    }
+    int in_b = 0;  // the prologue loaded the first window into w8a
+    uint32_t woff = wa_addr * 4u - 32u;
     if constexpr (J1) {
-        RF_L2_ROW_LOOP(RF_L2_STEP_J1)
+        RF_L2_ROW_LOOP(J1)
     } else if constexpr (MSAD) {
-        RF_L2_ROW_LOOP(RF_L2_STEP_MSAD)
+        RF_L2_ROW_LOOP(MSAD)
     } else {
-        RF_L2_ROW_LOOP(RF_L2_STEP)
+        RF_L2_ROW_LOOP(AND)
     }
     // the last steps' gathers (of a row that does not exist) are still in flight: nothing may re-use
     // their registers before they have landed
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(gg[0][0]), "+v"(gg[0][1]), "+v"(gg[0][2]), "+v"(gg[0][3]), "+v"(gg[1][0]),
                    "+v"(gg[1][1]), "+v"(gg[1][2]), "+v"(gg[1][3]), "+v"(tp[0]), "+v"(tp[1]),
-                   "+s"(ws8), "+s"(wn8), "+s"(hw_ahead));
+                   "+s"(w8a), "+s"(w8b), "+s"(hw_ahead));
 #undef RF_L2_ROW_LOOP
 #undef RF_L2_GROUP
-#undef RF_L2_LOAD_WINDOW
-#undef RF_L2_HAND_OVER
-#undef RF_L2_STEP_J1
-#undef RF_L2_STEP_MSAD
-#undef RF_L2_STEP
-#undef RF_L2_ADR
-#undef RF_L2_AND_AND
-#undef RF_L2_AND_MSAD
-#undef RF_L2_TJOUT_AND
-#undef RF_L2_TJOUT_MSAD
-#undef RF_L2_MASKIN_AND
+#undef RF_L2_HALF
+#undef RF_L2_WLOAD_0
+#undef RF_L2_MID3
+#undef RF_L2_MID3_LAST
+#undef RF_L2_WLOAD_1
+#undef RF_L2_STEP_TXT
+#undef RF_L2_GATHER
+#undef RF_L2_SADD
+#undef RF_L2_SMUL
+#undef RF_L2_WADD
+#undef RF_L2_WMUL
+#undef RF_L2_MASKIN_J1
 #undef RF_L2_MASKIN_MSAD
-#undef RF_L2_STEP_X
-#undef RF_L2_READ
-#undef RF_L2_READ_0
-#undef RF_L2_READ_1
-#undef RF_L2_READ_2
-#undef RF_L2_READ_3
-#undef RF_L2_TNOUT
-#undef RF_L2_TNOUT_0
-#undef RF_L2_TNOUT_1
-#undef RF_L2_TNOUT_2
-#undef RF_L2_TNOUT_3
-#undef RF_L2_TQ
+#undef RF_L2_MASKIN_AND
+#undef RF_L2_TJOUT_J1
+#undef RF_L2_TJOUT_MSAD
+#undef RF_L2_TJOUT_AND
+#undef RF_L2_ADR_J1
+#undef RF_L2_ADR_MSAD
+#undef RF_L2_ADR_AND
+#undef RF_L2_SAD_J1
+#undef RF_L2_SAD_MSAD
+#undef RF_L2_SAD_AND
+#undef RF_L2_PRE_J1
+#undef RF_L2_PRE_MSAD
+#undef RF_L2_PRE_AND
 }
 
 // Hand-scheduled tap loop for colour tiles with 6-byte texels (main plane {B,G,R joint, B src},
