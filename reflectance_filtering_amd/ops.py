@@ -410,6 +410,34 @@ def guided_filter_ragged_u8(guides, srcs, radius, eps, iterations=1, grey_as_bgr
     return out, split_packed(out, sizes)
 
 
+def guided_filter_ragged_sweep_u8(guides, srcs, radius, eps_list, grey_as_bgr=False, sizes=None, out=None):
+    """guided_filter_ragged_u8 for several eps at one radius (the guided half of a parameter sweep): the
+    list is packed and checked once and filtered by one rf_gf_ragged_u8 call per eps.  (A stage 1 shared
+    by the eps of a radius was built and measured: it did not beat these calls by more than the
+    run-to-run spread of a sweep and was taken out - DESIGN.md 3.2.)  guides / srcs / sizes: as
+    guided_filter_ragged_u8.  out: the result buffer [n_eps, total pixels, src C], if the caller has
+    one; it must not overlap the packed srcs.
+    Returns CUDA uint8 [n_eps, total pixels, src C]; slice e is, byte for byte, the packed result of
+    guided_filter_ragged_u8(guides, srcs, radius, eps_list[e]).  Synchronises the current stream."""
+    torch = _ffi.require_gpu()
+    guides, srcs, sizes = _packed_pair(guides, srcs, sizes, torch)
+    eps = np.ascontiguousarray(eps_list, dtype=np.float64).ravel()
+    shape = (eps.shape[0],) + tuple(srcs.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=srcs.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8
+              and out.is_contiguous() and tuple(out.shape) == shape):
+        raise ValueError("out must be a contiguous CUDA uint8 tensor [n_eps, total pixels, src C]")
+    nbytes = srcs.numel()
+    if eps.shape[0] and nbytes and out.data_ptr() < srcs.data_ptr() + nbytes \
+            and srcs.data_ptr() < out.data_ptr() + eps.shape[0] * nbytes:
+        raise ValueError("out must not overlap srcs: every eps reads them again")
+    for e in range(eps.shape[0]):
+        guided_filter_ragged_u8(guides, srcs, radius, float(eps[e]), grey_as_bgr=grey_as_bgr, sizes=sizes,
+                                out=out[e])
+    return out
+
+
 def _cnn_device_consts(torch, device, weights):
     """(packed weights, sRGB table) on `device`.  Packing is the net-load step
     (rf_cnn_pack_weights): done once for the shipped weights (cached per device), once per call

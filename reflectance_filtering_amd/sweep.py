@@ -10,7 +10,8 @@ Each photo `<stem>.png` comes with IIW judgements `<stem>.json` beside it.  The 
 reflectance bytes (`<stem>-r.png` of decompose_with_trained_CNN); the grid is the outer product
 of the two sigma lists; every pair filters the prediction and scores it with WHDR
 (the bilateral filter evaluated at the judgement points only, all photos of whatever sizes in one
-ragged call per pack of 2^30 pixels; the guided filter in full passes over equal-size batches).  --guidance cnn filters the prediction with itself as guidance (BF/GF(CNN, CNN),
+ragged call per pack of 2^30 pixels; the guided filter in full passes, all photos of a pack in one
+ragged call per pair).  --guidance cnn filters the prediction with itself as guidance (BF/GF(CNN, CNN),
 the bytes of decompose_and_filter_batch), --guidance image with the photo (the reference
 README's example call).  The JSON holds the grid, the mean WHDR per pair over the images that
 have judgements, the best pair and the image count; the npz the per-image matrix.
@@ -60,7 +61,7 @@ def run(photos, filter_type, sigma_color, sigma_spatial, guidance="cnn", delta=0
     """The sweep over a list of photo files: returns (pairs [P,2], per_image float64 [P,N],
     has_judgements bool [N])."""
     import torch
-    from . import batch, ops, whdr
+    from . import ops, whdr
     from . import image_utils as iu
     pairs = grid_pairs(sigma_color, sigma_spatial)
     images, comps = [], []
@@ -93,18 +94,27 @@ def run(photos, filter_type, sigma_color, sigma_spatial, guidance="cnn", delta=0
                 res = whdr.sweep_packed(r1, bgr, psizes, joined, pairs, delta)
             per_image[:, pack] = res
         return pairs, per_image, np.array([c.shape[0] > 0 for c in comps], dtype=bool)
-    # guided: full passes need equal shapes, batched wherever they stand in the list
-    order = sorted(range(len(photos)), key=lambda i: images[i].shape)
-    for run_ in batch.group_by_shape(order, lambda i: images[i].shape):
-        bgr = torch.from_numpy(np.stack([images[i] for i in run_])).cuda()
-        _, r8 = ops.cnn_reflectance_u8(bgr, want_float=False)
-        r1 = r8.unsqueeze(-1)
+    # guided: full passes.  The photos of a pack - whatever their sizes - go through the network as
+    # one image [1, 1, total pixels, 3], like the bilateral branch, and the packed bytes go to the
+    # ragged guided filter (whdr.sweep_guided_packed: one ragged call per distinct pair; a radius
+    # outside 1..128 falls back inside the entry, to the same bytes).
+    from . import filter_reflectance as fr
+    sizes = [img.shape[:2] for img in images]
+    dedup = [whdr.dedup_points([c], h, w) for c, (h, w) in zip(comps, sizes)]
+    cap = ops.gf_workspace_cap(torch.device("cuda", torch.cuda.current_device()), torch)
+    for pack in fr.guided_ragged_packs(sizes, fr.GF_RAGGED_MAX_BYTES, cap):
+        joined = whdr.join_dedup([dedup[i] for i in pack])
+        if joined[2].shape[0] == 0:
+            continue
+        bgr = torch.from_numpy(np.concatenate([images[i].reshape(-1, 3) for i in pack])).cuda()
+        _, r8 = ops.cnn_reflectance_u8(bgr.view(1, 1, -1, 3), want_float=False)
+        r1 = r8.view(-1, 1)
+        psizes = [sizes[i] for i in pack]
         if guidance == "cnn":
-            res = whdr.sweep(filter_type, r1, r1, [comps[i] for i in run_], pairs, delta=delta,
-                             grey_as_bgr=True)
+            res = whdr.sweep_guided_packed(r1, r1, psizes, joined, pairs, delta, grey_as_bgr=True)
         else:
-            res = whdr.sweep(filter_type, r1, bgr, [comps[i] for i in run_], pairs, delta=delta)
-        per_image[:, run_] = res
+            res = whdr.sweep_guided_packed(r1, bgr, psizes, joined, pairs, delta)
+        per_image[:, pack] = res
     return pairs, per_image, np.array([c.shape[0] > 0 for c in comps], dtype=bool)
 
 

@@ -323,6 +323,47 @@ def sweep_packed(src, joint, sizes, dedup, pairs, delta=0.1, grey_as_bgr=False):
     return whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta)
 
 
+def sweep_guided_packed(src, joint, sizes, dedup, pairs, delta=0.1, grey_as_bgr=False):
+    """The guided sweep on one pack: one-channel images of sizes[i] = (h_i, w_i) packed one after
+    another in the CUDA uint8 tensors src [total pixels, 1] / joint [total pixels, C], dedup =
+    dedup_points_ragged of their comparisons.  Pairs are
+    grouped by radius, equal (radius, eps) pairs computed once: per radius one
+    ops.guided_filter_ragged_sweep_u8 call (one ragged filter call per eps; a radius outside 1..128
+    falls back inside the entry, to the same bytes) for as many eps as keep the
+    filtered bytes under SWEEP_GUIDED_BYTES, and one WHDR call on the packed results - the packed
+    images are the point list, pixel index y * w_i + x behind the image's first pixel.
+    float64 [P, n]."""
+    from . import ops
+    pts, point_offsets, comps, weights, comp_offsets = dedup
+    pairs = np.asarray(pairs, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros((pairs.shape[0], len(sizes)), dtype=np.float64)
+    if comps.shape[0] == 0:
+        return out
+    image_offsets = np.concatenate([[0], np.cumsum([int(h) * int(w) for h, w in sizes],
+                                                   dtype=np.int64)])
+    px_comps = comps.copy()
+    for i, (_, w) in enumerate(sizes):
+        k0, k1 = comp_offsets[i], comp_offsets[i + 1]
+        own = pts[point_offsets[i]:point_offsets[i + 1]].astype(np.int64)
+        for col in (0, 1):
+            q = own[comps[k0:k1, col]]
+            px_comps[k0:k1, col] = q[:, 1] * int(w) + q[:, 0]
+    by_radius = {}      # radius -> {eps: [rows of pairs]}, both in order of first appearance
+    for p, (sc, ss) in enumerate(pairs):
+        by_radius.setdefault(int(ss), {}).setdefault(float(sc), []).append(p)
+    per = max(1, SWEEP_GUIDED_BYTES // max(1, int(image_offsets[-1])))
+    for radius, rows in by_radius.items():
+        eps = list(rows)
+        for e0 in range(0, len(eps), per):
+            chunk = eps[e0:e0 + per]
+            filtered = ops.guided_filter_ragged_sweep_u8(joint, src, radius, chunk,
+                                                         grey_as_bgr=grey_as_bgr, sizes=sizes)
+            res = whdr_points_u8(filtered, image_offsets, px_comps, weights, comp_offsets, delta)
+            for j, e in enumerate(chunk):
+                out[rows[e]] = res[j]
+    return out
+
+
 def _as3(image):
     return image.unsqueeze(-1) if image.dim() == 2 else image
 
@@ -361,8 +402,13 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
                    order, into ragged calls (ops.joint_bilateral_points_ragged_u8: the same bytes)
                    of equal channel counts and at most SWEEP_PACK_PIXELS pixels, one filter launch
                    and one WHDR launch per pack;
-      'guided'     guided_filter_u8(joint, src, int(sigma_space), sigma_color), full passes; the
-                   images of a list that have equal shapes are batched wherever they stand in it.
+      'guided'     guided_filter_u8(joint, src, int(sigma_space), sigma_color), full passes.  A
+                   one-channel list of device tensors of more than one shape is packed (packs of
+                   filter_reflectance.guided_ragged_packs) and, for the pairs with int(sigma_space)
+                   in 1..128, filtered by one ragged call per pack and distinct pair
+                   (ops.guided_filter_ragged_sweep_u8 per pack and radius; equal pairs are computed
+                   once; the same bytes).  Any other list, and any other pair, batches the images of equal
+                   shapes wherever they stand in the list.
     Each result equals whdr_batch on the filtered bytes as float32 / 255 (planar), bit for bit."""
     from . import filter_reflectance as fr
     from .batch import group_by_shape
@@ -411,7 +457,32 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
                 _pack_list([joint[i] for i in pack], torch)
             out[:, pack] = sweep_packed(s_p, j_p, psizes, pdedup, pairs, delta, grey_as_bgr)
         return out
-    # guided: equal shapes per pass, grouped wherever they stand in the list
+    # guided, a one-channel device list of more than one shape (the conditions of
+    # filter_reflectance.apply_filter_list's ragged route): the pairs whose radius the ragged guided
+    # filter takes run pack by pack, one ragged call per pack and distinct pair
+    keys = [key(i) for i in range(len(src))]
+    rows = [p for p, (_, ss) in enumerate(pairs) if 1 <= int(ss) <= fr.GF_RAGGED_MAX_RADIUS]
+    if (rows and len(set(k[:2] for k in keys)) > 1 and all(k[2] == 1 for k in keys)
+            and len(set(k[3] for k in keys)) == 1
+            and all(getattr(t, "is_cuda", False) for t in src + joint)):
+        from . import ops
+        sizes = [k[:2] for k in keys]
+        cap = ops.gf_workspace_cap(src[0].device, torch)
+        for pack in fr.guided_ragged_packs(sizes, fr.GF_RAGGED_MAX_BYTES, cap):
+            pdedup = join_dedup([dedup[i] for i in pack])
+            if pdedup[2].shape[0] == 0:
+                continue
+            s_p = _pack_list([src[i] for i in pack], torch)
+            j_p = s_p if all(joint[i] is src[i] for i in pack) else \
+                _pack_list([joint[i] for i in pack], torch)
+            out[np.ix_(rows, pack)] = sweep_guided_packed(s_p, j_p, [sizes[i] for i in pack], pdedup,
+                                                          pairs[rows], delta, grey_as_bgr)
+        rest = [p for p in range(pairs.shape[0]) if p not in rows]
+        if not rest:
+            return out
+    else:
+        rest = list(range(pairs.shape[0]))
+    # everything else: equal shapes per pass, grouped wherever they stand in the list
     # (1 GiB runs: the guided half addresses a run's pixels with int32 offsets)
     order = sorted(range(len(src)), key=key)
     for run in group_by_shape(order, key, max_bytes=1 << 30):
@@ -419,6 +490,6 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
         j_b = _stack([joint[i] for i in run])
         if s_b.shape[:3] != j_b.shape[:3]:
             raise ValueError("src and joint images must have the same size")
-        out[:, run] = _sweep_batch(filter_type, s_b, j_b, [comparisons_px[i] for i in run], pairs,
-                                   delta, grey_as_bgr)
+        out[np.ix_(rest, run)] = _sweep_batch(filter_type, s_b, j_b, [comparisons_px[i] for i in run],
+                                              pairs[rest], delta, grey_as_bgr)
     return out
