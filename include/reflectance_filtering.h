@@ -397,6 +397,42 @@ int rf_whdr_points_u8(const uint8_t *samples, int n_sets, long long set_stride, 
                       const int *point_offsets, const int *comps, const double *weights,
                       const int *comp_offsets, double delta, double *out, void *stream);
 
+/*
+ * PNG encode on the device: n packed 8-bit images of different sizes to one complete zlib stream
+ * per image - the body of a PNG file's single IDAT chunk; the caller adds signature, IHDR, the
+ * chunk framing and IEND.
+ *   images         the n images tightly packed one after another (as for rf_jbf_ragged_u8), cn_in
+ *                  channels each: 1 (written as colour type 0), 3 (BGR in memory, written as colour
+ *                  type 2 in RGB order), or 1 with RF_PNG_GREY_AS_RGB (colour type 2, three equal
+ *                  bytes per pixel, without a replicated copy)
+ *   heights, widths  n ints each, HOST memory, every entry > 0
+ *   streams        device buffer of stream_capacity >= rf_png_stream_bound(...) bytes; must not
+ *                  overlap images.  The stream of image i is the bytes
+ *                  [stream_offsets[i], stream_offsets[i + 1]) of it: the streams lie one after
+ *                  another without gaps, so stream_offsets[n] bytes are used
+ *   stream_offsets n + 1 uint64, DEVICE memory, written by the call
+ *   workspace      device scratch of at least rf_png_workspace_bytes(...) bytes, 16-byte aligned
+ * The raw stream of an image is, per row, the filter byte 2 (Up) and the differences to the row
+ * above (zeros above the first row), cut into chunks of one library-wide length (rf_debug_png_plan)
+ * that are deflated independently: literals and runs of the previous byte (length 3..258 at distance
+ * 1) in one dynamic-Huffman block per chunk, closed by an empty stored block so that chunks join on
+ * byte boundaries, or one stored block where that is shorter.  The stream is 78 01, the chunks,
+ * 03 00 and the Adler-32 of the raw stream; any inflate reads it.  Its bytes are a function of the
+ * input alone (the same on every run), and differ from zlib's for the same pixels.
+ * rf_png_stream_bound: sum over the images of 2 + sum over its chunks of (chunk bytes + 9) + 2 + 4;
+ * an image whose own bound reaches 2^31 is refused (one IDAT chunk holds 2^31 - 1 bytes).  Both size
+ * queries return 0 for n <= 0 and for arguments the call refuses.  n == 0 is RF_OK and touches
+ * nothing.  Three launches per call whatever the list holds.  SYNCHRONISES THE STREAM once (before
+ * its launches, to upload the image table) and is refused (RF_E_UNSUPPORTED) on a capturing stream.
+ */
+#define RF_PNG_GREY_AS_RGB 1 /* cn_in = 1 only: write three equal samples per pixel */
+size_t rf_png_stream_bound(int n, const int *heights, const int *widths, int cn_in, int flags);
+size_t rf_png_workspace_bytes(int n, const int *heights, const int *widths, int cn_in, int flags);
+int rf_png_deflate_ragged_u8(const uint8_t *images, int n, const int *heights, const int *widths,
+                             int cn_in, int flags, uint8_t *streams, size_t stream_capacity,
+                             unsigned long long *stream_offsets, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

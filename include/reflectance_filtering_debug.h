@@ -167,6 +167,14 @@ int rf_debug_colorize_ragged_plan(int n, const int *heights, const int *widths, 
 int rf_debug_gf_ragged_plan(int n, const int *heights, const int *widths, int guide_cn, int src_cn,
                             int radius, int flags, int *out, int cap);
 
+/* The plan of rf_png_deflate_ragged_u8 for images of these sizes: the ints {chunk length in raw
+ * bytes (one library-wide constant), chunks of all images} followed by each image's number of chunks
+ * (ceil(h * (1 + w * c_out) / chunk length)), as many of these 2 + n ints as `cap` holds, at out.
+ * Returns n (out may be NULL when cap is 0; n == 0 gives the two leading ints), or the entry's
+ * refusal code for arguments it refuses or a bad cap.  Host only: needs no device. */
+int rf_debug_png_plan(int n, const int *heights, const int *widths, int cn_in, int flags, int *out,
+                      int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ JBF_TRUE_DIVISION = 1
 JBF_FORCE_GENERIC = 2
 JBF_GREY_AS_BGR = 4
 GF_GREY_AS_BGR = 1          # rf_gf_ex_u8: a 1-channel guide stands for three equal channels
+PNG_GREY_AS_RGB = 1         # rf_png_deflate_ragged_u8: a 1-channel image is written as three equal samples
 CNN_NPARAMS = 4513
 CNN_NPACKED = 4673          # RF_CNN_NPACKED: floats of rf_cnn_pack_weights' output
 
@@ -33,13 +34,14 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
            "rf_jbf_points_u8", "rf_jbf_points_ragged_workspace_bytes", "rf_jbf_points_ragged_u8",
            "rf_whdr_points_u8", "rf_jbf_ragged_workspace_bytes", "rf_jbf_ragged_u8",
            "rf_colorize_ragged_workspace_bytes", "rf_colorize_ragged_srgb_u8",
-           "rf_gf_ragged_workspace_bytes", "rf_gf_ragged_u8")
+           "rf_gf_ragged_workspace_bytes", "rf_gf_ragged_u8", "rf_png_stream_bound",
+           "rf_png_workspace_bytes", "rf_png_deflate_ragged_u8")
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
                  "rf_debug_jbf_points_plan", "rf_debug_jbf_ragged_plan",
                  "rf_debug_jbf_ragged_slab_plan", "rf_debug_colorize_ragged_plan",
-                 "rf_debug_gf_ragged_plan")
+                 "rf_debug_gf_ragged_plan", "rf_debug_png_plan")
 # switches that leave work out (wrong results, timing experiments only); all others keep the bytes
 RESULT_CHANGING_OPTIONS = ("jbf_stage_only", "gf_exp_skip")
 
@@ -128,6 +130,14 @@ def load_library():
         lib.rf_whdr_points_u8.argtypes = [vp, ci, ctypes.c_longlong, ci, ci, vp, vp, vp, vp, cd, vp,
                                           vp]
         lib.rf_whdr_points_u8.restype = ci
+        lib.rf_png_stream_bound.argtypes = [ci, vp, vp, ci, ci]
+        lib.rf_png_stream_bound.restype = sz
+        lib.rf_png_workspace_bytes.argtypes = [ci, vp, vp, ci, ci]
+        lib.rf_png_workspace_bytes.restype = sz
+        lib.rf_png_deflate_ragged_u8.argtypes = [vp, ci, vp, vp, ci, ci, vp, sz, vp, vp, sz, vp]
+        lib.rf_png_deflate_ragged_u8.restype = ci
+        lib.rf_debug_png_plan.argtypes = [ci, vp, vp, ci, ci, vp, ci]
+        lib.rf_debug_png_plan.restype = ci
         lib.rf_debug_option.argtypes = [ctypes.c_char_p, ci]
         lib.rf_debug_option.restype = ci
         lib.rf_debug_clock_probe.argtypes = [vp, ci, vp]
@@ -304,6 +314,23 @@ def gf_ragged_plan(sizes, guide_cn, src_cn, radius, flags=0):
         return None
     return dict(zip(("launches", "stage1", "rowstate", "colwalk", "hl", "out_w"),
                     (int(v) for v in out)))
+
+
+def png_plan(sizes, cn_in=1, flags=0):
+    """The plan of rf_png_deflate_ragged_u8 for images of these sizes ([n,2] (h, w)) (rf_debug_png_plan,
+    host only): (chunk length in raw bytes, chunks of all images, [chunks of each image])."""
+    import numpy as np
+    lib = load_library()
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    n = sizes.shape[0]
+    hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
+    ws = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
+    out = np.zeros(n + 2, dtype=np.int32)
+    rc = lib.rf_debug_png_plan(n, hs.ctypes.data, ws.ctypes.data, int(cn_in), int(flags),
+                               out.ctypes.data, n + 2)
+    if rc < 0:
+        check(rc, "rf_debug_png_plan")
+    return int(out[0]), int(out[1]), [int(v) for v in out[2:]]
 
 
 def require_gpu():

@@ -48,10 +48,12 @@ IO_THREADS = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_g
 def pipeline(items, load, compute, step=None):
     """Three-stage pipeline over `items` in steps of `step` files: while the device works on step
     k (in the calling thread: `compute(list of load() results)` returns a list of
-    (file name, array) pairs to write), the thread pool decodes step k+1 and encodes what step k-1
-    produced.  Image decode / encode spend their time in zlib with the GIL released and the device
-    calls release it too, so the three stages overlap; at most two decoded steps and two steps of
-    pending writes are alive at a time.  Returns the names written, in order."""
+    (file name, payload) pairs to write), the thread pool decodes step k+1 and encodes what step k-1
+    produced: an array payload goes through image_utils.imwrite, a `bytes` payload - a file encoded
+    on the device already - is written as it is.  Image decode / encode spend their time in zlib with
+    the GIL released and the device calls release it too, so the three stages overlap; at most two
+    decoded steps and two steps of pending writes are alive at a time.  Returns the names written,
+    in order."""
     step = step or STEP_FILES
     items = list(items)
     steps = [items[i:i + step] for i in range(0, len(items), step)]
@@ -68,13 +70,37 @@ def pipeline(items, load, compute, step=None):
             while len(pending) > 1:        # writes of step k-2 must be done before step k's start
                 for f in pending.pop(0):
                     f.result()
-            pending.append([pool.submit(iu.imwrite, name, arr) for name, arr in jobs])
+            pending.append([pool.submit(_write_job, name, payload) for name, payload in jobs])
             written.extend(name for name, _ in jobs)
             loads = nxt
         for futs in pending:
             for f in futs:
                 f.result()
     return written
+
+
+def _write_job(name, payload):
+    if isinstance(payload, (bytes, bytearray, memoryview)):
+        try:
+            with open(name, "wb") as fh:
+                fh.write(payload)
+        except OSError:
+            raise Exception("Not able to write {}, does the folder exist?".format(name))
+    else:
+        iu.imwrite(name, payload)
+
+
+PNG_ENCODERS = ("host", "device")
+
+
+def _check_png_encoder(png_encoder):
+    if png_encoder not in PNG_ENCODERS:
+        raise ValueError("png_encoder must be one of {}".format(", ".join(PNG_ENCODERS)))
+    return png_encoder == "device"
+
+
+def _is_png(name):
+    return os.path.splitext(name)[1].lower() == ".png"
 
 
 def expand_inputs(patterns):
@@ -134,11 +160,14 @@ def _is_grey(batch):
 
 
 def filter_files(filter_type, inputs, guidance_pattern, sigma_color, sigma_spatial, path_out,
-                 iterations=1, rank=None, world=None):
+                 iterations=1, rank=None, world=None, png_encoder="host"):
     """filter_reflectance.read_filter_write over this rank's share of `inputs`; returns the
-    list of files written."""
+    list of files written.  png_encoder="device" deflates the `.png` outputs on the device
+    (ops.png_encode_ragged_u8: the same pixels in files of other bytes); any other extension keeps
+    the host writer."""
     import torch
     fr._check_params(filter_type, sigma_color, sigma_spatial)
+    on_device = _check_png_encoder(png_encoder)
     mine = my_slice(inputs, rank, world)
 
     def load(f):
@@ -153,6 +182,22 @@ def filter_files(filter_type, inputs, guidance_pattern, sigma_color, sigma_spati
             name = fr.output_filename(name, path_out, filter_type, sigma_color, sigma_spatial)
         return name
 
+    def device_jobs(names, results, grey_src):
+        """The jobs of one device result per name ([H,W,C] tensors): files encoded on the device for
+        the `.png` names (one call for all of them; a grey source as three equal samples, which is
+        what the host path replicates), arrays for the others."""
+        jobs = [None] * len(names)
+        png = [i for i, name in enumerate(names) if _is_png(name)]
+        if png:
+            files = ops.png_encode_ragged_u8([results[i] for i in png], grey_as_rgb=grey_src)
+            for i, data in zip(png, files):
+                jobs[i] = (names[i], data)
+        for i, name in enumerate(names):
+            if jobs[i] is None:
+                res = results[i].cpu().numpy()
+                jobs[i] = (name, np.repeat(res, 3, axis=2) if grey_src else res)
+        return jobs
+
     def compute_ragged(loaded):
         """A bilateral step whose images differ in shape - or a guided one whose sources are all
         grey: one ragged call over the whole step (fr.apply_filter_list; one per pass for the
@@ -165,6 +210,8 @@ def filter_files(filter_type, inputs, guidance_pattern, sigma_color, sigma_spati
         joints = [torch.from_numpy(cut(t[2], grey_gui)).cuda() for t in loaded]
         outs = fr.apply_filter_list(filter_type, images, joints, sigma_color, sigma_spatial,
                                     iterations=iterations, grey_as_bgr=grey_gui)
+        if on_device:
+            return device_jobs([out_name(t[0]) for t in loaded], list(outs), grey_src)
         jobs = []
         for (f, _, _), res in zip(loaded, outs):
             res = res.cpu().numpy()
@@ -203,6 +250,9 @@ def filter_files(filter_type, inputs, guidance_pattern, sigma_color, sigma_spati
                 joints = torch.from_numpy(guis).cuda()
                 out = fr.apply_filter_batch(filter_type, images, joints, sigma_color,
                                             sigma_spatial, iterations=iterations)
+            if on_device:
+                jobs.extend(device_jobs([out_name(t[0]) for t in group], list(out), grey_src))
+                continue
             out = out.cpu().numpy()
             if grey_src:
                 out = np.repeat(out, 3, axis=3)
@@ -213,14 +263,24 @@ def filter_files(filter_type, inputs, guidance_pattern, sigma_color, sigma_spati
     return pipeline(mine, load, compute)
 
 
-def decompose_files(inputs, path_out, rank=None, world=None):
+def decompose_files(inputs, path_out, rank=None, world=None, png_encoder="host"):
     """decompose_image over this rank's share of `inputs`: CNN, colourisation, percentile
     normalisation and the sRGB byte conversion all run batched on the device; the host only
-    decodes and encodes the image files."""
+    decodes and encodes the image files - or, with png_encoder="device", only decodes them: the
+    three outputs of a step are deflated on the device (ops.png_encode_ragged_u8, three calls) and
+    come back as finished files with the same pixels in other bytes."""
     import torch
     from . import decompose_with_trained_CNN as dc
+    on_device = _check_png_encoder(png_encoder)
     mine = my_slice(inputs, rank, world)
     firsts = []
+
+    def add_encoded(jobs, loaded, sizes, r8, refl, shad):
+        """The step's jobs from its packed device outputs ([total pixels], [total pixels, 3],
+        [total pixels]), encoded there."""
+        files = [ops.png_encode_ragged_u8(t, sizes=sizes) for t in (r8, refl, shad)]
+        for i, t in enumerate(loaded):
+            add(jobs, t[0], files[0][i], files[1][i], files[2][i])
 
     def add(jobs, f, r8, refl, shad):
         base = os.path.splitext(os.path.basename(f))[0]
@@ -234,6 +294,10 @@ def decompose_files(inputs, path_out, rank=None, world=None):
         step (one CNN pass, one ragged colourise) instead of one decompose_batch per run of equal
         shapes, then three copies of the packed outputs to the host, split there: identical bytes."""
         sizes, _, r8, refl, shad = dc.decompose_packed([torch.from_numpy(t[1]).cuda() for t in loaded])
+        if on_device:
+            jobs = []
+            add_encoded(jobs, loaded, sizes, r8.reshape(-1), refl.reshape(-1, 3), shad.reshape(-1))
+            return jobs
         r8, refl, shad = r8.cpu().numpy(), refl.cpu().numpy(), shad.cpu().numpy()
         jobs, first = [], 0
         for (f, _), (h, w) in zip(loaded, sizes.tolist()):
@@ -249,6 +313,10 @@ def decompose_files(inputs, path_out, rank=None, world=None):
         for group in group_by_shape(loaded, lambda t: t[1].shape):
             images = torch.from_numpy(np.stack([t[1] for t in group])).cuda()
             _, r8, refl, shad = dc.decompose_batch(images)
+            if on_device:   # a uniform step goes through the same op, as a list of equal sizes
+                add_encoded(jobs, group, [t[1].shape[:2] for t in group], r8.reshape(-1),
+                            refl.reshape(-1, 3), shad.reshape(-1))
+                continue
             r8, refl, shad = r8.cpu().numpy(), refl.cpu().numpy(), shad.cpu().numpy()
             for i, (f, _) in enumerate(group):
                 add(jobs, f, r8[i], refl[i], shad[i])
@@ -269,9 +337,13 @@ def build_parser():
     f.add_argument("--sigma_spatial", type=float, required=True)
     f.add_argument("--filter_type", required=True)
     f.add_argument("--iterations", type=int, default=1)
+    f.add_argument("--png_encoder", choices=PNG_ENCODERS, default="host",
+                   help="who deflates the .png outputs: zlib on the I/O threads, or the device")
     d = sub.add_parser("decompose", help="decompose_with_trained_CNN over many files")
     d.add_argument("--inputs", nargs="+", required=True)
     d.add_argument("--path_out", required=True)
+    d.add_argument("--png_encoder", choices=PNG_ENCODERS, default="host",
+                   help="who deflates the three .png outputs per photo")
     return parser
 
 
@@ -287,9 +359,10 @@ def main(argv=None):
     files = expand_inputs(args.inputs)
     if args.command == "filter":
         out = filter_files(args.filter_type, files, args.guidance, args.sigma_color,
-                           args.sigma_spatial, args.path_out, iterations=args.iterations)
+                           args.sigma_spatial, args.path_out, iterations=args.iterations,
+                           png_encoder=args.png_encoder)
     else:
-        out = decompose_files(files, args.path_out)
+        out = decompose_files(files, args.path_out, png_encoder=args.png_encoder)
     print("rank {}: wrote {} file(s)".format(os.environ.get("RANK", "0"), len(out)))
     return 0
 

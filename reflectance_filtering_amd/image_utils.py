@@ -239,6 +239,28 @@ def _png_encode(image, level=1):
             + chunk(b"IDAT", deflated) + chunk(b"IEND", b""))
 
 
+def png_container(stream, height, width, ctype):
+    """A complete 8-bit PNG file around a finished zlib stream of its filtered rows (whoever deflated
+    them - ops.png_encode_ragged_u8 does it on the device): signature, IHDR (colour type 0 grey or
+    2 RGB, no interlace), one IDAT holding `stream`, IEND."""
+    if ctype not in (0, 2):
+        raise ValueError("colour type must be 0 (grey) or 2 (RGB)")
+    if height <= 0 or width <= 0:
+        raise ValueError("image sizes must be positive")
+    view = memoryview(stream).cast("B")      # bytes, or any buffer of them: copied once, by the join
+    if view.nbytes >= 2 ** 31:
+        raise ValueError("one IDAT chunk holds at most 2^31 - 1 bytes")
+
+    def chunk(tag, body):
+        return (struct.pack(">I", len(body)) + tag + body
+                + struct.pack(">I", zlib.crc32(body, zlib.crc32(tag)) & 0xFFFFFFFF))
+
+    crc = zlib.crc32(view, zlib.crc32(b"IDAT")) & 0xFFFFFFFF
+    return b"".join((_PNG_SIG, chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, ctype, 0, 0, 0)),
+                     struct.pack(">I", view.nbytes), b"IDAT", view, struct.pack(">I", crc),
+                     chunk(b"IEND", b"")))
+
+
 def _read_any(filename):
     """File -> uint8 HxWx3 BGR, or None if it cannot be decoded (cv2.imread contract)."""
     try:

@@ -14,11 +14,14 @@ _cnn_consts = {}
 _jbf_ragged_workspaces = {}
 _colorize_ragged_workspaces = {}
 _gf_ragged_workspaces = {}
+_png_workspaces = {}
 
 
 def release_workspaces():
-    """Drop the cached guided-filter, ragged-bilateral, ragged-colourise and ragged-guided scratch
-    buffers and CNN constants (device memory)."""
+    """Drop the cached guided-filter, ragged-bilateral, ragged-colourise, ragged-guided and PNG-encode
+    scratch buffers and CNN constants (device memory)."""
+    _png_workspaces.clear()
+    del _png_host[:]
     _gf_workspaces.clear()
     _gf_ragged_workspaces.clear()
     _jbf_ragged_workspaces.clear()
@@ -600,6 +603,106 @@ def colorize_ragged_srgb_u8(images, r, sizes=None, want_reflectance=True, want_s
     _ffi.check(rc, "rf_colorize_ragged_srgb_u8")
     return (refl, shad, split_packed(refl, sizes) if refl is not None else [],
             [v.squeeze(-1) for v in split_packed(shad.view(-1, 1), sizes)] if shad is not None else [])
+
+
+_png_host = []
+_png_threads = []
+
+
+def _png_host_buffer(need, torch):
+    """A page-locked host buffer of at least `need` bytes for the streams' way back (a copy into
+    pageable memory runs at a fraction of the link's rate); release_workspaces() drops it."""
+    if not _png_host or _png_host[0].numel() < need:
+        del _png_host[:]
+        _png_host.append(torch.empty(max(need, 1 << 20), dtype=torch.uint8, pin_memory=True))
+    return _png_host[0]
+
+
+def _png_pool():
+    if not _png_threads:
+        import os
+        from concurrent.futures import ThreadPoolExecutor
+        cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        _png_threads.append(ThreadPoolExecutor(max_workers=max(1, min(8, cpus))))
+    return _png_threads[0]
+
+
+def png_encode_ragged_u8(images, sizes=None, grey_as_rgb=False):
+    """PNG files of images of different sizes, deflated on the device in one call
+    (rf_png_deflate_ragged_u8: Up filter, runs and literals in one dynamic-Huffman block per chunk).
+    images: a list of n CUDA uint8 tensors [H_i, W_i], [H_i, W_i, 1] (written as grey, colour type 0)
+    or [H_i, W_i, 3] (BGR, written as colour type 2), all of one kind - or, with sizes = [n,2] (h, w),
+    the images already packed one after another as one contiguous CUDA tensor [total pixels, C] (or
+    [total pixels] for C = 1).  grey_as_rgb: one-channel images are written as colour type 2 with
+    three equal samples per pixel - the file cv2.imwrite makes of np.repeat(image, 3, axis=2) -
+    without that copy.  Returns a list of n `bytes`, each a complete PNG file that decodes to the
+    image's pixels (its bytes differ from image_utils._png_encode's: another deflate).  What crosses
+    to the host is the n + 1 stream offsets and then the compressed bytes, in one copy; the host adds
+    the container (image_utils.png_container).  Synchronises the current stream."""
+    from . import image_utils as iu
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    if sizes is None:
+        images = list(images)
+        if not images:
+            return []
+        flat = []
+        for t in images:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8
+                    and t.dim() in (2, 3) and t.is_contiguous()):
+                raise ValueError("images must be contiguous CUDA uint8 tensors [H,W] or [H,W,C]")
+            flat.append(t if t.dim() == 3 else t.unsqueeze(-1))
+        images, sizes = pack_images(flat, "images", torch)
+    else:
+        sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+        if sizes.shape[0] == 0:
+            return []
+        if sizes.min() <= 0:
+            raise ValueError("image sizes must be positive")
+        npx = int((sizes[:, 0] * sizes[:, 1]).sum())
+        if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8
+                and images.dim() in (1, 2) and images.is_contiguous() and images.shape[0] == npx):
+            raise ValueError("images must be a contiguous CUDA uint8 tensor [%d, C]: the pixels of "
+                             "all images" % npx)
+        if images.dim() == 1:
+            images = images.view(-1, 1)
+    if sizes.max() >= 2 ** 31:
+        raise ValueError("image too large")
+    cn = int(images.shape[1])
+    flags = _ffi.PNG_GREY_AS_RGB if grey_as_rgb else 0
+    dev = images.device
+    n = sizes.shape[0]
+    hs = np.ascontiguousarray(sizes[:, 0], dtype=np.int32)
+    wds = np.ascontiguousarray(sizes[:, 1], dtype=np.int32)
+    args = (n, hs.ctypes.data, wds.ctypes.data, cn, flags)
+    bound = lib.rf_png_stream_bound(*args)
+    need = lib.rf_png_workspace_bytes(*args)
+    # bound == 0 or need == 0: the entry says why.  One cached buffer: workspace, offsets, streams.
+    up = lambda b: (b + 255) & ~255
+    off_at = up(need)
+    str_at = off_at + up(8 * (n + 1))
+    buf = _stream_workspace(_png_workspaces, str_at + max(bound, 1), dev, torch)
+    offsets = buf[off_at:off_at + 8 * (n + 1)].view(torch.int64)
+    rc = lib.rf_png_deflate_ragged_u8(images.data_ptr(), n, hs.ctypes.data, wds.ctypes.data, cn, flags,
+                                      buf.data_ptr() + str_at, bound, offsets.data_ptr(),
+                                      buf.data_ptr(), need, _ffi.current_stream_ptr(torch))
+    _ffi.check(rc, "rf_png_deflate_ragged_u8")
+    off = offsets.cpu().numpy()
+    if off[0] != 0 or np.any(np.diff(off) <= 0) or off[-1] > bound:
+        raise _ffi.RFError("rf_png_deflate_ragged_u8 returned stream offsets outside its bound")
+    used = int(off[-1])
+    host = _png_host_buffer(used, torch)
+    host[:used].copy_(buf[str_at:str_at + used], non_blocking=True)
+    torch.cuda.current_stream(dev).synchronize()
+    data = host.numpy()
+    ctype = 2 if (cn == 3 or grey_as_rgb) else 0
+    jobs = [(data[int(off[i]):int(off[i + 1])], int(h), int(w), ctype)
+            for i, (h, w) in enumerate(sizes.tolist())]
+    if used < (1 << 20) or n == 1:
+        return [iu.png_container(*job) for job in jobs]
+    # the checksums of large streams run side by side (zlib.crc32 releases the GIL); every file is a
+    # copy of its own, so the host buffer is free again when the call returns
+    return list(_png_pool().map(lambda job: iu.png_container(*job), jobs))
 
 
 def _chk_images_f32(t, name, torch):
