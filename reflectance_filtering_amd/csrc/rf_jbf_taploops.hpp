@@ -664,22 +664,55 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
 #define RF_L2_SMUL(X, N) "v_mul_f32 %[w" #N "], %[w" #N "], %[s" X "]\n\t"
 #define RF_L2_SADD(N) "v_add_f32 %[s" #N "], %[s" #N "], %[w" #N "]\n\t"
 #define RF_L2_GATHER(X, N) "ds_read_b32 %[a" X #N "], %[a" X #N "]\n\t"
-#define RF_L2_STEP_TXT(F, X, MID, WAITTXT)                                                                       \
+    // End groups: a column of a row's first or last group lies outside the disk of some of the lane's four
+    // outputs whatever the parity of the half-width - its spatial weight for them is exactly 0, and adding
+    // +0.0 to a non-negative sum is the same as not adding it.  A step therefore takes two live masks over
+    // the outputs 0..3, FM for its front half (SAD, address and gather of column U + 2) and BM for its back
+    // half (the four float instructions of column U), written (o0, o1, o2, o3, number of outputs): a slot's
+    // instructions are emitted only where the mask has the output, and the step's wait leaves exactly the
+    // gathers it issued in flight.  A back half never runs for a slot whose front half did not (0 x a
+    // stale register is not +0 if the register holds an Inf or NaN pattern): BM of column U is a subset of
+    // the FM that column's front half was issued with, two steps earlier.
+#define RF_L2_M15 (1, 1, 1, 1, 4)
+#define RF_L2_M14 (0, 1, 1, 1, 3)
+#define RF_L2_M12 (0, 0, 1, 1, 2)
+#define RF_L2_M8 (0, 0, 0, 1, 1)
+#define RF_L2_M7 (1, 1, 1, 0, 3)
+#define RF_L2_M4 (0, 0, 1, 0, 1)
+#define RF_L2_M3 (1, 1, 0, 0, 2)
+#define RF_L2_M2 (0, 1, 0, 0, 1)
+#define RF_L2_M1 (1, 0, 0, 0, 1)
+#define RF_L2_SEL0(A, B, C, D, K) A
+#define RF_L2_SEL1(A, B, C, D, K) B
+#define RF_L2_SEL2(A, B, C, D, K) C
+#define RF_L2_SEL3(A, B, C, D, K) D
+#define RF_L2_SELK(A, B, C, D, K) K
+#define RF_L2_ON_0(T)
+#define RF_L2_ON_1(T) T
+#define RF_L2_ON_P(B, T) RF_L2_ON_##B(T)
+#define RF_L2_ON_E(B, T) RF_L2_ON_P(B, T)
+#define RF_L2_ON(M, N, T) RF_L2_ON_E(RF_L2_SEL##N M, T)
+#define RF_L2_STR_P(K) #K
+#define RF_L2_STR(K) RF_L2_STR_P(K)
+#define RF_L2_STEP_TXT(F, X, MID, FM, BM, END)                                                                   \
     RF_L2_PRE_##F(X)                                                                                             \
-    RF_L2_SAD_##F(X, 0) RF_L2_WMUL(X, 0)                                                                         \
-    RF_L2_SAD_##F(X, 1) RF_L2_WMUL(X, 1)                                                                         \
-    RF_L2_SAD_##F(X, 2) RF_L2_WMUL(X, 2)                                                                         \
-    RF_L2_SAD_##F(X, 3) RF_L2_WMUL(X, 3)                                                                         \
+    RF_L2_ON(FM, 0, RF_L2_SAD_##F(X, 0)) RF_L2_ON(BM, 0, RF_L2_WMUL(X, 0))                                       \
+    RF_L2_ON(FM, 1, RF_L2_SAD_##F(X, 1)) RF_L2_ON(BM, 1, RF_L2_WMUL(X, 1))                                       \
+    RF_L2_ON(FM, 2, RF_L2_SAD_##F(X, 2)) RF_L2_ON(BM, 2, RF_L2_WMUL(X, 2))                                       \
+    RF_L2_ON(FM, 3, RF_L2_SAD_##F(X, 3)) RF_L2_ON(BM, 3, RF_L2_WMUL(X, 3))                                       \
     "v_cvt_f32_ubyte3 %[s2" X "], %[t2" X "]\n\t"                                                                \
     MID                                                                                                          \
-    RF_L2_ADR_##F(X, 0) RF_L2_WADD(0)                                                                            \
-    RF_L2_ADR_##F(X, 1) RF_L2_WADD(1)                                                                            \
-    RF_L2_ADR_##F(X, 2) RF_L2_WADD(2)                                                                            \
-    RF_L2_ADR_##F(X, 3) RF_L2_WADD(3)                                                                            \
-    RF_L2_GATHER(X, 0) RF_L2_GATHER(X, 1) RF_L2_GATHER(X, 2) RF_L2_GATHER(X, 3)                                  \
-    RF_L2_SMUL(X, 0) RF_L2_SMUL(X, 1) RF_L2_SMUL(X, 2) RF_L2_SMUL(X, 3)                                          \
-    RF_L2_SADD(0) RF_L2_SADD(1) RF_L2_SADD(2) RF_L2_SADD(3)                                                      \
-    WAITTXT
+    RF_L2_ON(FM, 0, RF_L2_ADR_##F(X, 0)) RF_L2_ON(BM, 0, RF_L2_WADD(0))                                          \
+    RF_L2_ON(FM, 1, RF_L2_ADR_##F(X, 1)) RF_L2_ON(BM, 1, RF_L2_WADD(1))                                          \
+    RF_L2_ON(FM, 2, RF_L2_ADR_##F(X, 2)) RF_L2_ON(BM, 2, RF_L2_WADD(2))                                          \
+    RF_L2_ON(FM, 3, RF_L2_ADR_##F(X, 3)) RF_L2_ON(BM, 3, RF_L2_WADD(3))                                          \
+    RF_L2_ON(FM, 0, RF_L2_GATHER(X, 0)) RF_L2_ON(FM, 1, RF_L2_GATHER(X, 1))                                      \
+    RF_L2_ON(FM, 2, RF_L2_GATHER(X, 2)) RF_L2_ON(FM, 3, RF_L2_GATHER(X, 3))                                      \
+    RF_L2_ON(BM, 0, RF_L2_SMUL(X, 0)) RF_L2_ON(BM, 1, RF_L2_SMUL(X, 1))                                          \
+    RF_L2_ON(BM, 2, RF_L2_SMUL(X, 2)) RF_L2_ON(BM, 3, RF_L2_SMUL(X, 3))                                          \
+    RF_L2_ON(BM, 0, RF_L2_SADD(0)) RF_L2_ON(BM, 1, RF_L2_SADD(1))                                                \
+    RF_L2_ON(BM, 2, RF_L2_SADD(2)) RF_L2_ON(BM, 3, RF_L2_SADD(3))                                                \
+    "s_waitcnt lgkmcnt(" RF_L2_STR(RF_L2_SELK FM) ")" END
     // Half H of a group (steps 2 H and 2 H + 1).  WC = the octet that holds the group's window, WN = the
     // one the next group's window is loaded into - both are in-out operands of EVERY statement, so that
     // on every path each of the two C++ variables is only ever the output of a statement of this loop
@@ -691,14 +724,14 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
 #define RF_L2_MID3_LAST "s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %[hwc], %[hwa]\n\t"
 #define RF_L2_WLOAD_0 "s_load_dwordx8 %[wn], %[wb], %[wo] offset:%[wi]\n\t"
 #define RF_L2_WLOAD_1
-#define RF_L2_HALF(F, H, WC, WN, TA, O0, O1, WOFF, WIMM, MIDB)                                                   \
+#define RF_L2_HALF(F, H, WC, WN, TA, O0, O1, WOFF, WIMM, MIDB, FA, BA, FB, BB)                                   \
     {                                                                                                            \
         float w0_, w1_, w2_, w3_;                                                                                \
         [[maybe_unused]] uint32_t tj_;                                                                           \
         asm volatile(RF_L2_WLOAD_##H                                                                             \
                      "ds_read2_b32 %[tn], %[ta] offset0:%[o0] offset1:%[o1]\n\t"                                 \
-                     RF_L2_STEP_TXT(F, "a", "", "s_waitcnt lgkmcnt(4)\n\t")                                      \
-                     RF_L2_STEP_TXT(F, "b", MIDB, "s_waitcnt lgkmcnt(4)")                                        \
+                     RF_L2_STEP_TXT(F, "a", "", FA, BA, "\n\t")                                                  \
+                     RF_L2_STEP_TXT(F, "b", MIDB, FB, BB, "")                                                    \
                      : [tn] "=&v"(tp[H]), RF_L2_TJOUT_##F                                                        \
                        [aa0] "+v"(gg[(2 * (H) + 2) & 3][0]), [aa1] "+v"(gg[(2 * (H) + 2) & 3][1]),               \
                        [aa2] "+v"(gg[(2 * (H) + 2) & 3][2]), [aa3] "+v"(gg[(2 * (H) + 2) & 3][3]),               \
@@ -725,7 +758,8 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
                        [sb] "v"(sv[2 * (H) + 1]), [wb] "s"(swsym), [wo] "s"(WOFF),                               \
                        [wi] "n"(WIMM), [hwa] "s"(hw_ahead));                                                     \
     }
-    // (The last step of a row waits like any other: four gathers stay in flight across the row loop's
+    // (The last step of a row waits like any other: its gathers - two of them, the fronts [3] of the next
+    //  row's column 1 - stay in flight across the row loop's
     //  back edge, where the compiler writes code of its own - the next row's addresses.  That it moves
     //  none of the registers in flight there is checked on the machine code, along every path of the
     //  control-flow graph: tests/test_cabi.py.  A variant of this loop once got such a v_mov; a full wait
@@ -734,20 +768,43 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
     // group or the next row's first one), PA / PB their ds_read2 offsets; the group's full wait - for the
     // weight window requested at its top - sits in the middle of step 3, where nothing is in flight but
     // the gathers of step 2, a whole step old (step 3 reads no texel pair).
+    // F0 B0 .. F3 B3: the front and back masks of the group's steps 0..3.
+#define RF_L2_GROUP_M(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM, MID3, F0, B0, F1, B1, F2, B2, F3, B3)               \
+    RF_L2_HALF(F, 0, WC, WN, NA, PA, PB, WOFF, WIMM, "", F0, B0, F1, B1)                                         \
+    RF_L2_HALF(F, 1, WC, WN, NB, PA, PB, WOFF, WIMM, MID3, F2, B2, F3, B3)
 #define RF_L2_GROUP(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM, MID3)                                                 \
-    RF_L2_HALF(F, 0, WC, WN, NA, PA, PB, WOFF, WIMM, "")                                                         \
-    RF_L2_HALF(F, 1, WC, WN, NB, PA, PB, WOFF, WIMM, MID3)
+    RF_L2_GROUP_M(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM, MID3, RF_L2_M15, RF_L2_M15, RF_L2_M15, RF_L2_M15,       \
+                  RF_L2_M15, RF_L2_M15, RF_L2_M15, RF_L2_M15)
+    // The last group of a row: its columns 0..3 are live for the outputs [15, 14, 12, 8] at most (column u
+    // lies right of the disk of every output below u), so the front halves of its own columns 2 and 3 -
+    // issued in its steps 0 and 1 - take [12, 8]; steps 2 and 3 form the next row's columns 0 and 1, whose
+    // back halves - in that row's first group - take [1, 3].
+#define RF_L2_GROUP_LAST(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM)                                                  \
+    RF_L2_GROUP_M(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM, RF_L2_MID3_LAST, RF_L2_M12, RF_L2_M15, RF_L2_M8,        \
+                  RF_L2_M14, RF_L2_M1, RF_L2_M12, RF_L2_M3, RF_L2_M8)
+    // The first group of a row of two groups or more: columns 0..3 live for [1, 3, 7, 15] (column u lies left
+    // of the disk of every output above u); the fronts of columns 0 and 1 came from the row before.
+#define RF_L2_GROUP_FIRST(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM)                                                 \
+    RF_L2_GROUP_M(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM, RF_L2_MID3, RF_L2_M7, RF_L2_M1, RF_L2_M15, RF_L2_M3,    \
+                  RF_L2_M15, RF_L2_M7, RF_L2_M15, RF_L2_M15)
+    // A row of one group (half-width 0, the disk's top and bottom rows) is first and last at once: the
+    // intersection [1, 2, 4, 8] - each output's own column.
+#define RF_L2_GROUP_SINGLE(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM)                                                \
+    RF_L2_GROUP_M(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM, RF_L2_MID3_LAST, RF_L2_M4, RF_L2_M1, RF_L2_M8,          \
+                  RF_L2_M2, RF_L2_M1, RF_L2_M4, RF_L2_M3, RF_L2_M8)
     // The two octets swap roles from group to group: a group in role A multiplies from w8a and loads the
     // next window into w8b, one in role B the other way round - no copy hands the window on.  Which octet
-    // holds the current window is a state of the control flow (`in_b`, tested once per row): the loop body
-    // is a PAIR of groups, A then B, a row that starts in role B runs one lone B group first, and the last
-    // group of a row - the one that reads ahead into the next row through ta_next / tb_next and loads its
-    // first window - exists in both roles, so rows with an odd number of groups need neither a padding
-    // group nor a copy and the next row simply starts in the other role.  Inside a pair the second group's
-    // ds_read2 offsets are the first group's plus one dword and ta / tb advance once, by 8 bytes.  The
-    // windows of a row descend by 16 bytes per group: woff = byte offset of the current window - 32, one
-    // s_sub per pair; the loads take woff + 16 and woff + 0 (never below 0 where used: a row's last
-    // window starts at float r4 + 3 - hw >= 4 of its table row).
+    // holds the current window is a state of the control flow (`in_b`, tested at the row top).  A row of two
+    // groups or more runs: its FIRST group in the role it starts in; where that was an A and more groups
+    // follow, one lone B group; PAIRS of groups, A then B; a lone A group where one is left over; and its
+    // LAST group - the one that reads ahead into the next row through ta_next / tb_next and loads its first
+    // window -, which exists in both roles, so rows with an odd number of groups need neither a padding
+    // group nor a copy and the next row simply starts in the other role.  A row of one group runs the SINGLE
+    // form in its role.  Inside a pair the second group's ds_read2 offsets are the first group's plus one
+    // dword and ta / tb advance once, by 8 bytes; a lone group advances them by 4.  The windows of a row
+    // descend by 16 bytes per group: woff = byte offset of the current window - 32, one s_sub per pair or
+    // lone group; the loads take woff + 16 and woff + 0 (never below 0 where used: a row's last window
+    // starts at float r4 + 3 - hw >= 4 of its table row).
 #define RF_L2_ROW_LOOP(F)                                                                                        \
     for (int i = i_lo; i <= i_hi; i++) {                                                                         \
         uint32_t ta_next, tb_next, wa_next;                                                                      \
@@ -764,39 +821,69 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
         }                                                                                                        \
         const uint32_t woff_next = wa_next * 4u;                                                                 \
         int m = ngroups - 1; /* groups before the row's last one */                                              \
-        const int b_first = in_b;                                                                                \
-        const int single_b = b_first & (int)(m == 0);                                                            \
-        if (!single_b) {                                                                                         \
-            if (b_first) {                                                                                       \
-                RF_L2_GROUP(F, w8b, w8a, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                \
-                ta += 4;                                                                                         \
-                tb += 4;                                                                                         \
-                woff -= 16;                                                                                      \
-                m--;                                                                                             \
-            }                                                                                                    \
-            for (int k = m >> 1; k > 0; k--) {                                                                   \
-                RF_L2_GROUP(F, w8a, w8b, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                \
-                RF_L2_GROUP(F, w8b, w8a, ta, tb, 2, Q4 + 2, woff, 0, RF_L2_MID3)                                 \
-                ta += 8;                                                                                         \
-                tb += 8;                                                                                         \
-                woff -= 32;                                                                                      \
-            }                                                                                                    \
-            if (m & 1) {                                                                                         \
-                RF_L2_GROUP(F, w8a, w8b, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                \
-            }                                                                                                    \
+        int first_a = (in_b ^ 1) & (int)(m > 0), first_b = in_b & (int)(m > 0);                                  \
+        int lone_b = in_b & (int)(m == 0); /* the role the remaining groups start in */                          \
+        if (first_a) {                                                                                           \
+            RF_L2_GROUP_FIRST(F, w8a, w8b, ta, tb, 1, Q4 + 1, woff, 16)                                          \
+            ta += 4;                                                                                             \
+            tb += 4;                                                                                             \
+            woff -= 16;                                                                                          \
+            m--;                                                                                                 \
+            lone_b = 1;                                                                                          \
         }                                                                                                        \
-        /* (two ifs, the second one on a value the compiler cannot see through: an if / else with a              \
-            statement of this loop in either arm is structurized into two ifs with the state BEFORE the          \
-            first arm kept alive for the second, which costs a copy of every register of the loop) */            \
-        int last_a = ((single_b | m) & 1) ^ 1;                                                                   \
-        if (!last_a) {                                                                                           \
-            RF_L2_GROUP(F, w8b, w8a, ta_next, tb_next, 0, Q4, woff_next, 0, RF_L2_MID3_LAST)                     \
+        /* (the two first-group tests stay two ifs as they are; an empty asm statement on first_b between them   \
+            does not compile - "illegal VGPR to SGPR copy", the compare result lives in VCC) */                  \
+        if (first_b) {                                                                                           \
+            RF_L2_GROUP_FIRST(F, w8b, w8a, ta, tb, 1, Q4 + 1, woff, 16)                                          \
+            ta += 4;                                                                                             \
+            tb += 4;                                                                                             \
+            woff -= 16;                                                                                          \
+            m--;                                                                                                 \
         }                                                                                                        \
-        asm volatile("" : "+s"(last_a));                                                                         \
-        in_b = __builtin_amdgcn_readfirstlane(last_a);                                                           \
-        if (in_b) {                                                                                              \
-            RF_L2_GROUP(F, w8a, w8b, ta_next, tb_next, 0, Q4, woff_next, 0, RF_L2_MID3_LAST)                     \
+        const int mid_b = lone_b & (int)(m > 0); /* (a row of one group has m == 0) */                           \
+        if (mid_b) {                                                                                             \
+            RF_L2_GROUP(F, w8b, w8a, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                    \
+            ta += 4;                                                                                             \
+            tb += 4;                                                                                             \
+            woff -= 16;                                                                                          \
+            m--;                                                                                                 \
+            lone_b = 0;                                                                                          \
         }                                                                                                        \
+        for (int k = m >> 1; k > 0; k--) {                                                                       \
+            RF_L2_GROUP(F, w8a, w8b, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                    \
+            RF_L2_GROUP(F, w8b, w8a, ta, tb, 2, Q4 + 2, woff, 0, RF_L2_MID3)                                     \
+            ta += 8;                                                                                             \
+            tb += 8;                                                                                             \
+            woff -= 32;                                                                                          \
+        }                                                                                                        \
+        if (m & 1) {                                                                                             \
+            RF_L2_GROUP(F, w8a, w8b, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                    \
+        }                                                                                                        \
+        /* the row's closing group: last or single, role A or B - four alternative ifs in sequence, each         \
+            but the first on a value the compiler cannot see through: an if / else with a statement of this      \
+            loop in either arm is structurized into two ifs with the state BEFORE the first arm kept alive       \
+            for the second, which costs a copy of every register of the loop */                                  \
+        const int last_a = ((lone_b | m) & 1) ^ 1;                                                               \
+        int sel = last_a | ((int)(ngroups == 1) << 1);                                                           \
+        if (sel == 0) {                                                                                          \
+            RF_L2_GROUP_LAST(F, w8b, w8a, ta_next, tb_next, 0, Q4, woff_next, 0)                                 \
+        }                                                                                                        \
+        asm volatile("" : "+s"(sel));                                                                            \
+        sel = __builtin_amdgcn_readfirstlane(sel);                                                               \
+        if (sel == 1) {                                                                                          \
+            RF_L2_GROUP_LAST(F, w8a, w8b, ta_next, tb_next, 0, Q4, woff_next, 0)                                 \
+        }                                                                                                        \
+        asm volatile("" : "+s"(sel));                                                                            \
+        sel = __builtin_amdgcn_readfirstlane(sel);                                                               \
+        if (sel == 2) {                                                                                          \
+            RF_L2_GROUP_SINGLE(F, w8b, w8a, ta_next, tb_next, 0, Q4, woff_next, 0)                               \
+        }                                                                                                        \
+        asm volatile("" : "+s"(sel));                                                                            \
+        sel = __builtin_amdgcn_readfirstlane(sel);                                                               \
+        if (sel == 3) {                                                                                          \
+            RF_L2_GROUP_SINGLE(F, w8a, w8b, ta_next, tb_next, 0, Q4, woff_next, 0)                               \
+        }                                                                                                        \
+        in_b = sel & 1;                                                                                          \
         ta = ta_next;                                                                                            \
         tb = tb_next;                                                                                            \
         woff = woff_next - 32u;                                                                                  \
@@ -818,13 +905,38 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
                    "+v"(gg[1][1]), "+v"(gg[1][2]), "+v"(gg[1][3]), "+v"(tp[0]), "+v"(tp[1]),
                    "+s"(w8a), "+s"(w8b), "+s"(hw_ahead));
 #undef RF_L2_ROW_LOOP
+#undef RF_L2_GROUP_SINGLE
+#undef RF_L2_GROUP_FIRST
+#undef RF_L2_GROUP_LAST
 #undef RF_L2_GROUP
+#undef RF_L2_GROUP_M
 #undef RF_L2_HALF
 #undef RF_L2_WLOAD_0
 #undef RF_L2_MID3
 #undef RF_L2_MID3_LAST
 #undef RF_L2_WLOAD_1
 #undef RF_L2_STEP_TXT
+#undef RF_L2_STR
+#undef RF_L2_STR_P
+#undef RF_L2_ON
+#undef RF_L2_ON_E
+#undef RF_L2_ON_P
+#undef RF_L2_ON_1
+#undef RF_L2_ON_0
+#undef RF_L2_SELK
+#undef RF_L2_SEL3
+#undef RF_L2_SEL2
+#undef RF_L2_SEL1
+#undef RF_L2_SEL0
+#undef RF_L2_M1
+#undef RF_L2_M2
+#undef RF_L2_M3
+#undef RF_L2_M4
+#undef RF_L2_M7
+#undef RF_L2_M8
+#undef RF_L2_M12
+#undef RF_L2_M14
+#undef RF_L2_M15
 #undef RF_L2_GATHER
 #undef RF_L2_SADD
 #undef RF_L2_SMUL
