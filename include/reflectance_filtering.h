@@ -433,6 +433,48 @@ int rf_png_deflate_ragged_u8(const uint8_t *images, int n, const int *heights, c
                              unsigned long long *stream_offsets, void *workspace,
                              size_t workspace_bytes, void *stream);
 
+/*
+ * The device half of a PNG decode: the inflated IDAT streams of n images of different sizes and
+ * formats to packed 8-bit BGR images (what cv2.imread returns), plus one flag byte per image.  The
+ * caller parses the files and inflates them (one serial zlib stream per file: host work); the entry
+ * undoes the row filters and unpacks the samples.
+ *   raw            device buffer holding the inflated streams: for image i the bytes
+ *                  [raw_offsets[i], raw_offsets[i + 1]), h rows of one filter byte and w * bpp
+ *                  filtered bytes.  OVERWRITTEN: the rows are reconstructed in place
+ *   raw_offsets    n + 1 uint64, HOST memory; raw_offsets[i + 1] - raw_offsets[i] must equal
+ *                  h * (1 + w * bpp)
+ *   heights, widths, formats  n ints each, HOST memory.  formats[i] = RF_PNG_FORMAT(bit depth,
+ *                  colour type): depth 8 or 16 with colour type 0 (grey), 2 (RGB), 4 (grey + alpha),
+ *                  6 (RGBA), or depth 8 with colour type 3 (palette); bpp = 1, 2, 3, 4, 6 or 8.  No
+ *                  interlace
+ *   palettes       device, 768 bytes per image (256 RGB entries, unused ones zero), read for the
+ *                  images of colour type 3 only; may be NULL where the list holds none
+ *   images         device, written: the n images tightly packed one after another, 3 bytes per
+ *                  pixel in BGR order (grey replicated, alpha dropped, the high byte of a 16-bit
+ *                  sample, the palette entry of an index); must not overlap raw
+ *   image_flags    device, n bytes, written: RF_PNG_FLAG_GREY where the three channels are equal at
+ *                  every pixel of the image, RF_PNG_FLAG_BAD_FILTER where a row's filter byte is
+ *                  above 4 (such a row is taken as filter 0; the call still returns RF_OK)
+ *   workspace      device scratch of at least rf_png_unfilter_workspace_bytes(...) bytes (48 + 4
+ *                  bytes per image, each part rounded up to 256), 16-byte aligned
+ * Refused before any device work: NULL pointers, n < 0, a size <= 0, an unsupported format
+ * (RF_E_UNSUPPORTED), a raw length that does not match, an image whose raw stream or pixel count
+ * reaches 2^31 (RF_E_UNSUPPORTED), a short (RF_E_WORKSPACE) or misaligned workspace, images
+ * overlapping raw.  The size query returns 0 for n <= 0 and for arguments the call refuses.  n == 0
+ * is RF_OK and touches nothing.  The bytes written are a function of the input alone.  Three
+ * launches per call whatever the list holds.  SYNCHRONISES THE STREAM once (before its launches, to
+ * upload the image table) and is refused (RF_E_UNSUPPORTED) on a capturing stream.
+ */
+#define RF_PNG_FORMAT(depth, ctype) (((depth) << 8) | (ctype))
+#define RF_PNG_FLAG_GREY 1       /* image_flags: all three channels equal at every pixel */
+#define RF_PNG_FLAG_BAD_FILTER 2 /* image_flags: a filter byte above 4 was seen */
+size_t rf_png_unfilter_workspace_bytes(int n, const int *heights, const int *widths,
+                                       const int *formats);
+int rf_png_unfilter_ragged_u8(uint8_t *raw, const unsigned long long *raw_offsets, int n,
+                              const int *heights, const int *widths, const int *formats,
+                              const uint8_t *palettes, uint8_t *images, uint8_t *image_flags,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ JBF_FORCE_GENERIC = 2
 JBF_GREY_AS_BGR = 4
 GF_GREY_AS_BGR = 1          # rf_gf_ex_u8: a 1-channel guide stands for three equal channels
 PNG_GREY_AS_RGB = 1         # rf_png_deflate_ragged_u8: a 1-channel image is written as three equal samples
+PNG_FLAG_GREY, PNG_FLAG_BAD_FILTER = 1, 2   # image_flags of rf_png_unfilter_ragged_u8
 CNN_NPARAMS = 4513
 CNN_NPACKED = 4673          # RF_CNN_NPACKED: floats of rf_cnn_pack_weights' output
 
@@ -35,7 +36,8 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
            "rf_whdr_points_u8", "rf_jbf_ragged_workspace_bytes", "rf_jbf_ragged_u8",
            "rf_colorize_ragged_workspace_bytes", "rf_colorize_ragged_srgb_u8",
            "rf_gf_ragged_workspace_bytes", "rf_gf_ragged_u8", "rf_png_stream_bound",
-           "rf_png_workspace_bytes", "rf_png_deflate_ragged_u8")
+           "rf_png_workspace_bytes", "rf_png_deflate_ragged_u8",
+           "rf_png_unfilter_workspace_bytes", "rf_png_unfilter_ragged_u8")
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
@@ -136,6 +138,10 @@ def load_library():
         lib.rf_png_workspace_bytes.restype = sz
         lib.rf_png_deflate_ragged_u8.argtypes = [vp, ci, vp, vp, ci, ci, vp, sz, vp, vp, sz, vp]
         lib.rf_png_deflate_ragged_u8.restype = ci
+        lib.rf_png_unfilter_workspace_bytes.argtypes = [ci, vp, vp, vp]
+        lib.rf_png_unfilter_workspace_bytes.restype = sz
+        lib.rf_png_unfilter_ragged_u8.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        lib.rf_png_unfilter_ragged_u8.restype = ci
         lib.rf_debug_png_plan.argtypes = [ci, vp, vp, ci, ci, vp, ci]
         lib.rf_debug_png_plan.restype = ci
         lib.rf_debug_option.argtypes = [ctypes.c_char_p, ci]

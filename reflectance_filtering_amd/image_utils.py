@@ -239,6 +239,68 @@ def _png_encode(image, level=1):
             + chunk(b"IDAT", deflated) + chunk(b"IEND", b""))
 
 
+def _png_parse(data):
+    view = memoryview(data)
+    if bytes(view[:8]) != _PNG_SIG:
+        return None
+    pos, idat, palette, header, ended = 8, [], None, None, False
+    while pos + 12 <= len(view):
+        (length,) = struct.unpack(">I", view[pos:pos + 4])
+        tag = bytes(view[pos + 4:pos + 8])
+        end = pos + 8 + length
+        if end + 4 > len(view):
+            return None                                   # a truncated chunk
+        if tag in (b"IHDR", b"PLTE", b"IDAT", b"IEND"):
+            (crc,) = struct.unpack(">I", view[end:end + 4])
+            if zlib.crc32(view[pos + 4:end]) & 0xFFFFFFFF != crc:
+                return None
+            if tag == b"IHDR":
+                if header is not None or length != 13:
+                    return None
+                header = struct.unpack(">IIBBBBB", view[pos + 8:end])
+            elif tag == b"PLTE":
+                if length == 0 or length % 3 or length > 768:
+                    return None
+                palette = np.frombuffer(view[pos + 8:end], np.uint8).reshape(-1, 3)
+            elif tag == b"IDAT":
+                idat.append(view[pos + 8:end])
+            else:
+                ended = True
+                break
+        pos = end + 4
+    if header is None or not ended or not idat:
+        return None
+    width, height, depth, ctype, compression, filtering, interlace = header
+    if compression or filtering or interlace or depth not in (8, 16):
+        return None
+    chans = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}.get(ctype)
+    if chans is None or (ctype == 3 and (depth != 8 or palette is None)):
+        return None
+    rowlen = 1 + width * chans * depth // 8
+    if width <= 0 or height <= 0 or height * rowlen >= 2 ** 31 or height * width >= 2 ** 31:
+        return None
+    raw = zlib.decompress(b"".join(idat))
+    if len(raw) != height * rowlen:
+        return None
+    if int(np.frombuffer(raw, np.uint8)[::rowlen].max()) > 4:   # the filter byte of every row
+        return None
+    return height, width, depth, ctype, (palette if ctype == 3 else None), raw
+
+
+def png_parse(data):
+    """The host half of a PNG decode whose device half is ops.png_decode_ragged_u8: signature, IHDR,
+    PLTE and all IDAT bodies joined and inflated (zlib releases the GIL), with the CRC of every
+    chunk used, the length of the inflated stream and the filter byte of every row checked.  Returns
+    (height, width, bit depth, colour type, palette [k,3] uint8 or None, raw bytes: per row one
+    filter byte and the filtered samples) - or None for anything the device route does not take
+    (interlace, bit depth 1, 2 or 4, an unknown colour type, a damaged file, not a PNG).  Never
+    raises for a bad file: the caller falls back to imread, which says what is wrong."""
+    try:
+        return _png_parse(data)
+    except Exception:
+        return None
+
+
 def png_container(stream, height, width, ctype):
     """A complete 8-bit PNG file around a finished zlib stream of its filtered rows (whoever deflated
     them - ops.png_encode_ragged_u8 does it on the device): signature, IHDR (colour type 0 grey or

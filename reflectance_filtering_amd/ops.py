@@ -15,12 +15,14 @@ _jbf_ragged_workspaces = {}
 _colorize_ragged_workspaces = {}
 _gf_ragged_workspaces = {}
 _png_workspaces = {}
+_png_decode_workspaces = {}
 
 
 def release_workspaces():
     """Drop the cached guided-filter, ragged-bilateral, ragged-colourise, ragged-guided and PNG-encode
     scratch buffers and CNN constants (device memory)."""
     _png_workspaces.clear()
+    _png_decode_workspaces.clear()
     del _png_host[:]
     _gf_workspaces.clear()
     _gf_ragged_workspaces.clear()
@@ -610,8 +612,9 @@ _png_threads = []
 
 
 def _png_host_buffer(need, torch):
-    """A page-locked host buffer of at least `need` bytes for the streams' way back (a copy into
-    pageable memory runs at a fraction of the link's rate); release_workspaces() drops it."""
+    """A page-locked host buffer of at least `need` bytes for the encoder's streams on their way back
+    and the decoder's raw streams on their way up (a copy from or into pageable memory runs at a
+    fraction of the link's rate); release_workspaces() drops it."""
     if not _png_host or _png_host[0].numel() < need:
         del _png_host[:]
         _png_host.append(torch.empty(max(need, 1 << 20), dtype=torch.uint8, pin_memory=True))
@@ -703,6 +706,68 @@ def png_encode_ragged_u8(images, sizes=None, grey_as_rgb=False):
     # the checksums of large streams run side by side (zlib.crc32 releases the GIL); every file is a
     # copy of its own, so the host buffer is free again when the call returns
     return list(_png_pool().map(lambda job: iu.png_container(*job), jobs))
+
+
+def png_decode_ragged_u8(parsed):
+    """The pixels of PNG files of different sizes and formats, reconstructed and unpacked on the
+    device in one call (rf_png_unfilter_ragged_u8: the row filters undone as a skewed wavefront, the
+    samples unpacked to BGR).  parsed: a list of n image_utils.png_parse results (height, width, bit
+    depth, colour type, palette or None, raw bytes).  The raw streams (and the palettes, if any)
+    cross in one upload from one page-locked staging buffer; what comes back is the n flag bytes.
+    Returns (images, grey): a list of n CUDA uint8 [H_i, W_i, 3] views (BGR, what image_utils.imread
+    returns for the file) of one packed tensor, and a list of n bools - the image's three channels
+    are equal at every pixel.  Raises RFError naming the image if a row's filter byte is above 4.
+    Synchronises the current stream."""
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    parsed = list(parsed)
+    n = len(parsed)
+    if n == 0:
+        return [], []
+    hs = np.ascontiguousarray([p[0] for p in parsed], dtype=np.int32)
+    wds = np.ascontiguousarray([p[1] for p in parsed], dtype=np.int32)
+    fmts = np.ascontiguousarray([(int(p[2]) << 8) | int(p[3]) for p in parsed], dtype=np.int32)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(p[5]) for p in parsed], dtype=np.uint64)
+    total = int(offs[-1])
+    with_palette = [i for i, p in enumerate(parsed) if p[4] is not None]
+    up = lambda b: (b + 255) & ~255
+    pal_bytes = 768 * n if with_palette else 0
+    staged = up(total) + pal_bytes
+    host = _png_host_buffer(staged, torch)
+    data = host.numpy()
+    for i, p in enumerate(parsed):
+        data[int(offs[i]):int(offs[i + 1])] = np.frombuffer(p[5], np.uint8)
+    if with_palette:
+        pals = data[up(total):staged].reshape(n, 768)
+        pals[:] = 0
+        for i in with_palette:
+            entries = np.asarray(parsed[i][4], dtype=np.uint8).reshape(-1)[:768]
+            pals[i, :entries.size] = entries
+    need = lib.rf_png_unfilter_workspace_bytes(n, hs.ctypes.data, wds.ctypes.data, fmts.ctypes.data)
+    # need == 0: the entry says why.  One cached buffer: workspace, flags, raw streams, palettes.
+    dev = torch.device("cuda", torch.cuda.current_device())
+    flags_at = up(need)
+    raw_at = flags_at + up(n)
+    buf = _stream_workspace(_png_decode_workspaces, raw_at + staged, dev, torch)
+    buf[raw_at:raw_at + staged].copy_(host[:staged], non_blocking=True)
+    npx = int((hs.astype(np.int64) * wds.astype(np.int64)).sum())
+    packed = torch.empty((max(npx, 0), 3), dtype=torch.uint8, device=dev)
+    rc = lib.rf_png_unfilter_ragged_u8(buf.data_ptr() + raw_at, offs.ctypes.data, n, hs.ctypes.data,
+                                       wds.ctypes.data, fmts.ctypes.data,
+                                       buf.data_ptr() + raw_at + up(total) if with_palette else None,
+                                       packed.data_ptr(), buf.data_ptr() + flags_at, buf.data_ptr(),
+                                       need, _ffi.current_stream_ptr(torch))
+    if rc != _ffi.RF_OK:   # refused before its synchronisation: the upload still reads the staging buffer
+        torch.cuda.current_stream(dev).synchronize()
+    _ffi.check(rc, "rf_png_unfilter_ragged_u8")
+    flags = buf[flags_at:flags_at + n].cpu().numpy()
+    bad = np.flatnonzero(flags & _ffi.PNG_FLAG_BAD_FILTER)
+    if bad.size:
+        raise _ffi.RFError("rf_png_unfilter_ragged_u8: image %d has a row filter byte above 4"
+                           % int(bad[0]))
+    sizes = np.stack([hs, wds], axis=1)
+    return split_packed(packed, sizes), [bool(f & _ffi.PNG_FLAG_GREY) for f in flags]
 
 
 def _chk_images_f32(t, name, torch):
