@@ -570,11 +570,14 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
     float sv[4];         // sv[u]: src value of column u as float
     uint32_t ta, tb, wa_addr;
     int ngroups;
+    int odd = 0;         // the parity of the current row's half-width (wave-uniform; RF_L2_ROW_LOOP)
     if constexpr (SLAB) {
         int hw0;
         const int *hp0 = hwtab + (i_lo + radius);
         asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(hw0) : "s"(hp0));
-        row_addr(i_lo, __builtin_amdgcn_readfirstlane(hw0), ta, tb, wa_addr, ngroups);
+        hw0 = __builtin_amdgcn_readfirstlane(hw0);
+        odd = hw0 & 1;
+        row_addr(i_lo, hw0, ta, tb, wa_addr, ngroups);
     } else {
         row_addr(-radius, 0, ta, tb, wa_addr, ngroups);  // (the top row of the disk: half-width 0)
     }
@@ -682,6 +685,7 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
 #define RF_L2_M3 (1, 1, 0, 0, 2)
 #define RF_L2_M2 (0, 1, 0, 0, 1)
 #define RF_L2_M1 (1, 0, 0, 0, 1)
+#define RF_L2_M0 (0, 0, 0, 0, 0)
 #define RF_L2_SEL0(A, B, C, D, K) A
 #define RF_L2_SEL1(A, B, C, D, K) B
 #define RF_L2_SEL2(A, B, C, D, K) C
@@ -792,6 +796,19 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
 #define RF_L2_GROUP_SINGLE(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM)                                                \
     RF_L2_GROUP_M(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM, RF_L2_MID3_LAST, RF_L2_M4, RF_L2_M1, RF_L2_M8,          \
                   RF_L2_M2, RF_L2_M1, RF_L2_M4, RF_L2_M3, RF_L2_M8)
+    // Rows of ODD half-width (hws = hw + 1): the row's first column lies left of the disk of all four outputs
+    // and the padding column at its end right of it - the live outputs are [0, 1, 3, 7] and [14, 12, 8, 0],
+    // one output less per column than the masks above, which are the union over both parities.  The first
+    // and the last group of such a row have forms of their own (an odd row has at least two groups): the
+    // step of the dead column issues no back half, the step that would form the dead column no gather (it
+    // ends in a full wait).  The last group goes on issuing the NEXT row's columns 0 and 1 with [1, 3]
+    // whatever that row's parity: the first group of either parity runs a subset of them.
+#define RF_L2_GROUP_FIRST_ODD(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM)                                             \
+    RF_L2_GROUP_M(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM, RF_L2_MID3, RF_L2_M3, RF_L2_M0, RF_L2_M7, RF_L2_M1,     \
+                  RF_L2_M15, RF_L2_M3, RF_L2_M15, RF_L2_M7)
+#define RF_L2_GROUP_LAST_ODD(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM)                                              \
+    RF_L2_GROUP_M(F, WC, WN, NA, NB, PA, PB, WOFF, WIMM, RF_L2_MID3_LAST, RF_L2_M8, RF_L2_M14, RF_L2_M0,         \
+                  RF_L2_M12, RF_L2_M1, RF_L2_M8, RF_L2_M3, RF_L2_M0)
     // The two octets swap roles from group to group: a group in role A multiplies from w8a and loads the
     // next window into w8b, one in role B the other way round - no copy hands the window on.  Which octet
     // holds the current window is a state of the control flow (`in_b`, tested at the row top).  A row of two
@@ -821,25 +838,41 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
         }                                                                                                        \
         const uint32_t woff_next = wa_next * 4u;                                                                 \
         int m = ngroups - 1; /* groups before the row's last one */                                              \
-        int first_a = (in_b ^ 1) & (int)(m > 0), first_b = in_b & (int)(m > 0);                                  \
-        int lone_b = in_b & (int)(m == 0); /* the role the remaining groups start in */                          \
-        if (first_a) {                                                                                           \
+        /* (hw_cur is the NEXT row's half-width until this row's last group takes over the one after) */        \
+        const int odd_next = __builtin_amdgcn_readfirstlane(hw_cur) & 1;                                         \
+        /* the row's first group: role A or B, even or odd half-width - four alternative ifs in sequence on a    \
+            value built without a compare (m > 0 as min(m, 1), an s_min: a compare result lives in VCC and does  \
+            not pass an empty asm statement, "illegal VGPR to SGPR copy", and the sign bit of -m is turned back  \
+            into one), each but the first behind the barrier of the closing forms below.  fsel 0: a row of one   \
+            group has no first group */                                                                          \
+        int has_first = m < 1 ? m : 1;                                                                           \
+        asm volatile("" : "+s"(has_first)); /* (a number from here on, not a condition) */                       \
+        int fsel = (1 + in_b + 2 * odd) & -has_first;                                                            \
+        if (fsel == 1) {                                                                                         \
             RF_L2_GROUP_FIRST(F, w8a, w8b, ta, tb, 1, Q4 + 1, woff, 16)                                          \
-            ta += 4;                                                                                             \
-            tb += 4;                                                                                             \
-            woff -= 16;                                                                                          \
-            m--;                                                                                                 \
-            lone_b = 1;                                                                                          \
         }                                                                                                        \
-        /* (the two first-group tests stay two ifs as they are; an empty asm statement on first_b between them   \
-            does not compile - "illegal VGPR to SGPR copy", the compare result lives in VCC) */                  \
-        if (first_b) {                                                                                           \
+        asm volatile("" : "+s"(fsel));                                                                           \
+        fsel = __builtin_amdgcn_readfirstlane(fsel);                                                             \
+        if (fsel == 2) {                                                                                         \
             RF_L2_GROUP_FIRST(F, w8b, w8a, ta, tb, 1, Q4 + 1, woff, 16)                                          \
-            ta += 4;                                                                                             \
-            tb += 4;                                                                                             \
-            woff -= 16;                                                                                          \
-            m--;                                                                                                 \
         }                                                                                                        \
+        asm volatile("" : "+s"(fsel));                                                                           \
+        fsel = __builtin_amdgcn_readfirstlane(fsel);                                                             \
+        if (fsel == 3) {                                                                                         \
+            RF_L2_GROUP_FIRST_ODD(F, w8a, w8b, ta, tb, 1, Q4 + 1, woff, 16)                                      \
+        }                                                                                                        \
+        asm volatile("" : "+s"(fsel));                                                                           \
+        fsel = __builtin_amdgcn_readfirstlane(fsel);                                                             \
+        if (fsel == 4) {                                                                                         \
+            RF_L2_GROUP_FIRST_ODD(F, w8b, w8a, ta, tb, 1, Q4 + 1, woff, 16)                                      \
+        }                                                                                                        \
+        /* what a first group leaves behind, without a branch: the addresses one group on, and the remaining    \
+            groups start in the other role (lone_b: they start in B) */                                          \
+        ta += 4 * has_first;                                                                                     \
+        tb += 4 * has_first;                                                                                     \
+        woff -= 16 * has_first;                                                                                  \
+        m -= has_first;                                                                                          \
+        int lone_b = in_b ^ has_first;                                                                           \
         const int mid_b = lone_b & (int)(m > 0); /* (a row of one group has m == 0) */                           \
         if (mid_b) {                                                                                             \
             RF_L2_GROUP(F, w8b, w8a, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                    \
@@ -859,12 +892,12 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
         if (m & 1) {                                                                                             \
             RF_L2_GROUP(F, w8a, w8b, ta, tb, 1, Q4 + 1, woff, 16, RF_L2_MID3)                                    \
         }                                                                                                        \
-        /* the row's closing group: last or single, role A or B - four alternative ifs in sequence, each         \
-            but the first on a value the compiler cannot see through: an if / else with a statement of this      \
-            loop in either arm is structurized into two ifs with the state BEFORE the first arm kept alive       \
-            for the second, which costs a copy of every register of the loop */                                  \
+        /* the row's closing group: last, single or last of an odd row, role A or B - six alternative ifs in     \
+            sequence, each but the first on a value the compiler cannot see through: an if / else with a         \
+            statement of this loop in either arm is structurized into two ifs with the state BEFORE the first    \
+            arm kept alive for the second, which costs a copy of every register of the loop */                   \
         const int last_a = ((lone_b | m) & 1) ^ 1;                                                               \
-        int sel = last_a | ((int)(ngroups == 1) << 1);                                                           \
+        int sel = last_a | ((int)(ngroups == 1) << 1) | (odd << 2); /* (an odd row is never a single) */         \
         if (sel == 0) {                                                                                          \
             RF_L2_GROUP_LAST(F, w8b, w8a, ta_next, tb_next, 0, Q4, woff_next, 0)                                 \
         }                                                                                                        \
@@ -883,7 +916,18 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
         if (sel == 3) {                                                                                          \
             RF_L2_GROUP_SINGLE(F, w8a, w8b, ta_next, tb_next, 0, Q4, woff_next, 0)                               \
         }                                                                                                        \
+        asm volatile("" : "+s"(sel));                                                                            \
+        sel = __builtin_amdgcn_readfirstlane(sel);                                                               \
+        if (sel == 4) {                                                                                          \
+            RF_L2_GROUP_LAST_ODD(F, w8b, w8a, ta_next, tb_next, 0, Q4, woff_next, 0)                             \
+        }                                                                                                        \
+        asm volatile("" : "+s"(sel));                                                                            \
+        sel = __builtin_amdgcn_readfirstlane(sel);                                                               \
+        if (sel == 5) {                                                                                          \
+            RF_L2_GROUP_LAST_ODD(F, w8a, w8b, ta_next, tb_next, 0, Q4, woff_next, 0)                             \
+        }                                                                                                        \
         in_b = sel & 1;                                                                                          \
+        odd = odd_next;                                                                                          \
         ta = ta_next;                                                                                            \
         tb = tb_next;                                                                                            \
         woff = woff_next - 32u;                                                                                  \
@@ -916,27 +960,9 @@ __device__ __forceinline__ void jbf_tap_loop_grey4_la2(uint32_t lut_lane_addr,
 #undef RF_L2_MID3_LAST
 #undef RF_L2_WLOAD_1
 #undef RF_L2_STEP_TXT
-#undef RF_L2_STR
-#undef RF_L2_STR_P
-#undef RF_L2_ON
-#undef RF_L2_ON_E
-#undef RF_L2_ON_P
-#undef RF_L2_ON_1
-#undef RF_L2_ON_0
-#undef RF_L2_SELK
-#undef RF_L2_SEL3
-#undef RF_L2_SEL2
-#undef RF_L2_SEL1
-#undef RF_L2_SEL0
-#undef RF_L2_M1
-#undef RF_L2_M2
-#undef RF_L2_M3
-#undef RF_L2_M4
-#undef RF_L2_M7
-#undef RF_L2_M8
-#undef RF_L2_M12
-#undef RF_L2_M14
-#undef RF_L2_M15
+    // (the live masks RF_L2_M* and RF_L2_ON stay defined for jbf_tap_loop_rgb6 below)
+#undef RF_L2_GROUP_LAST_ODD
+#undef RF_L2_GROUP_FIRST_ODD
 #undef RF_L2_GATHER
 #undef RF_L2_SADD
 #undef RF_L2_SMUL
@@ -1060,7 +1086,22 @@ __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
 #define RF_C6_MASKIN_MSAD
 #define RF_C6_SAD_AND(N) "v_sad_u8 %[a" #N "], %[tj], %[jc" #N "], 0\n\t"
 #define RF_C6_SAD_MSAD(N) "v_msad_u8 %[a" #N "], %[t1], %[jc" #N "], 0\n\t"
-#define RF_C6_STEP(F, U, GA, GB, TA, TB, OFFT, EXTRA_ASM, EXTRA_OPERANDS)                        \
+    // End groups, as in jbf_tap_loop_grey4_la2: FM = live outputs of the step's front half (SAD, address and
+    // gather of column U + 1), BM = those of its back half (the eight float instructions of column U); the
+    // texel reads, the three conversions and the step's full wait are not slots.  BM of a column is a subset
+    // of the FM its front half was issued with, one step earlier.
+#define RF_C6_WMUL(N) "v_mul_f32 %[w" #N "], %[wv" #N "], %[g" #N "]\n\t"
+#define RF_C6_WADD(N) "v_add_f32 %[ws" #N "], %[ws" #N "], %[w" #N "]\n\t"
+#define RF_C6_ADR(N) "v_lshl_add_u32 %[a" #N "], %[a" #N "], %[sh], %[la]\n\t"
+#define RF_C6_GATHER(N) "ds_read_b32 %[a" #N "], %[a" #N "]\n\t"
+#define RF_C6_CMUL(N, C) "v_mul_f32 %[m" #N "], %[w" #N "], %[s" #C "]\n\t"
+#define RF_C6_CADD(N, C) "v_add_f32 %[c" #N #C "], %[c" #N #C "], %[m" #N "]\n\t"
+#define RF_C6_CH(BM, C)                                                                          \
+    RF_L2_ON(BM, 0, RF_C6_CMUL(0, C)) RF_L2_ON(BM, 1, RF_C6_CMUL(1, C))                          \
+    RF_L2_ON(BM, 2, RF_C6_CMUL(2, C)) RF_L2_ON(BM, 3, RF_C6_CMUL(3, C))                          \
+    RF_L2_ON(BM, 0, RF_C6_CADD(0, C)) RF_L2_ON(BM, 1, RF_C6_CADD(1, C))                          \
+    RF_L2_ON(BM, 2, RF_C6_CADD(2, C)) RF_L2_ON(BM, 3, RF_C6_CADD(3, C))
+#define RF_C6_STEP(F, U, GA, GB, TA, TB, OFFT, EXTRA_ASM, EXTRA_OPERANDS, FM, BM)                \
     {                                                                                            \
         float w0_, w1_, w2_, w3_, s0_, s1_, s2_, m0_, m1_, m2_, m3_;                             \
         [[maybe_unused]] uint32_t tj_;                                                           \
@@ -1068,49 +1109,27 @@ __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
         asm volatile("ds_read_b32 %[tn], %[ta] offset:%[off4]\n\t"                               \
                      "ds_read_u16 %[tnb], %[tb] offset:%[off2]\n\t"                              \
                      RF_C6_AND_##F                                                               \
-                     RF_C6_SAD_##F(0) "v_mul_f32 %[w0], %[wv0], %[g0]\n\t"                       \
-                     RF_C6_SAD_##F(1) "v_mul_f32 %[w1], %[wv1], %[g1]\n\t"                       \
-                     RF_C6_SAD_##F(2) "v_mul_f32 %[w2], %[wv2], %[g2]\n\t"                       \
-                     RF_C6_SAD_##F(3) "v_mul_f32 %[w3], %[wv3], %[g3]\n\t"                       \
+                     RF_L2_ON(FM, 0, RF_C6_SAD_##F(0)) RF_L2_ON(BM, 0, RF_C6_WMUL(0))            \
+                     RF_L2_ON(FM, 1, RF_C6_SAD_##F(1)) RF_L2_ON(BM, 1, RF_C6_WMUL(1))            \
+                     RF_L2_ON(FM, 2, RF_C6_SAD_##F(2)) RF_L2_ON(BM, 2, RF_C6_WMUL(2))            \
+                     RF_L2_ON(FM, 3, RF_C6_SAD_##F(3)) RF_L2_ON(BM, 3, RF_C6_WMUL(3))            \
                      "v_cvt_f32_ubyte3 %[s0], %[t0]\n\t"                                         \
-                     "v_add_f32 %[ws0], %[ws0], %[w0]\n\t"                                       \
+                     RF_L2_ON(BM, 0, RF_C6_WADD(0))                                              \
                      "v_cvt_f32_ubyte0 %[s1], %[tb0]\n\t"                                        \
-                     "v_add_f32 %[ws1], %[ws1], %[w1]\n\t"                                       \
+                     RF_L2_ON(BM, 1, RF_C6_WADD(1))                                              \
                      "v_cvt_f32_ubyte1 %[s2], %[tb0]\n\t"                                        \
-                     "v_add_f32 %[ws2], %[ws2], %[w2]\n\t"                                       \
-                     "v_lshl_add_u32 %[a0], %[a0], %[sh], %[la]\n\t"                             \
-                     "v_add_f32 %[ws3], %[ws3], %[w3]\n\t"                                       \
-                     "v_lshl_add_u32 %[a1], %[a1], %[sh], %[la]\n\t"                             \
-                     "v_mul_f32 %[m0], %[w0], %[s0]\n\t"                                         \
-                     "v_lshl_add_u32 %[a2], %[a2], %[sh], %[la]\n\t"                             \
-                     "v_mul_f32 %[m1], %[w1], %[s0]\n\t"                                         \
-                     "v_lshl_add_u32 %[a3], %[a3], %[sh], %[la]\n\t"                             \
-                     "v_mul_f32 %[m2], %[w2], %[s0]\n\t"                                         \
-                     "ds_read_b32 %[a0], %[a0]\n\t"                                              \
-                     "ds_read_b32 %[a1], %[a1]\n\t"                                              \
-                     "ds_read_b32 %[a2], %[a2]\n\t"                                              \
-                     "ds_read_b32 %[a3], %[a3]\n\t"                                              \
-                     "v_mul_f32 %[m3], %[w3], %[s0]\n\t"                                         \
-                     "v_add_f32 %[c00], %[c00], %[m0]\n\t"                                       \
-                     "v_add_f32 %[c10], %[c10], %[m1]\n\t"                                       \
-                     "v_add_f32 %[c20], %[c20], %[m2]\n\t"                                       \
-                     "v_add_f32 %[c30], %[c30], %[m3]\n\t"                                       \
-                     "v_mul_f32 %[m0], %[w0], %[s1]\n\t"                                         \
-                     "v_mul_f32 %[m1], %[w1], %[s1]\n\t"                                         \
-                     "v_mul_f32 %[m2], %[w2], %[s1]\n\t"                                         \
-                     "v_mul_f32 %[m3], %[w3], %[s1]\n\t"                                         \
-                     "v_add_f32 %[c01], %[c01], %[m0]\n\t"                                       \
-                     "v_add_f32 %[c11], %[c11], %[m1]\n\t"                                       \
-                     "v_add_f32 %[c21], %[c21], %[m2]\n\t"                                       \
-                     "v_add_f32 %[c31], %[c31], %[m3]\n\t"                                       \
-                     "v_mul_f32 %[m0], %[w0], %[s2]\n\t"                                         \
-                     "v_mul_f32 %[m1], %[w1], %[s2]\n\t"                                         \
-                     "v_mul_f32 %[m2], %[w2], %[s2]\n\t"                                         \
-                     "v_mul_f32 %[m3], %[w3], %[s2]\n\t"                                         \
-                     "v_add_f32 %[c02], %[c02], %[m0]\n\t"                                       \
-                     "v_add_f32 %[c12], %[c12], %[m1]\n\t"                                       \
-                     "v_add_f32 %[c22], %[c22], %[m2]\n\t"                                       \
-                     "v_add_f32 %[c32], %[c32], %[m3]\n\t"                                       \
+                     RF_L2_ON(BM, 2, RF_C6_WADD(2))                                              \
+                     RF_L2_ON(FM, 0, RF_C6_ADR(0)) RF_L2_ON(BM, 3, RF_C6_WADD(3))                \
+                     RF_L2_ON(FM, 1, RF_C6_ADR(1)) RF_L2_ON(BM, 0, RF_C6_CMUL(0, 0))             \
+                     RF_L2_ON(FM, 2, RF_C6_ADR(2)) RF_L2_ON(BM, 1, RF_C6_CMUL(1, 0))             \
+                     RF_L2_ON(FM, 3, RF_C6_ADR(3)) RF_L2_ON(BM, 2, RF_C6_CMUL(2, 0))             \
+                     RF_L2_ON(FM, 0, RF_C6_GATHER(0)) RF_L2_ON(FM, 1, RF_C6_GATHER(1))           \
+                     RF_L2_ON(FM, 2, RF_C6_GATHER(2)) RF_L2_ON(FM, 3, RF_C6_GATHER(3))           \
+                     RF_L2_ON(BM, 3, RF_C6_CMUL(3, 0))                                           \
+                     RF_L2_ON(BM, 0, RF_C6_CADD(0, 0)) RF_L2_ON(BM, 1, RF_C6_CADD(1, 0))         \
+                     RF_L2_ON(BM, 2, RF_C6_CADD(2, 0)) RF_L2_ON(BM, 3, RF_C6_CADD(3, 0))         \
+                     RF_C6_CH(BM, 1)                                                             \
+                     RF_C6_CH(BM, 2)                                                             \
                      "s_waitcnt lgkmcnt(0)"                                                      \
                      : [tn] "=&v"(tq[((U) + 2) & 3]), [tnb] "=&v"(tqb[((U) + 2) & 3]),           \
                        RF_C6_TJOUT_##F [a0] "=&v"(GB[0]), [a1] "=&v"(GB[1]), [a2] "=&v"(GB[2]),  \
@@ -1140,40 +1159,65 @@ __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
         asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=&s"(wn8) : "s"(wp_));                      \
     }
 
-#define RF_C6_ROW_LOOP(F)                                                                           \
+    // One group of four steps: steps 0, 1 read columns 2, 3 through (ta, tb), steps 2, 3 read columns 0, 1 of
+    // the next group - or of the next row's first one - through (TA2, TB2) at the offsets O2, O3; step 3
+    // requests the window at index WIDX, which the group hands on by copy.  F0 B0 .. F3 B3: the front and back
+    // masks of the steps.  First group of a row: backs [1, 3, 7, 15], the fronts of its columns 1..3 [3, 7, 15]
+    // (column 0's came from the row before); last group: backs [15, 14, 12, 8], fronts [14, 12, 8] and [1] for
+    // the next row's column 0; a row of one group: backs [1, 2, 4, 8], fronts [3, 4, 8] and [1].
+#define RF_C6_GROUP(F, TA2, TB2, O2, O3, WIDX, F0, B0, F1, B1, F2, B2, F3, B3)                              \
+    {                                                                                                       \
+        float wv[8];                                                                                        \
+        wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];                                     \
+        wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];                                     \
+        RF_C6_STEP(F, 0, gg[0], gg[1], ta, tb, 0, RF_C6_NOASM, , F0, B0)                                    \
+        RF_C6_STEP(F, 1, gg[1], gg[0], ta, tb, Q4, RF_C6_NOASM, , F1, B1)                                   \
+        RF_C6_STEP(F, 2, gg[0], gg[1], TA2, TB2, O2, RF_C6_NOASM, , F2, B2)                                 \
+        RF_C6_STEP(F, 3, gg[1], gg[0], TA2, TB2, O3, RF_C6_LOAD_WINDOW(WIDX), RF_C6_COMMA_W, F3, B3)        \
+        ws8 = wn8;                                                                                          \
+    }
+#define RF_C6_ROW_LOOP(F)                                                                         \
     for (int i = i_lo; i <= i_hi; i++) {                                                            \
         uint32_t ta_next, tb_next, ta2_next, tb2_next, wa_next;                                     \
         int ngroups_next;                                                                           \
         row_addr(i < i_hi ? i + 1 : i, ta_next, tb_next, ta2_next, tb2_next, wa_next,               \
                  ngroups_next);                                                                     \
-        for (int gq = 0; gq < ngroups - 1; gq++) {                                                  \
-            float wv[8];                                                                            \
-            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];                         \
-            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];                         \
-            RF_C6_STEP(F, 0, gg[0], gg[1], ta, tb, 0, RF_C6_NOASM, )                                \
-            RF_C6_STEP(F, 1, gg[1], gg[0], ta, tb, Q4, RF_C6_NOASM, )                               \
-            RF_C6_STEP(F, 2, gg[0], gg[1], ta2, tb2, 1, RF_C6_NOASM, )                              \
-            wa_addr -= 4;                                                                           \
-            RF_C6_STEP(F, 3, gg[1], gg[0], ta2, tb2, Q4 + 1, RF_C6_LOAD_WINDOW(wa_addr),            \
-                       RF_C6_COMMA_W)                                                               \
-            ws8 = wn8;                                                                              \
-            ta += 4;                                                                                \
-            tb += 2;                                                                                \
-            ta2 += 4;                                                                               \
-            tb2 += 2;                                                                               \
-        }                                                                                           \
-        {                                                                                           \
-            float wv[8];                                                                            \
-            wv[0] = ws8[0]; wv[1] = ws8[1]; wv[2] = ws8[2]; wv[3] = ws8[3];                         \
-            wv[4] = ws8[4]; wv[5] = ws8[5]; wv[6] = ws8[6]; wv[7] = ws8[7];                         \
-            RF_C6_STEP(F, 0, gg[0], gg[1], ta, tb, 0, RF_C6_NOASM, )                                \
-            RF_C6_STEP(F, 1, gg[1], gg[0], ta, tb, Q4, RF_C6_NOASM, )                               \
-            /* the columns past the end of this row carry no weight: the next row's first two */    \
-            RF_C6_STEP(F, 2, gg[0], gg[1], ta2_next, tb2_next, 0, RF_C6_NOASM, )                    \
-            RF_C6_STEP(F, 3, gg[1], gg[0], ta2_next, tb2_next, Q4, RF_C6_LOAD_WINDOW(wa_next),      \
-                       RF_C6_COMMA_W)                                                               \
-            ws8 = wn8;                                                                              \
-        }                                                                                           \
+        /* first group, full groups, last group; a row of one group (half-width 0) runs the single form    \
+            instead.  Ifs without else, each but the first on a value the compiler cannot see through (see  \
+            RF_L2_ROW_LOOP: an if / else around statements of the loop costs a copy of its registers). */   \
+        int csel = ngroups < 2 ? ngroups : 2; /* 1: one group; 2: two or more */                            \
+        if (csel == 2) {                                                                                    \
+            wa_addr -= 4;                                                                                   \
+            RF_C6_GROUP(F, ta2, tb2, 1, Q4 + 1, wa_addr, RF_L2_M3, RF_L2_M1, RF_L2_M7, RF_L2_M3,            \
+                        RF_L2_M15, RF_L2_M7, RF_L2_M15, RF_L2_M15)                                          \
+            ta += 4;                                                                                        \
+            tb += 2;                                                                                        \
+            ta2 += 4;                                                                                       \
+            tb2 += 2;                                                                                       \
+        }                                                                                                   \
+        for (int gq = ngroups - 2; gq > 0; gq--) {                                                          \
+            wa_addr -= 4;                                                                                   \
+            RF_C6_GROUP(F, ta2, tb2, 1, Q4 + 1, wa_addr, RF_L2_M15, RF_L2_M15, RF_L2_M15, RF_L2_M15,        \
+                        RF_L2_M15, RF_L2_M15, RF_L2_M15, RF_L2_M15)                                         \
+            ta += 4;                                                                                        \
+            tb += 2;                                                                                        \
+            ta2 += 4;                                                                                       \
+            tb2 += 2;                                                                                       \
+        }                                                                                                   \
+        /* the closing group reads ahead into the next row: the columns past the end of this row carry no   \
+            weight, steps 2 and 3 read the next row's columns 0 and 1, step 3 forms its column 0 [1] */      \
+        asm volatile("" : "+s"(csel));                                                                      \
+        csel = __builtin_amdgcn_readfirstlane(csel);                                                        \
+        if (csel == 2) {                                                                                    \
+            RF_C6_GROUP(F, ta2_next, tb2_next, 0, Q4, wa_next, RF_L2_M14, RF_L2_M15, RF_L2_M12, RF_L2_M14,  \
+                        RF_L2_M8, RF_L2_M12, RF_L2_M1, RF_L2_M8)                                            \
+        }                                                                                                   \
+        asm volatile("" : "+s"(csel));                                                                      \
+        csel = __builtin_amdgcn_readfirstlane(csel);                                                        \
+        if (csel == 1) {                                                                                    \
+            RF_C6_GROUP(F, ta2_next, tb2_next, 0, Q4, wa_next, RF_L2_M3, RF_L2_M1, RF_L2_M4, RF_L2_M2,      \
+                        RF_L2_M8, RF_L2_M4, RF_L2_M1, RF_L2_M8)                                             \
+        }                                                                                                   \
         ta = ta_next;                                                                               \
         tb = tb_next;                                                                               \
         ta2 = ta2_next;                                                                             \
@@ -1199,7 +1243,38 @@ __device__ __forceinline__ void jbf_tap_loop_rgb6(uint32_t lut_lane_addr,
 #undef RF_C6_COMMA_W
 #undef RF_C6_NOASM
 #undef RF_C6_STEP
+#undef RF_C6_GROUP
+#undef RF_C6_CH
+#undef RF_C6_CADD
+#undef RF_C6_CMUL
+#undef RF_C6_GATHER
+#undef RF_C6_ADR
+#undef RF_C6_WADD
+#undef RF_C6_WMUL
 }
+// the live masks of the end groups, shared by jbf_tap_loop_grey4_la2 and jbf_tap_loop_rgb6
+#undef RF_L2_STR
+#undef RF_L2_STR_P
+#undef RF_L2_ON
+#undef RF_L2_ON_E
+#undef RF_L2_ON_P
+#undef RF_L2_ON_1
+#undef RF_L2_ON_0
+#undef RF_L2_SELK
+#undef RF_L2_SEL3
+#undef RF_L2_SEL2
+#undef RF_L2_SEL1
+#undef RF_L2_SEL0
+#undef RF_L2_M0
+#undef RF_L2_M1
+#undef RF_L2_M2
+#undef RF_L2_M3
+#undef RF_L2_M4
+#undef RF_L2_M7
+#undef RF_L2_M8
+#undef RF_L2_M12
+#undef RF_L2_M14
+#undef RF_L2_M15
 #undef RF_LDS_READ_B64
 #undef RF_LDS_READ_B128
 #undef RF_LDS_READ_B32
