@@ -284,6 +284,25 @@ int rf_colorize_ragged_srgb_u8(const uint8_t *bgr, const float *r, uint8_t *refl
                                void *stream);
 
 /*
+ * rf_colorize_ragged_srgb_u8 of an 8-bit reflectance map - a filtered `-r.png` that is on the device
+ * already: the reflectance of a pixel is the float32 nearest to byte / 255 (__fdiv_rn((float)byte,
+ * 255.0f), the convention of rf_whdr_points_u8), formed in registers by the eight histogram passes
+ * and the write pass, which read one byte per pixel; no float copy of the map exists.
+ *   r8           one uint8 per pixel, packed like bgr.  Byte 0 is r == 0 of rf_colorize_srgb_u8:
+ *                the shading is +inf, a black pixel gives NaN, and a result holding a NaN is written
+ *                without normalisation.
+ * Every other argument, the workspace (rf_colorize_ragged_workspace_bytes), the refusals - all
+ * decided before any device work -, the one synchronisation of `stream`, the refusal on a capturing
+ * stream and n == 0 are those of rf_colorize_ragged_srgb_u8.  The bytes written are, for every input,
+ * those of rf_colorize_ragged_srgb_u8 given the float32 array (float)r8[i] / 255.0f.
+ */
+int rf_colorize_ragged_r8_srgb_u8(const uint8_t *bgr, const uint8_t *r8, uint8_t *refl_out,
+                                  uint8_t *shading_out, int n, const int *heights, const int *widths,
+                                  const unsigned long long *k_refl, const unsigned long long *k_shading,
+                                  const double *srgb_steps, void *workspace, size_t workspace_bytes,
+                                  void *stream);
+
+/*
  * CV_32F variants of the two filters (never reached by the reference's CLIs, whose images come
  * from cv2.imread as uint8; provided so that callers which stop quantising between stages keep
  * the cv2.ximgproc semantics).  Same layouts as the 8-bit entry points with float pixels.

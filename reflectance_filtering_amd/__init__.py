@@ -20,5 +20,5 @@ from . import whdr  # noqa: F401
 from .filter_reflectance import (  # noqa: F401
     apply_filter, apply_filter_batch, apply_filter_list, read_filter_write)
 from .decompose_with_trained_CNN import (  # noqa: F401
-    decompose_and_filter_batch, decompose_and_filter_list, decompose_batch, decompose_image, decompose_list,
-    get_reflectance_batch, get_reflectance_caffe)
+    decompose_and_filter_batch, decompose_and_filter_list, decompose_batch, decompose_filter_list,
+    decompose_filter_packed, decompose_image, decompose_list, get_reflectance_batch, get_reflectance_caffe)

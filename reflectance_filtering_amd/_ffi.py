@@ -37,7 +37,8 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
            "rf_colorize_ragged_workspace_bytes", "rf_colorize_ragged_srgb_u8",
            "rf_gf_ragged_workspace_bytes", "rf_gf_ragged_u8", "rf_png_stream_bound",
            "rf_png_workspace_bytes", "rf_png_deflate_ragged_u8",
-           "rf_png_unfilter_workspace_bytes", "rf_png_unfilter_ragged_u8")
+           "rf_png_unfilter_workspace_bytes", "rf_png_unfilter_ragged_u8",
+           "rf_colorize_ragged_r8_srgb_u8")
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
@@ -104,6 +105,8 @@ def load_library():
         lib.rf_colorize_ragged_workspace_bytes.restype = sz
         lib.rf_colorize_ragged_srgb_u8.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]
         lib.rf_colorize_ragged_srgb_u8.restype = ci
+        lib.rf_colorize_ragged_r8_srgb_u8.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]
+        lib.rf_colorize_ragged_r8_srgb_u8.restype = ci
         lib.rf_jbf_f32_workspace_bytes.argtypes = [ci, ci]
         lib.rf_jbf_f32_workspace_bytes.restype = sz
         lib.rf_jbf_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, cd, cd, ci, vp, sz, vp]

@@ -20,6 +20,17 @@ is still cut into runs of equal size, one batch per run.  No collective is invol
     python -m torch.distributed.run --nproc-per-node 8 -m reflectance_filtering_amd.batch \
         decompose --inputs 'photos/*.png' --path_out out
 
+    python -m reflectance_filtering_amd.batch decompose_filter --inputs 'photos/*.png' \
+        --path_out out --filter_type=bilateral --sigma_color=20 --sigma_spatial=22
+
+`decompose_filter` is both tools in one pass over the photos: a step goes through
+decompose_with_trained_CNN.decompose_filter_packed (one CNN pass, the ragged filter routes, two ragged
+colourises) and writes what `decompose` writes, what `filter` makes of its `-r.png` outputs, and the
+colour reflectance and shading derived from the filtered map (`<filtered stem>-r_colorized.png`,
+`-s_colorized.png`).  Every photo is decoded once and no `-r.png` is read back.  Its `--guidance` is
+omitted (the CNN map guides itself), `image` (the photo guides) or a pattern evaluated on the photo's
+path.
+
 `--png_encoder device` deflates the `.png` outputs on the device and `--png_decoder device` leaves
 only parsing and inflate of the `.png` inputs to the I/O threads (the device undoes the row filters
 and unpacks the samples); both default to `host`, and the pixels are the same either way.
@@ -455,6 +466,111 @@ def decompose_files(inputs, path_out, rank=None, world=None, png_encoder="host",
     return firsts
 
 
+def decompose_filter_names(filename_in, path_out, filter_type, sigma_color, sigma_spatial, iterations=1):
+    """The six files decompose_filter_files writes for one photo, in the order it writes them: the
+    three of `decompose`, the file `filter` makes of `<base>-r.png` in `iterations` chained runs (the
+    suffix once per pass), and that file's stem + `-r_colorized.png` / `-s_colorized.png`."""
+    base = os.path.splitext(os.path.basename(filename_in))[0]
+    first = os.path.join(path_out, base + "-r.png")
+    filtered = first
+    for _ in range(iterations):
+        filtered = fr.output_filename(filtered, path_out, filter_type, sigma_color, sigma_spatial)
+    stem = os.path.splitext(filtered)[0]
+    return (first, os.path.join(path_out, base + "-r_colorized.png"),
+            os.path.join(path_out, base + "-s_colorized.png"), filtered,
+            stem + "-r_colorized.png", stem + "-s_colorized.png")
+
+
+def decompose_filter_files(inputs, path_out, filter_type, sigma_color, sigma_spatial,
+                           guidance_pattern=None, iterations=1, rank=None, world=None,
+                           png_encoder="host", png_decoder="host", colorize_filtered=True):
+    """`decompose` and `filter` of its `-r.png` outputs in one pass over this rank's share of the
+    photos `inputs`, plus the decomposition derived from the filtered map
+    (decompose_with_trained_CNN.decompose_filter_packed, one call per step): every photo - and
+    guidance file - is decoded once and no `-r.png` is read back.  guidance_pattern: None - the CNN
+    map guides itself; "image" - the photo guides; anything else is a guidance_for pattern evaluated
+    on the photo's path.  Writes the files of decompose_filter_names per photo: the first three are
+    the bytes of decompose_files, the fourth those of filter_files on `<base>-r.png` with the same
+    guidance (the grey map as three equal channels), the last two
+    imwrite(colorize(float32(filtered) / 255, photo), sRGB=True) (left out with
+    colorize_filtered=False).  png_encoder / png_decoder as in filter_files.  Returns the names of the
+    filtered files."""
+    import torch
+    from . import decompose_with_trained_CNN as dc
+    fr._check_params(filter_type, sigma_color, sigma_spatial)
+    if iterations < 1:
+        raise ValueError("iterations must be >= 1")
+    on_device = _check_png_encoder(png_encoder)
+    decode_on_device = _check_png_decoder(png_decoder)
+    mine = my_slice(inputs, rank, world)
+    read = _read_for_device if decode_on_device else iu.imread
+    filtered_names = []
+
+    def load(f):
+        g = None if guidance_pattern in (None, "image") else guidance_for(f, guidance_pattern)
+        # a guidance file that is the photo itself is read and decoded once
+        return f, read(f), (None if g is None or g == f else read(g)), g == f
+
+    def compute(loaded):
+        if decode_on_device:
+            flat = []
+            for _, img, gui, _ in loaded:
+                flat.extend((img,) if gui is None else (img, gui))
+            dec = iter(_decode_step(flat, torch))
+            step = []
+            for f, _, gui, own in loaded:
+                img = next(dec)[0]
+                step.append((f, img, None if gui is None else next(dec), own))
+            greys = [t[2][1] for t in step if t[2] is not None]
+            step = [(f, img, None if gui is None else gui[0], own) for f, img, gui, own in step]
+        else:
+            greys = [_is_grey(t[2]) for t in loaded if t[2] is not None]
+            step = [(f, torch.from_numpy(img).cuda(), None if gui is None else torch.from_numpy(gui).cuda(),
+                     own) for f, img, gui, own in loaded]
+        photos = [t[1] for t in step]
+        if guidance_pattern is None:
+            guidance = None
+        elif guidance_pattern == "image":
+            guidance = "image"
+        else:
+            # as filter_files: a step of grey guidance files is read as one channel standing for three
+            grey_gui = all(greys) and not any(t[3] for t in step)
+            guidance = []
+            for f, photo, gui, own in step:
+                gui = photo if own else gui
+                if tuple(gui.shape[:2]) != tuple(photo.shape[:2]):
+                    raise ValueError("input {} and its guidance differ in size".format(f))
+                guidance.append(gui[..., :1].contiguous() if grey_gui else gui)
+        res = dc.decompose_filter_packed(photos, sigma_color, sigma_spatial, filter_type, guidance,
+                                         iterations, colorize_filtered=colorize_filtered)
+        names = [decompose_filter_names(t[0], path_out, filter_type, sigma_color, sigma_spatial, iterations)
+                 for t in step]
+        filtered_names.extend(n[3] for n in names)
+        kinds = [res.r_u8, res.reflectance, res.shading, res.filtered]
+        if colorize_filtered:
+            kinds += [res.filtered_reflectance, res.filtered_shading]
+        jobs = []
+        if on_device:
+            files = [ops.png_encode_ragged_u8(t, sizes=res.sizes, grey_as_rgb=(k == 3))
+                     for k, t in enumerate(kinds)]
+            for i, n in enumerate(names):
+                jobs.extend((n[k], files[k][i]) for k in range(len(kinds)))
+            return jobs
+        kinds = [t.cpu().numpy() for t in kinds]
+        first = 0
+        for n, (h, w) in zip(names, res.sizes.tolist()):
+            px = slice(first, first + h * w)
+            for k, a in enumerate(kinds):
+                a = a[px].reshape((h, w, 3) if a.ndim == 2 else (h, w))
+                # the filtered grey map as three equal channels, as filter_files writes it
+                jobs.append((n[k], np.repeat(a[:, :, None], 3, axis=2) if k == 3 else a))
+            first += h * w
+        return jobs
+
+    pipeline(mine, load, compute)
+    return filtered_names
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description="Batched, multi-GPU front-end of the two tools.")
     sub = parser.add_subparsers(dest="command")
@@ -473,7 +589,20 @@ def build_parser():
     d.add_argument("--path_out", required=True)
     d.add_argument("--png_encoder", choices=PNG_ENCODERS, default="host",
                    help="who deflates the three .png outputs per photo")
-    for p in (f, d):
+    c = sub.add_parser("decompose_filter", help="decompose, filter the CNN map and colourise the "
+                                                "filtered map: every photo decoded once")
+    c.add_argument("--inputs", nargs="+", required=True, help="photos: files or glob patterns")
+    c.add_argument("--path_out", required=True)
+    c.add_argument("--filter_type", default="bilateral")
+    c.add_argument("--sigma_color", type=float, default=20.0)
+    c.add_argument("--sigma_spatial", type=float, default=22.0)
+    c.add_argument("--guidance", default=None,
+                   help="omitted: the CNN map guides itself; `image`: the photo guides; anything else: "
+                        "a pattern for the guidance file, evaluated on the photo's path")
+    c.add_argument("--iterations", type=int, default=1)
+    c.add_argument("--png_encoder", choices=PNG_ENCODERS, default="host",
+                   help="who deflates the six .png outputs per photo")
+    for p in (f, d, c):
         p.add_argument("--png_decoder", choices=PNG_DECODERS, default="host",
                        help="who undoes the row filters of the .png inputs and unpacks them: the I/O "
                             "threads, or the device (the threads then only parse and inflate)")
@@ -494,6 +623,11 @@ def main(argv=None):
         out = filter_files(args.filter_type, files, args.guidance, args.sigma_color,
                            args.sigma_spatial, args.path_out, iterations=args.iterations,
                            png_encoder=args.png_encoder, png_decoder=args.png_decoder)
+    elif args.command == "decompose_filter":
+        out = decompose_filter_files(files, args.path_out, args.filter_type, args.sigma_color,
+                                     args.sigma_spatial, guidance_pattern=args.guidance,
+                                     iterations=args.iterations, png_encoder=args.png_encoder,
+                                     png_decoder=args.png_decoder)
     else:
         out = decompose_files(files, args.path_out, png_encoder=args.png_encoder,
                               png_decoder=args.png_decoder)

@@ -21,6 +21,7 @@
 //    step function with at most 255 steps on the power branch, so the host computes the 255 step
 //    positions once with numpy itself (image_utils.srgb_write_steps) and the kernel counts the
 //    steps at or below x: exact for whatever libm the host has.
+#include <type_traits>
 #include <vector>
 
 #include "reflectance_filtering_debug.h"
@@ -50,6 +51,12 @@ __device__ inline void pixel_values(const uint8_t *px, float r, double (&refl)[3
     for (int c = 0; c < 3; c++)
         refl[c] = __ddiv_rn((double)px[c], den);
 }
+
+// The reflectance the kernels divide by: the float32 of the CNN as it is, or, for the entries that
+// read an 8-bit map (rf_colorize_ragged_r8_srgb_u8), the float32 nearest to byte / 255 - the
+// convention of rf_whdr_points_u8 - formed in registers from the one byte read per pixel.
+__device__ __forceinline__ float reflectance_of(float r) { return r; }
+__device__ __forceinline__ float reflectance_of(uint8_t r) { return __fdiv_rn((float)r, 255.0f); }
 
 // what a call's first kernel leaves in one (image, target) state: everything the passes read
 __device__ __forceinline__ void init_state(SelState &s, unsigned long long k)
@@ -106,7 +113,8 @@ __device__ __forceinline__ int ragged_image(const ColImage *__restrict__ images,
 // pass p = 0..7 looks at key byte 7-p of the values whose higher bytes equal the prefix.
 // One workgroup's share of one image: the pixels p0, p0 + step, ... below p1 of the image at b / rr,
 // counted into the image's two states st[0..1].
-__device__ __forceinline__ void hist_pixels(const uint8_t *__restrict__ b, const float *__restrict__ rr,
+template <typename R>
+__device__ __forceinline__ void hist_pixels(const uint8_t *__restrict__ b, const R *__restrict__ rr,
                                             SelState *__restrict__ st, size_t p0, size_t p1,
                                             size_t step, int pass)
 {
@@ -123,7 +131,7 @@ __device__ __forceinline__ void hist_pixels(const uint8_t *__restrict__ b, const
     unsigned long long m0 = 0, m1 = 0;
     for (size_t p = p0; p < p1; p += step) {
         double refl[3], sh;
-        pixel_values(b + p * 3, rr[p], refl, sh);
+        pixel_values(b + p * 3, reflectance_of(rr[p]), refl, sh);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const unsigned long long k = key_of(refl[c]);
@@ -179,6 +187,19 @@ __global__ __launch_bounds__(256) void colorize_ragged_hist_kernel(
     const size_t c0 = (size_t)(blockIdx.x - im.wg0) * chunk_px;
     const size_t c1 = c0 + chunk_px < im.npx ? c0 + chunk_px : (size_t)im.npx;
     hist_pixels(bgr + im.first * 3, r + im.first, st + img * kTargets, c0 + threadIdx.x, c1, 256,
+                pass);
+}
+
+// ... and with an 8-bit reflectance map: the same pass, one byte read per pixel
+__global__ __launch_bounds__(256) void colorize_ragged_hist_r8_kernel(
+    const uint8_t *__restrict__ bgr, const uint8_t *__restrict__ r8, SelState *__restrict__ st,
+    const ColImage *__restrict__ images, int n, unsigned int chunk_px, int pass)
+{
+    const int img = ragged_image(images, n);
+    const ColImage &im = images[img];
+    const size_t c0 = (size_t)(blockIdx.x - im.wg0) * chunk_px;
+    const size_t c1 = c0 + chunk_px < im.npx ? c0 + chunk_px : (size_t)im.npx;
+    hist_pixels(bgr + im.first * 3, r8 + im.first, st + img * kTargets, c0 + threadIdx.x, c1, 256,
                 pass);
 }
 
@@ -238,7 +259,8 @@ __device__ inline double normalise(double v, bool on, double pct)
 
 // One workgroup's share of one image, as hist_pixels: the bytes of the pixels p0, p0 + step, ...
 // below p1 of the image at b / rr into refl_o / shading_o (the image's own outputs, or NULL).
-__device__ __forceinline__ void write_pixels(const uint8_t *__restrict__ b, const float *__restrict__ rr,
+template <typename R>
+__device__ __forceinline__ void write_pixels(const uint8_t *__restrict__ b, const R *__restrict__ rr,
                                              const SelState *__restrict__ st,
                                              uint8_t *__restrict__ refl_o,
                                              uint8_t *__restrict__ shading_o, size_t p0, size_t p1,
@@ -259,7 +281,7 @@ __device__ __forceinline__ void write_pixels(const uint8_t *__restrict__ b, cons
     const double pc1 = __longlong_as_double((long long)s1.prefix);
     for (size_t p = p0; p < p1; p += step) {
         double refl[3], sh;
-        pixel_values(b + p * 3, rr[p], refl, sh);
+        pixel_values(b + p * 3, reflectance_of(rr[p]), refl, sh);
         if (refl_o) {
             uint8_t *o = refl_o + p * 3;
 #pragma unroll
@@ -294,6 +316,21 @@ __global__ __launch_bounds__(256) void colorize_ragged_write_kernel(
     const size_t c0 = (size_t)(blockIdx.x - im.wg0) * chunk_px;
     const size_t c1 = c0 + chunk_px < im.npx ? c0 + chunk_px : (size_t)im.npx;
     write_pixels(bgr + im.first * 3, r + im.first, st + img * kTargets,
+                 refl_out ? refl_out + im.first * 3 : nullptr,
+                 shading_out ? shading_out + im.first : nullptr, c0 + threadIdx.x, c1, 256, steps_g);
+}
+
+__global__ __launch_bounds__(256) void colorize_ragged_write_r8_kernel(
+    const uint8_t *__restrict__ bgr, const uint8_t *__restrict__ r8, const SelState *__restrict__ st,
+    uint8_t *__restrict__ refl_out, uint8_t *__restrict__ shading_out,
+    const ColImage *__restrict__ images, int n, unsigned int chunk_px,
+    const double *__restrict__ steps_g)
+{
+    const int img = ragged_image(images, n);
+    const ColImage &im = images[img];
+    const size_t c0 = (size_t)(blockIdx.x - im.wg0) * chunk_px;
+    const size_t c1 = c0 + chunk_px < im.npx ? c0 + chunk_px : (size_t)im.npx;
+    write_pixels(bgr + im.first * 3, r8 + im.first, st + img * kTargets,
                  refl_out ? refl_out + im.first * 3 : nullptr,
                  shading_out ? shading_out + im.first : nullptr, c0 + threadIdx.x, c1, 256, steps_g);
 }
@@ -457,15 +494,17 @@ extern "C" int rf_debug_colorize_ragged_plan(int n, const int *heights, const in
     return n;
 }
 
-extern "C" int rf_colorize_ragged_srgb_u8(const uint8_t *bgr, const float *r, uint8_t *refl_out,
-                                          uint8_t *shading_out, int n, const int *heights,
-                                          const int *widths, const unsigned long long *k_refl,
-                                          const unsigned long long *k_shading,
-                                          const double *srgb_steps, void *workspace,
-                                          size_t workspace_bytes, void *stream_)
+namespace rf {
+namespace {
+
+// The ragged entries: `r` is the float32 map of rf_colorize_ragged_srgb_u8 or the 8-bit map of
+// rf_colorize_ragged_r8_srgb_u8; everything but the two kernels that read it is shared.
+template <typename R>
+int colorize_ragged(const char *who, const uint8_t *bgr, const R *r, uint8_t *refl_out,
+                    uint8_t *shading_out, int n, const int *heights, const int *widths,
+                    const unsigned long long *k_refl, const unsigned long long *k_shading,
+                    const double *srgb_steps, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    using namespace rf;
-    const char *who = "rf_colorize_ragged_srgb_u8";
     if (n == 0)
         return RF_OK;
     if (!bgr || !r || !srgb_steps || !workspace || !heights || !widths || !k_refl || !k_shading ||
@@ -493,15 +532,51 @@ extern "C" int rf_colorize_ragged_srgb_u8(const uint8_t *bgr, const float *r, ui
     const ColImage *images = reinterpret_cast<const ColImage *>(workspace);
     SelState *st = reinterpret_cast<SelState *>(static_cast<char *>(workspace) + off_states);
     const dim3 grid((unsigned int)plan.workgroups);
+    constexpr bool kBytes = std::is_same<R, uint8_t>::value;
     hipLaunchKernelGGL(colorize_ragged_init_kernel, dim3(n * kTargets), dim3(256), 0, stream, st,
                        images);
     for (int pass = 0; pass < 8; pass++) {
-        hipLaunchKernelGGL(colorize_ragged_hist_kernel, grid, dim3(256), 0, stream, bgr, r, st, images,
-                           n, plan.chunk_px, pass);
+        if constexpr (kBytes)
+            hipLaunchKernelGGL(colorize_ragged_hist_r8_kernel, grid, dim3(256), 0, stream, bgr, r, st,
+                               images, n, plan.chunk_px, pass);
+        else
+            hipLaunchKernelGGL(colorize_ragged_hist_kernel, grid, dim3(256), 0, stream, bgr, r, st,
+                               images, n, plan.chunk_px, pass);
         hipLaunchKernelGGL(colorize_pick_kernel, dim3(n * kTargets), dim3(256), 0, stream, st, pass);
     }
-    hipLaunchKernelGGL(colorize_ragged_write_kernel, grid, dim3(256), 0, stream, bgr, r, st, refl_out,
-                       shading_out, images, n, plan.chunk_px, srgb_steps);
+    if constexpr (kBytes)
+        hipLaunchKernelGGL(colorize_ragged_write_r8_kernel, grid, dim3(256), 0, stream, bgr, r, st,
+                           refl_out, shading_out, images, n, plan.chunk_px, srgb_steps);
+    else
+        hipLaunchKernelGGL(colorize_ragged_write_kernel, grid, dim3(256), 0, stream, bgr, r, st,
+                           refl_out, shading_out, images, n, plan.chunk_px, srgb_steps);
     RF_HIP_CHECK(hipGetLastError());
     return RF_OK;
+}
+
+}  // namespace
+}  // namespace rf
+
+extern "C" int rf_colorize_ragged_srgb_u8(const uint8_t *bgr, const float *r, uint8_t *refl_out,
+                                          uint8_t *shading_out, int n, const int *heights,
+                                          const int *widths, const unsigned long long *k_refl,
+                                          const unsigned long long *k_shading,
+                                          const double *srgb_steps, void *workspace,
+                                          size_t workspace_bytes, void *stream)
+{
+    return rf::colorize_ragged("rf_colorize_ragged_srgb_u8", bgr, r, refl_out, shading_out, n, heights,
+                               widths, k_refl, k_shading, srgb_steps, workspace, workspace_bytes,
+                               stream);
+}
+
+extern "C" int rf_colorize_ragged_r8_srgb_u8(const uint8_t *bgr, const uint8_t *r8, uint8_t *refl_out,
+                                             uint8_t *shading_out, int n, const int *heights,
+                                             const int *widths, const unsigned long long *k_refl,
+                                             const unsigned long long *k_shading,
+                                             const double *srgb_steps, void *workspace,
+                                             size_t workspace_bytes, void *stream)
+{
+    return rf::colorize_ragged("rf_colorize_ragged_r8_srgb_u8", bgr, r8, refl_out, shading_out, n,
+                               heights, widths, k_refl, k_shading, srgb_steps, workspace,
+                               workspace_bytes, stream);
 }

@@ -11,6 +11,7 @@ Image convention on the blob side: linear RGB, channels x height x width, range 
 from __future__ import division, print_function
 
 import argparse
+import collections
 import sys
 import os
 
@@ -180,6 +181,103 @@ def decompose_list(images, weights=None):
     sizes, r, r8, refl, shad = decompose_packed(images, weights=weights)
     grey = lambda t: [v.squeeze(-1) for v in ops.split_packed(t.view(-1, 1), sizes)]
     return grey(r), grey(r8), ops.split_packed(refl, sizes), grey(shad)
+
+
+DecomposeFilter = collections.namedtuple(
+    "DecomposeFilter", "sizes r r_u8 reflectance shading filtered filtered_reflectance filtered_shading")
+
+
+def _packed_views(views, torch):
+    """The packed tensor [total pixels, C] behind a list of [H_i,W_i,C] results: the views of the
+    ragged operators lie one after another in one buffer, which is handed back as it is; results of
+    separate batches are joined with one torch.cat (a copy, no arithmetic)."""
+    c = views[0].shape[2]
+    base = views[0]._base
+    total = 0
+    for v in views:
+        if base is None or v._base is not base or v.data_ptr() != base.data_ptr() + total * c:
+            return torch.cat([t.reshape(-1, c) for t in views])
+        total += v.shape[0] * v.shape[1]
+    if tuple(base.shape) != (total, c) or not base.is_contiguous():
+        return torch.cat([t.reshape(-1, c) for t in views])
+    return base
+
+
+def decompose_filter_packed(images, sigma_color=20.0, sigma_spatial=22.0, filter_type="bilateral",
+                            guidance=None, iterations=1, weights=None, colorize_filtered=True):
+    """The paper's whole result for a list of photos, left packed photo after photo: the CNN map, its
+    filtered form and the decomposition derived from each.  images: a list of CUDA uint8 BGR tensors
+    [H_i,W_i,3] of any sizes.  Returns a DecomposeFilter: sizes int64 [n,2] (h, w); r float32, r_u8,
+    reflectance [.., 3] and shading as decompose_packed; filtered uint8 [total pixels], the bytes
+    filter_reflectance makes of `<base>-r.png`; filtered_reflectance [total pixels, 3] and
+    filtered_shading [total pixels], the bytes of imwrite(colorize(float32(filtered) / 255, photo),
+    sRGB=True) (None with colorize_filtered=False).
+    guidance: None - the CNN map guides itself (the bytes of decompose_and_filter_list); "image" - the
+    photos guide; or a list of CUDA uint8 tensors [H_i,W_i,1 or 3] of the photos' sizes, e.g. `flat`
+    images (one channel stands for three equal ones).  iterations >= 1 chains the filter under the
+    same guidance as apply_filter_list does.  One pack, one pass through the network, the ragged
+    filter routes of apply_filter_list, one ops.colorize_ragged_srgb_u8 and one
+    ops.colorize_ragged_r8_srgb_u8, which reads the filtered bytes as they are: no host arithmetic and
+    no torch arithmetic on pixel values."""
+    from . import filter_reflectance as fr
+    fr._check_params(filter_type, sigma_color, sigma_spatial)
+    if iterations < 1:
+        raise ValueError("iterations must be >= 1")
+    torch = _ffi.require_gpu()
+    images = list(images)
+    bgr, sizes = ops.pack_images(images, "images", torch)
+    if bgr.shape[1] != 3:
+        raise ValueError("images must have 3 channels")
+    if guidance is not None and not isinstance(guidance, str):
+        guidance = list(guidance)
+        if len(guidance) != len(images):
+            raise ValueError("guidance must hold one image per photo")
+        for i, (g, (h, w)) in enumerate(zip(guidance, sizes.tolist())):
+            if not torch.is_tensor(g) or g.dim() != 3 or tuple(g.shape[:2]) != (h, w):
+                raise ValueError("guidance of image {} is not a tensor of its size {}x{}".format(i, h, w))
+            if g.shape[2] not in (1, 3) or g.shape[2] != guidance[0].shape[2]:
+                raise ValueError("guidance of image {} must have 1 or 3 channels, the same for the "
+                                 "whole list".format(i))
+    elif guidance not in (None, "image"):
+        raise ValueError("guidance must be None, 'image' or a list of device tensors")
+    r, r8 = ops.cnn_reflectance_u8(bgr.view(1, 1, -1, 3), weights=weights)
+    r, r8 = r.view(-1), r8.view(-1)
+    refl, shad, _, _ = ops.colorize_ragged_srgb_u8(bgr, r, sizes=sizes)
+    r1 = r8.view(-1, 1)
+    if guidance is None and filter_type == "bilateral":
+        filtered = r1
+        bufs = [torch.empty_like(r1) for _ in range(min(iterations, 2))]
+        for it in range(iterations):
+            filtered, _ = ops.joint_bilateral_ragged_u8(r1, filtered, -1, sigma_color, sigma_spatial,
+                                                        grey_as_bgr=True, sizes=sizes, out=bufs[it % 2])
+    else:
+        maps = ops.split_packed(r1, sizes)
+        if guidance is None:
+            joints, grey = maps, True
+        elif isinstance(guidance, str):
+            joints, grey = images, False
+        else:
+            joints, grey = guidance, guidance[0].shape[2] == 1
+        filtered = _packed_views(fr.apply_filter_list(filter_type, maps, joints, sigma_color, sigma_spatial,
+                                                      iterations=iterations, grey_as_bgr=grey), torch)
+    filtered = filtered.view(-1)
+    f_refl = f_shad = None
+    if colorize_filtered:
+        f_refl, f_shad, _, _ = ops.colorize_ragged_r8_srgb_u8(bgr, filtered, sizes=sizes)
+    return DecomposeFilter(sizes, r, r8, refl, shad, filtered, f_refl, f_shad)
+
+
+def decompose_filter_list(images, sigma_color=20.0, sigma_spatial=22.0, filter_type="bilateral",
+                          guidance=None, iterations=1, weights=None, colorize_filtered=True):
+    """decompose_filter_packed split photo by photo: the same DecomposeFilter with a list of views
+    [H_i,W_i] (reflectance and filtered_reflectance [H_i,W_i,3]) in every field but sizes; the views of
+    one field share one packed tensor."""
+    p = decompose_filter_packed(images, sigma_color, sigma_spatial, filter_type, guidance, iterations,
+                                weights, colorize_filtered)
+    grey = lambda t: None if t is None else [v.squeeze(-1) for v in ops.split_packed(t.view(-1, 1), p.sizes)]
+    colour = lambda t: None if t is None else ops.split_packed(t, p.sizes)
+    return DecomposeFilter(p.sizes, grey(p.r), grey(p.r_u8), colour(p.reflectance), grey(p.shading),
+                           grey(p.filtered), colour(p.filtered_reflectance), grey(p.filtered_shading))
 
 
 def decompose_image(filename_in, path_out, caffemodel=None):

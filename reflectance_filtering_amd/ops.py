@@ -538,15 +538,9 @@ def colorize_srgb_u8(images, r, want_reflectance=True, want_shading=True):
     return refl, shad
 
 
-def colorize_ragged_srgb_u8(images, r, sizes=None, want_reflectance=True, want_shading=True):
-    """colorize_srgb_u8 over photos of different sizes in one call (rf_colorize_ragged_srgb_u8): the
-    percentile, the `max > 1` test and the NaN rule stay per image.  images: a list of n CUDA uint8
-    tensors [H_i, W_i, 3] and r a list of CUDA float32 tensors [H_i, W_i], or, with sizes = [n,2]
-    (h, w), the images already packed one after another as contiguous CUDA tensors: images uint8
-    [total pixels, 3], r float32 [total pixels].  Returns (packed reflectance bytes [total pixels, 3]
-    or None, packed shading bytes [total pixels] or None, list of reflectance views [H_i, W_i, 3],
-    list of shading views [H_i, W_i]); image i is, byte for byte, colorize_srgb_u8(images[i][None],
-    r[i][None]).  Synchronises the current stream."""
+def _colorize_ragged(entry, images, r, r_dtype, r_kind, sizes, want_reflectance, want_shading):
+    """The two ragged colourise ops: `entry` reads a map of torch dtype `r_dtype` (`r_kind` names it
+    in the messages); everything else - argument checks, ranks, steps, workspace - is shared."""
     from . import image_utils as iu
     torch = _ffi.require_gpu()
     lib = _ffi.load_library()
@@ -556,9 +550,9 @@ def colorize_ragged_srgb_u8(images, r, sizes=None, want_reflectance=True, want_s
         if len(r) != sizes.shape[0]:
             raise ValueError("images and r must hold the same number of images")
         for t, (h, w) in zip(r, sizes.tolist()):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == r_dtype
                     and t.is_contiguous() and tuple(t.shape) == (h, w)):
-                raise ValueError("r must be contiguous CUDA float32 tensors [H,W] matching images")
+                raise ValueError("r must be contiguous CUDA %s tensors [H,W] matching images" % r_kind)
         r = torch.cat([t.view(-1) for t in r])
     else:
         sizes = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
@@ -571,10 +565,10 @@ def colorize_ragged_srgb_u8(images, r, sizes=None, want_reflectance=True, want_s
                 and images.dim() == 2 and images.is_contiguous() and images.shape[0] == npx):
             raise ValueError("images must be a contiguous CUDA uint8 tensor [%d, 3]: the pixels of "
                              "all images" % npx)
-        if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32
+        if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == r_dtype
                 and r.is_contiguous() and tuple(r.shape) == (npx,)):
-            raise ValueError("r must be a contiguous CUDA float32 tensor [%d]: the pixels of all "
-                             "images" % npx)
+            raise ValueError("r must be a contiguous CUDA %s tensor [%d]: the pixels of all "
+                             "images" % (r_kind, npx))
     if images.shape[1] != 3:
         raise ValueError("images must have 3 channels")
     if r.device != images.device:
@@ -596,15 +590,41 @@ def colorize_ragged_srgb_u8(images, r, sizes=None, want_reflectance=True, want_s
     need = lib.rf_colorize_ragged_workspace_bytes(n, hs.ctypes.data, wds.ctypes.data)
     # need == 0: the entry says why
     ws = _stream_workspace(_colorize_ragged_workspaces, need, dev, torch)
-    rc = lib.rf_colorize_ragged_srgb_u8(images.data_ptr(), r.data_ptr(),
-                                        refl.data_ptr() if refl is not None else None,
-                                        shad.data_ptr() if shad is not None else None, n,
-                                        hs.ctypes.data, wds.ctypes.data, k_refl.ctypes.data,
-                                        k_shad.ctypes.data, steps.data_ptr(), ws.data_ptr(),
-                                        ws.numel(), _ffi.current_stream_ptr(torch))
-    _ffi.check(rc, "rf_colorize_ragged_srgb_u8")
+    rc = getattr(lib, entry)(images.data_ptr(), r.data_ptr(),
+                             refl.data_ptr() if refl is not None else None,
+                             shad.data_ptr() if shad is not None else None, n,
+                             hs.ctypes.data, wds.ctypes.data, k_refl.ctypes.data,
+                             k_shad.ctypes.data, steps.data_ptr(), ws.data_ptr(),
+                             ws.numel(), _ffi.current_stream_ptr(torch))
+    _ffi.check(rc, entry)
     return (refl, shad, split_packed(refl, sizes) if refl is not None else [],
             [v.squeeze(-1) for v in split_packed(shad.view(-1, 1), sizes)] if shad is not None else [])
+
+
+def colorize_ragged_srgb_u8(images, r, sizes=None, want_reflectance=True, want_shading=True):
+    """colorize_srgb_u8 over photos of different sizes in one call (rf_colorize_ragged_srgb_u8): the
+    percentile, the `max > 1` test and the NaN rule stay per image.  images: a list of n CUDA uint8
+    tensors [H_i, W_i, 3] and r a list of CUDA float32 tensors [H_i, W_i], or, with sizes = [n,2]
+    (h, w), the images already packed one after another as contiguous CUDA tensors: images uint8
+    [total pixels, 3], r float32 [total pixels].  Returns (packed reflectance bytes [total pixels, 3]
+    or None, packed shading bytes [total pixels] or None, list of reflectance views [H_i, W_i, 3],
+    list of shading views [H_i, W_i]); image i is, byte for byte, colorize_srgb_u8(images[i][None],
+    r[i][None]).  Synchronises the current stream."""
+    torch = _ffi.require_gpu()
+    return _colorize_ragged("rf_colorize_ragged_srgb_u8", images, r, torch.float32, "float32", sizes,
+                            want_reflectance, want_shading)
+
+
+def colorize_ragged_r8_srgb_u8(images, r8, sizes=None, want_reflectance=True, want_shading=True):
+    """colorize_ragged_srgb_u8 of 8-bit reflectance maps - filtered `-r.png` bytes that are on the
+    device (rf_colorize_ragged_r8_srgb_u8): r8 is a list of CUDA uint8 tensors [H_i, W_i] or, with
+    sizes, one packed uint8 tensor [total pixels]; the reflectance of a pixel is the float32 nearest
+    to byte / 255, formed inside the kernels.  Same returns; byte for byte what
+    colorize_ragged_srgb_u8 makes of the float32 maps r8.astype(float32) / float32(255).
+    Synchronises the current stream."""
+    torch = _ffi.require_gpu()
+    return _colorize_ragged("rf_colorize_ragged_r8_srgb_u8", images, r8, torch.uint8, "uint8", sizes,
+                            want_reflectance, want_shading)
 
 
 _png_host = []
