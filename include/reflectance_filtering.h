@@ -223,6 +223,37 @@ int rf_cnn_reflectance_packed_u8(const uint8_t *bgr, float *r_out, uint8_t *r_u8
                                  int w, const float *packed, const float *srgb_lut, void *stream);
 
 /*
+ * The same network on float32 LINEAR images: whatever floats a Caffe blob holds (MIT Intrinsic, MPI
+ * Sintel, HDR / EXR / RAW data, the npz and movie inputs of the reference's trainer), not only the
+ * 256 values that 8-bit sRGB pixels decode to.  Only the input stage differs from the u8 entries:
+ * the network's input is the float as it is, where they look a byte up in srgb_lut.
+ *   x        n*h*w*3 float32 device, linear, nominally 0..1 (nothing is clamped), in one of two layouts:
+ *            RF_CNN_NCHW_RGB  planar [n][3][h][w], channels R, G, B: net.blobs['images'].data
+ *            RF_CNN_NHWC_BGR  interleaved [n][h][w][3], channels B, G, R: the float twin of `bgr`
+ *   r_out, r_u8_out, weights, packed   as for the u8 entries
+ * Contract: for an x whose values are all table levels, x = srgb_lut[byte], both entries write the
+ * SAME BITS (r_out and r_u8_out) as rf_cnn_reflectance_u8 / _packed_u8 on the corresponding bytes;
+ * a pixel's result depends on its three values only, not on its place, the layout or the entry.
+ * Non-finite inputs (NaN, +-inf): no input value is used as an index, so they cannot make the call
+ * read or write outside its buffers; the outputs of the pixels that hold them are unspecified, every
+ * other pixel of the call is unaffected, and the call returns RF_OK.
+ * Rules: those of the u8 twins - n == 0 is RF_OK whatever the pointers are; either output may be NULL,
+ * not both; n < 0, h <= 0, w <= 0 and NULL inputs are RF_E_BADARG; nothing is synchronised;
+ * rf_cnn_reflectance_f32 re-packs the weights on the caller's stream into the library's per-stream
+ * slot and is refused on a capturing stream, rf_cnn_reflectance_packed_f32 keeps no state and can be
+ * captured.  Refused in addition, before any device work (RF_E_BADARG): an unknown layout; r_out or
+ * r_u8_out overlapping x (a pixel is read long after others were written); n*h*w of 2^48 or more.
+ * Images of different sizes go through packed one after another as ONE image, n = 1, h = 1,
+ * w = total pixels: interleaved [1][1][P][3], planar three planes of P values [1][3][1][P].
+ */
+#define RF_CNN_NCHW_RGB 0
+#define RF_CNN_NHWC_BGR 1
+int rf_cnn_reflectance_f32(const float *x, float *r_out, uint8_t *r_u8_out, int n, int h, int w,
+                           int layout, const float *weights, void *stream);
+int rf_cnn_reflectance_packed_f32(const float *x, float *r_out, uint8_t *r_u8_out, int n, int h,
+                                  int w, int layout, const float *packed, void *stream);
+
+/*
  * Colourised reflectance and shading PNG bytes of decompose_image.
  * Replaces the host numpy chain  iu.colorize(reflectance_gray, image)  +  iu.imwrite(..., sRGB=True)
  * of both results (/root/reference/decompose_with_trained_CNN.py:121-128,

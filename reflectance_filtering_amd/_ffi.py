@@ -26,6 +26,8 @@ PNG_GREY_AS_RGB = 1         # rf_png_deflate_ragged_u8: a 1-channel image is wri
 PNG_FLAG_GREY, PNG_FLAG_BAD_FILTER = 1, 2   # image_flags of rf_png_unfilter_ragged_u8
 CNN_NPARAMS = 4513
 CNN_NPACKED = 4673          # RF_CNN_NPACKED: floats of rf_cnn_pack_weights' output
+CNN_NCHW_RGB, CNN_NHWC_BGR = 0, 1           # layouts of rf_cnn_reflectance_f32 / _packed_f32
+CNN_LAYOUTS = {"nchw_rgb": CNN_NCHW_RGB, "nhwc_bgr": CNN_NHWC_BGR}
 
 EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_workspace_bytes",
            "rf_gf_u8", "rf_gf_ex_u8", "rf_cnn_reflectance_u8", "rf_cnn_pack_weights",
@@ -38,7 +40,8 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
            "rf_gf_ragged_workspace_bytes", "rf_gf_ragged_u8", "rf_png_stream_bound",
            "rf_png_workspace_bytes", "rf_png_deflate_ragged_u8",
            "rf_png_unfilter_workspace_bytes", "rf_png_unfilter_ragged_u8",
-           "rf_colorize_ragged_r8_srgb_u8")
+           "rf_colorize_ragged_r8_srgb_u8", "rf_cnn_reflectance_f32",
+           "rf_cnn_reflectance_packed_f32")
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
@@ -96,6 +99,10 @@ def load_library():
         lib.rf_cnn_pack_weights.restype = ci
         lib.rf_cnn_reflectance_packed_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
         lib.rf_cnn_reflectance_packed_u8.restype = ci
+        lib.rf_cnn_reflectance_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, vp]
+        lib.rf_cnn_reflectance_f32.restype = ci
+        lib.rf_cnn_reflectance_packed_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, vp]
+        lib.rf_cnn_reflectance_packed_f32.restype = ci
         u64 = ctypes.c_ulonglong
         lib.rf_colorize_workspace_bytes.argtypes = [ci]
         lib.rf_colorize_workspace_bytes.restype = sz

@@ -11,7 +11,9 @@
 // bias is a second rank-1 gemm in Caffe).
 //
 // Two kernels with identical values: cnn_reflectance_regs_kernel (default; see the comment block
-// above it) and cnn_reflectance_kernel, the LDS-column form described next (cross-check).
+// above it) and cnn_reflectance_kernel, the LDS-column form described next (cross-check).  Each is
+// a template over the input stage ("Input stage" below): uint8 through the table as above, or the
+// linear float blob itself (rf_cnn_reflectance_f32), x = the floats as they are.
 //
 // Mapping: one lane = two pixels; the 32 activations of a pixel live in VGPRs; every FMA is a
 // v_pk_fma_f32 that advances TWO output channels of one pixel by one k, its weight pair
@@ -27,6 +29,7 @@
 // (SMEM returns out of order, so only lgkmcnt(0) is usable and nothing may be issued right
 // before a wait).  Left to hipcc the loads were issued and waited for back to back.
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "rf_common.hpp"
@@ -180,15 +183,80 @@ __device__ __forceinline__ void collect(float2v (*act)[kCnnThreads], const float
     }
 }
 
-__global__ __launch_bounds__(kCnnThreads) void cnn_reflectance_kernel(
-    const uint8_t *__restrict__ bgr, float *__restrict__ r_out, uint8_t *__restrict__ r_u8_out,
-    size_t npix, const float *__restrict__ packed, const float *__restrict__ srgb_lut)
+// ------------------------------------------------------------------------------------------
+// Input stage.  Both forward kernels are templates over where a pixel's linear RGB comes from;
+// everything from layer 0 onwards is one text.
+//   InU8              uint8 BGR through the 256-entry sRGB table staged in LDS (aux: the table)
+//   InF32Interleaved  float32 linear [n][h][w][3], channel order B, G, R (aux: unused)
+//   InF32Planar       float32 linear [n][3][h][w], channel order R, G, B: the Caffe blob (aux: the
+//                     plane size and its reciprocal)
+// The float forms need no table, so no LDS and no barrier.  No input value is used as an index.
+// ------------------------------------------------------------------------------------------
+struct PlaneGeom {
+    size_t hw;      // pixels per plane
+    double inv_hw;  // 1.0 / hw, rounded to nearest
+};
+struct InU8 {
+    typedef uint8_t px_t;
+    typedef const float *__restrict__ aux_t;
+};
+struct InF32Interleaved {
+    typedef float px_t;
+    typedef const float *aux_t;
+};
+struct InF32Planar {
+    typedef float px_t;
+    typedef PlaneGeom aux_t;
+};
+template <class IN>
+constexpr bool kIsU8 = std::is_same<IN, InU8>::value;
+
+// linear R, G, B of pixel q of the flat n*h*w index (q < npix)
+__device__ __forceinline__ void load_rgb(InF32Interleaved, const float *__restrict__ x, const float *,
+                                         size_t q, float (&v)[3])
 {
-    __shared__ float lut[256];
+    const float *px = x + q * 3;
+    v[0] = px[2];
+    v[1] = px[1];
+    v[2] = px[0];
+}
+
+// A lane's two pixels are half the call apart, so each finds its own (image, offset): image =
+// q / hw, taken as trunc(double(q) * (1 / hw)) and set right by at most one step - no integer
+// division of any width.  q < 2^48 (the entry points see to that) is exact in a double and the
+// quotient is below 2^31, so the product is off by far less than 1 and its truncation by at most 1.
+// The plane address is formed in 64 bits.
+__device__ __forceinline__ void load_rgb(InF32Planar, const float *__restrict__ x, PlaneGeom g,
+                                         size_t q, float (&v)[3])
+{
+    size_t img = (size_t)((double)q * g.inv_hw);
+    size_t off = q - img * g.hw;  // "negative" (wrapped) when the estimate is one too high
+    if ((long long)off < 0) {
+        img -= 1;
+        off += g.hw;
+    } else if (off >= g.hw) {
+        img += 1;
+        off -= g.hw;
+    }
+    const float *px = x + img * 3 * g.hw + off;
+    v[0] = px[0];
+    v[1] = px[g.hw];
+    v[2] = px[2 * g.hw];
+}
+
+template <class IN>
+__global__ __launch_bounds__(kCnnThreads) void cnn_reflectance_kernel(
+    const typename IN::px_t *__restrict__ in, float *__restrict__ r_out,
+    uint8_t *__restrict__ r_u8_out, size_t npix, const float *__restrict__ packed,
+    typename IN::aux_t aux)
+{
+    __shared__ float lut[256];  // the float forms never touch it: no LDS is allotted for them
     __shared__ float2v act[32][kCnnThreads];
-    for (int i = threadIdx.x; i < 256; i += kCnnThreads)
-        lut[i] = srgb_lut[i];
-    __syncthreads();
+    if constexpr (kIsU8<IN>) {
+        for (int i = threadIdx.x; i < 256; i += kCnnThreads)
+            lut[i] = aux[i];
+        __syncthreads();
+    }
     const float *wf = packed + kWfOff;
     const size_t stride = (size_t)gridDim.x * kCnnThreads;
     // lane handles pixels i and i + half (both halves stay coalesced)
@@ -199,10 +267,14 @@ __global__ __launch_bounds__(kCnnThreads) void cnn_reflectance_kernel(
 #pragma unroll
         for (int p = 0; p < kPxPerLane; p++) {
             const size_t q = idx[p] < npix ? idx[p] : npix - 1;
-            const uint8_t *px = bgr + q * 3;
-            x[p][0] = lut[px[2]];  // blob channel order is RGB
-            x[p][1] = lut[px[1]];
-            x[p][2] = lut[px[0]];
+            if constexpr (kIsU8<IN>) {
+                const uint8_t *px = in + q * 3;
+                x[p][0] = lut[px[2]];  // blob channel order is RGB
+                x[p][1] = lut[px[1]];
+                x[p][2] = lut[px[0]];
+            } else {
+                load_rgb(IN(), in, aux, q, x[p]);
+            }
         }
         float cur[kPxPerLane][32];
         float z[kPxPerLane] = {0.f, 0.f};
@@ -415,26 +487,37 @@ __device__ __forceinline__ void fuse32(const float2v (&act)[32], const float *__
 #undef RF_W2
 }
 
+template <class IN>
 __global__ __launch_bounds__(kCnnThreads) void cnn_reflectance_regs_kernel(
-    const uint8_t *__restrict__ bgr, float *__restrict__ r_out, uint8_t *__restrict__ r_u8_out,
-    size_t npix, const float *__restrict__ packed, const float *__restrict__ srgb_lut)
+    const typename IN::px_t *__restrict__ in, float *__restrict__ r_out,
+    uint8_t *__restrict__ r_u8_out, size_t npix, const float *__restrict__ packed,
+    typename IN::aux_t aux)
 {
-    __shared__ float lut[256];
-    for (int i = threadIdx.x; i < 256; i += kCnnThreads)
-        lut[i] = srgb_lut[i];
-    __syncthreads();
+    __shared__ float lut[256];  // the float forms never touch it: no LDS is allotted for them
+    if constexpr (kIsU8<IN>) {
+        for (int i = threadIdx.x; i < 256; i += kCnnThreads)
+            lut[i] = aux[i];
+        __syncthreads();
+    }
     const float *wf = packed + kWfOff;
     const size_t stride = (size_t)gridDim.x * kCnnThreads;
     const size_t half = (npix + 1) / 2;  // lane handles pixels i and i + half (both stay coalesced)
     for (size_t i = (size_t)blockIdx.x * kCnnThreads + threadIdx.x; i < half; i += stride) {
         const size_t idx[kPxPerLane] = {i, i + half};
         float2v x[3];
-        {
-            const uint8_t *p0 = bgr + idx[0] * 3;
-            const uint8_t *p1 = bgr + (idx[1] < npix ? idx[1] : npix - 1) * 3;
+        if constexpr (kIsU8<IN>) {
+            const uint8_t *p0 = in + idx[0] * 3;
+            const uint8_t *p1 = in + (idx[1] < npix ? idx[1] : npix - 1) * 3;
             x[0] = float2v{lut[p0[2]], lut[p1[2]]};  // blob channel order is RGB
             x[1] = float2v{lut[p0[1]], lut[p1[1]]};
             x[2] = float2v{lut[p0[0]], lut[p1[0]]};
+        } else {
+            float v0[3], v1[3];
+            load_rgb(IN(), in, aux, idx[0], v0);
+            load_rgb(IN(), in, aux, idx[1] < npix ? idx[1] : npix - 1, v1);
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+                x[k] = float2v{v0[k], v1[k]};
         }
         float2v A[32], B[32];
         float2v z = float2v{0.f, 0.f};  // the fuse dot product of {pixel 0, pixel 1}
@@ -495,7 +578,7 @@ __global__ __launch_bounds__(kCnnThreads) void cnn_reflectance_regs_kernel(
 #undef RF_PKMUL4
 #undef RF_PK4_TAIL
 
-// rf_cnn_reflectance_u8 (raw weights) keeps one packed copy per (device, stream): a call re-packs
+// rf_cnn_reflectance_u8 / _f32 (raw weights) keep one packed copy per (device, stream): a call re-packs
 // the caller's weights on its own stream (18 tiny workgroups; the weights may have changed since
 // the last call), so calls on different streams never share a buffer and calls on one stream are
 // ordered.  The table is bounded (kMaxSlots): when it is full the least recently used slot whose
@@ -516,7 +599,8 @@ std::mutex g_cnn_mu;
 std::vector<PackedSlot> g_packed;
 unsigned long long g_tick = 0;
 
-int packed_buffer(hipStream_t stream, float **out, std::unique_lock<std::mutex> &lock)
+int packed_buffer(const char *who, const char *packed_twin, hipStream_t stream, float **out,
+                  std::unique_lock<std::mutex> &lock)
 {
     int dev = 0;
     RF_HIP_CHECK(hipGetDevice(&dev));
@@ -525,10 +609,11 @@ int packed_buffer(hipStream_t stream, float **out, std::unique_lock<std::mutex> 
         (void)hipGetLastError();
     if (cap != hipStreamCaptureStatusNone)
         return fail(RF_E_UNSUPPORTED,
-                    "rf_cnn_reflectance_u8: the stream is being captured; this entry point keeps its "
+                    "%s: the stream is being captured; this entry point keeps its "
                     "packed weights in a per-stream slot of the library that a later call may hand "
-                    "to another stream - capture rf_cnn_reflectance_packed_u8 on weights packed "
-                    "beforehand with rf_cnn_pack_weights");
+                    "to another stream - capture %s on weights packed "
+                    "beforehand with rf_cnn_pack_weights",
+                    who, packed_twin);
     lock = std::unique_lock<std::mutex>(g_cnn_mu);  // held until the caller has enqueued its work
     for (PackedSlot &s : g_packed)
         if (s.device == dev && s.stream == stream) {
@@ -581,8 +666,9 @@ int packed_buffer(hipStream_t stream, float **out, std::unique_lock<std::mutex> 
     return RF_OK;
 }
 
-int launch_forward(const uint8_t *bgr, float *r_out, uint8_t *r_u8_out, int n, int h, int w,
-                   const float *packed, const float *srgb_lut, hipStream_t stream)
+template <class IN>
+int launch_forward(const typename IN::px_t *in, float *r_out, uint8_t *r_u8_out, int n, int h, int w,
+                   const float *packed, typename IN::aux_t aux, hipStream_t stream)
 {
     const size_t npix = (size_t)n * h * w;
     size_t blocks = ((npix + 1) / 2 + kCnnThreads - 1) / kCnnThreads;
@@ -593,13 +679,23 @@ int launch_forward(const uint8_t *bgr, float *r_out, uint8_t *r_u8_out, int n, i
     if (blocks > 256 * 128)
         blocks = 256 * 128;
     if (debug_get(kDbgCnnLdsColumns))  // cross-check: the LDS-column form of round 1
-        hipLaunchKernelGGL(cnn_reflectance_kernel, dim3((unsigned)blocks), dim3(kCnnThreads), 0,
-                           stream, bgr, r_out, r_u8_out, npix, packed, srgb_lut);
+        hipLaunchKernelGGL(cnn_reflectance_kernel<IN>, dim3((unsigned)blocks), dim3(kCnnThreads), 0,
+                           stream, in, r_out, r_u8_out, npix, packed, aux);
     else
-        hipLaunchKernelGGL(cnn_reflectance_regs_kernel, dim3((unsigned)blocks), dim3(kCnnThreads),
-                           0, stream, bgr, r_out, r_u8_out, npix, packed, srgb_lut);
+        hipLaunchKernelGGL(cnn_reflectance_regs_kernel<IN>, dim3((unsigned)blocks),
+                           dim3(kCnnThreads), 0, stream, in, r_out, r_u8_out, npix, packed, aux);
     RF_HIP_CHECK(hipGetLastError());
     return RF_OK;
+}
+
+int launch_forward_f32(const float *x, float *r_out, uint8_t *r_u8_out, int n, int h, int w,
+                       int layout, const float *packed, hipStream_t stream)
+{
+    if (layout == RF_CNN_NHWC_BGR)
+        return launch_forward<InF32Interleaved>(x, r_out, r_u8_out, n, h, w, packed, nullptr, stream);
+    const size_t hw = (size_t)h * w;
+    return launch_forward<InF32Planar>(x, r_out, r_u8_out, n, h, w, packed,
+                                       PlaneGeom{hw, 1.0 / (double)hw}, stream);
 }
 
 int check_forward_args(const char *who, const void *bgr, const void *weights, const void *srgb_lut,
@@ -609,6 +705,31 @@ int check_forward_args(const char *who, const void *bgr, const void *weights, co
         return fail(RF_E_BADARG, "%s: NULL pointer", who);
     if (n < 0 || h <= 0 || w <= 0)
         return fail(RF_E_BADARG, "%s: bad size n=%d h=%d w=%d", who, n, h, w);
+    return RF_OK;
+}
+
+// The float entries' refusals, all decided on the host before any device work.
+int check_forward_args_f32(const char *who, const float *x, const void *weights, const float *r_out,
+                           const uint8_t *r_u8_out, int n, int h, int w, int layout)
+{
+    if (!x || !weights || (!r_out && !r_u8_out))
+        return fail(RF_E_BADARG, "%s: NULL pointer", who);
+    if (n < 0 || h <= 0 || w <= 0)
+        return fail(RF_E_BADARG, "%s: bad size n=%d h=%d w=%d", who, n, h, w);
+    if (layout != RF_CNN_NCHW_RGB && layout != RF_CNN_NHWC_BGR)
+        return fail(RF_E_BADARG, "%s: unknown layout %d (RF_CNN_NCHW_RGB or RF_CNN_NHWC_BGR)", who,
+                    layout);
+    // (the planar form takes image = pixel / (h*w) through a double: exact below 2^53; no buffer of
+    //  2^48 pixels exists)
+    if ((double)n * (double)h * (double)w >= 281474976710656.0)
+        return fail(RF_E_BADARG, "%s: n*h*w = %d*%d*%d pixels is more than can be addressed", who, n,
+                    h, w);
+    // a lane reads pixel i + half long after other lanes wrote theirs: no output inside the input
+    const size_t npix = (size_t)n * h * w;
+    if (r_out && ranges_overlap(x, npix * 3 * sizeof(float), r_out, npix * sizeof(float)))
+        return fail(RF_E_BADARG, "%s: r_out must not overlap x", who);
+    if (r_u8_out && ranges_overlap(x, npix * 3 * sizeof(float), r_u8_out, npix))
+        return fail(RF_E_BADARG, "%s: r_u8_out must not overlap x", who);
     return RF_OK;
 }
 
@@ -650,7 +771,8 @@ extern "C" int rf_cnn_reflectance_packed_u8(const uint8_t *bgr, float *r_out, ui
                                       r_u8_out, n, h, w);
     if (rc != RF_OK)
         return rc;
-    return launch_forward(bgr, r_out, r_u8_out, n, h, w, packed, srgb_lut, (hipStream_t)stream_);
+    return launch_forward<InU8>(bgr, r_out, r_u8_out, n, h, w, packed, srgb_lut,
+                                (hipStream_t)stream_);
 }
 
 extern "C" int rf_cnn_reflectance_u8(const uint8_t *bgr, float *r_out, uint8_t *r_u8_out, int n,
@@ -667,11 +789,48 @@ extern "C" int rf_cnn_reflectance_u8(const uint8_t *bgr, float *r_out, uint8_t *
     hipStream_t stream = (hipStream_t)stream_;
     float *packed = nullptr;
     std::unique_lock<std::mutex> slot_lock;  // released when both kernels are enqueued
-    rc = packed_buffer(stream, &packed, slot_lock);
+    rc = packed_buffer("rf_cnn_reflectance_u8", "rf_cnn_reflectance_packed_u8", stream, &packed,
+                       slot_lock);
     if (rc != RF_OK)
         return rc;
     // (the packed copy is rebuilt on the caller's stream every call: the weights may have changed)
     hipLaunchKernelGGL(cnn_pack_weights_kernel, dim3((RF_CNN_NPACKED + 255) / 256), dim3(256), 0,
                        stream, weights, packed);
-    return launch_forward(bgr, r_out, r_u8_out, n, h, w, packed, srgb_lut, stream);
+    return launch_forward<InU8>(bgr, r_out, r_u8_out, n, h, w, packed, srgb_lut, stream);
+}
+
+extern "C" int rf_cnn_reflectance_packed_f32(const float *x, float *r_out, uint8_t *r_u8_out, int n,
+                                             int h, int w, int layout, const float *packed,
+                                             void *stream_)
+{
+    using namespace rf;
+    if (n == 0)
+        return RF_OK;
+    const int rc = check_forward_args_f32("rf_cnn_reflectance_packed_f32", x, packed, r_out,
+                                          r_u8_out, n, h, w, layout);
+    if (rc != RF_OK)
+        return rc;
+    return launch_forward_f32(x, r_out, r_u8_out, n, h, w, layout, packed, (hipStream_t)stream_);
+}
+
+extern "C" int rf_cnn_reflectance_f32(const float *x, float *r_out, uint8_t *r_u8_out, int n, int h,
+                                      int w, int layout, const float *weights, void *stream_)
+{
+    using namespace rf;
+    if (n == 0)
+        return RF_OK;
+    int rc = check_forward_args_f32("rf_cnn_reflectance_f32", x, weights, r_out, r_u8_out, n, h, w,
+                                    layout);
+    if (rc != RF_OK)
+        return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    float *packed = nullptr;
+    std::unique_lock<std::mutex> slot_lock;  // released when both kernels are enqueued
+    rc = packed_buffer("rf_cnn_reflectance_f32", "rf_cnn_reflectance_packed_f32", stream, &packed,
+                       slot_lock);
+    if (rc != RF_OK)
+        return rc;
+    hipLaunchKernelGGL(cnn_pack_weights_kernel, dim3((RF_CNN_NPACKED + 255) / 256), dim3(256), 0,
+                       stream, weights, packed);
+    return launch_forward_f32(x, r_out, r_u8_out, n, h, w, layout, packed, stream);
 }

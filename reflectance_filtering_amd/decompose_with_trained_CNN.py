@@ -48,13 +48,21 @@ class _Blob(object):
         self.data = np.zeros(shape, dtype=np.float32)
 
 
+class _NotByteLevels(ValueError):
+    """_blob_to_bytes: the blob is well formed but holds values between the sRGB byte levels."""
+
+
 class ReflectanceNet(object):
     """pycaffe-shaped wrapper of the HIP forward pass.
 
-    ``blobs['images'].data`` holds the float32 linear-RGB blob exactly as the reference fills it;
-    since every blob value is ``float32(srgb_to_rgb(v/255))`` for a byte v, forward() recovers
-    the bytes through the same 256-entry table and hands uint8 BGR to the kernel (3 B/pixel
-    over PCIe instead of 12).  Blobs that were not produced from 8-bit pixels are rejected.
+    ``blobs['images'].data`` holds the float32 linear-RGB blob [N,3,H,W] exactly as the reference
+    fills it, and forward() runs whatever floats are there, as Caffe does, for any N.  When every
+    blob value is ``float32(srgb_to_rgb(v/255))`` for a byte v - what imgCV2_to_caffeBlob makes of
+    8-bit pixels - forward() recovers the bytes through the same 256-entry table and hands uint8
+    BGR to the kernel (3 B/pixel over PCIe instead of 12).  Any other blob (linear data deeper
+    than 8 bits: MIT Intrinsic, MPI Sintel, HDR, the trainer's npz and movie inputs) is uploaded
+    as it is and takes the float entry (ops.cnn_reflectance_f32, layout "nchw_rgb"), which on byte
+    levels computes the same bits as the byte route.
     """
 
     def __init__(self, caffemodel=None):
@@ -70,15 +78,21 @@ class ReflectanceNet(object):
         idx = np.searchsorted(self._lut, x)
         idx = np.clip(idx, 0, 255)
         if not np.array_equal(self._lut[idx], x):
-            raise ValueError("blob 'images' does not hold sRGB byte levels; "
-                             "use get_reflectance_batch() on uint8 images instead")
+            raise _NotByteLevels("blob 'images' does not hold sRGB byte levels; "
+                                 "use get_reflectance_batch() on uint8 images instead")
         # blob is RGB, channel-first -> BGR, channel-last
         return np.ascontiguousarray(idx.astype(np.uint8).transpose(0, 2, 3, 1)[:, :, :, ::-1])
 
     def forward(self):
         torch = _ffi.require_gpu()
-        bgr = torch.from_numpy(self._blob_to_bytes()).cuda()
-        r, _ = ops.cnn_reflectance_u8(bgr, weights=self.weights, want_u8=False)
+        try:                                    # (a blob that is not [N,3,H,W] stays an error)
+            bgr = torch.from_numpy(self._blob_to_bytes()).cuda()
+        except _NotByteLevels:
+            blob = np.ascontiguousarray(self.blobs["images"].data, dtype=np.float32)
+            r, _ = ops.cnn_reflectance_f32(torch.from_numpy(blob).cuda(), layout="nchw_rgb",
+                                           weights=self.weights, want_u8=False)
+        else:
+            r, _ = ops.cnn_reflectance_u8(bgr, weights=self.weights, want_u8=False)
         self.blobs["reflectance_intensity"].data = r.cpu().numpy()[:, np.newaxis, :, :]
         return {"reflectance_intensity": self.blobs["reflectance_intensity"].data}
 
@@ -93,10 +107,23 @@ def get_reflectance_caffe(net, image):
     return caffeBlob_to_imgGrayLinear(net.blobs["reflectance_intensity"].data)
 
 
+def _cnn_batch(images, weights, **want):
+    """The network on a device batch [N,H,W,3], routed by dtype: uint8 sRGB BGR (cv2.imread) or
+    float32 linear BGR."""
+    dtype = str(getattr(images, "dtype", None))
+    if dtype == "torch.uint8":
+        return ops.cnn_reflectance_u8(images, weights=weights, **want)
+    if dtype == "torch.float32":
+        return ops.cnn_reflectance_f32(images, layout="nhwc_bgr", weights=weights, **want)
+    raise ValueError("images must be uint8 sRGB BGR [N,H,W,3] or float32 linear BGR [N,H,W,3], "
+                     "got dtype {}".format(dtype))
+
+
 def get_reflectance_batch(images, weights=None):
-    """Device-resident batch form: CUDA uint8 BGR [N,H,W,3] -> (r float32 [N,H,W],
-    r_u8 uint8 [N,H,W] = the `-r.png` bytes)."""
-    return ops.cnn_reflectance_u8(images, weights=weights)
+    """Device-resident batch form: CUDA uint8 BGR [N,H,W,3] (sRGB, as cv2.imread returns it) or
+    CUDA float32 BGR [N,H,W,3] (linear, 0..1: data deeper than 8 bits) -> (r float32 [N,H,W],
+    r_u8 uint8 [N,H,W] = the `-r.png` bytes).  Any other dtype is a ValueError."""
+    return _cnn_batch(images, weights)
 
 
 def decompose_and_filter_batch(images, sigma_color=20.0, sigma_spatial=22.0, weights=None,
@@ -107,10 +134,12 @@ def decompose_and_filter_batch(images, sigma_color=20.0, sigma_spatial=22.0, wei
     radius = int(sigma_spatial), eps = sigma_color; the tool suggests sigma_color=7,
     sigma_spatial=52).  CUDA uint8 BGR [N,H,W,3] -> (r_u8 [N,H,W], filtered [N,H,W]) with
     `filtered` bit-identical to what the two CLIs produce through `<base>-r.png` (grey PNG re-read
-    as 3 equal channels, filtered with itself as guidance, any channel of the result)."""
+    as 3 equal channels, filtered with itself as guidance, any channel of the result).  A float32
+    linear BGR batch [N,H,W,3] is accepted as by get_reflectance_batch: the filter consumes r_u8
+    and nothing else here reads the photo."""
     if filter_type not in ("bilateral", "guided"):
         raise ValueError("filter_type must be 'bilateral' or 'guided'.")
-    _, r8 = ops.cnn_reflectance_u8(images, weights=weights, want_float=False)
+    _, r8 = _cnn_batch(images, weights, want_float=False)
     r1 = r8.unsqueeze(-1)
     if filter_type == "guided":
         out = ops.guided_filter_u8(r1, r1, int(sigma_spatial), sigma_color, grey_as_bgr=True)

@@ -492,6 +492,37 @@ def cnn_reflectance_u8(bgr, weights=None, want_float=True, want_u8=True):
     return r, r8
 
 
+def cnn_reflectance_f32(x, layout="nchw_rgb", weights=None, want_float=True, want_u8=True):
+    """cnn_reflectance_u8 for float32 LINEAR images, i.e. whatever a Caffe blob holds: a contiguous
+    CUDA float32 tensor, layout "nchw_rgb" [N,3,H,W] (channels R, G, B: blobs['images'].data) or
+    "nhwc_bgr" [N,H,W,3] (channels B, G, R: the float twin of the uint8 form) -> (r float32 [N,H,W],
+    r_u8 [N,H,W]).  On values that are sRGB byte levels the results are bit for bit those of
+    cnn_reflectance_u8 on the bytes."""
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    if layout not in _ffi.CNN_LAYOUTS:
+        raise ValueError("layout must be 'nchw_rgb' or 'nhwc_bgr'")
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32
+            and x.dim() == 4 and x.is_contiguous()):
+        raise ValueError("x must be a contiguous CUDA float32 tensor [N,3,H,W] or [N,H,W,3]")
+    if layout == "nchw_rgb":
+        n, c, h, w = x.shape
+    else:
+        n, h, w, c = x.shape
+    if c != 3:
+        raise ValueError("x must have 3 channels (%s: dimension %d)"
+                         % (layout, 1 if layout == "nchw_rgb" else 3))
+    packed, _ = _cnn_device_consts(torch, x.device, weights)
+    r = torch.empty((n, h, w), dtype=torch.float32, device=x.device) if want_float else None
+    r8 = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if want_u8 else None
+    rc = lib.rf_cnn_reflectance_packed_f32(x.data_ptr(), r.data_ptr() if want_float else None,
+                                           r8.data_ptr() if want_u8 else None, n, h, w,
+                                           _ffi.CNN_LAYOUTS[layout], packed.data_ptr(),
+                                           _ffi.current_stream_ptr(torch))
+    _ffi.check(rc, "rf_cnn_reflectance_packed_f32")
+    return r, r8
+
+
 _steps_dev = {}
 
 
