@@ -55,6 +55,12 @@ const char *rf_last_error(void);
    packed-weight slots of rf_cnn_reflectance_u8 and the guided filter's side streams.  Call it with
    no library work in flight. */
 int rf_shutdown(void);
+/* Frees the scratch rf_jbf_u8 keeps from call to call (one vote byte per 64x64 tile of its largest
+   launch, per device and stream, for at most 16 streams).  Call it with no rf_jbf_u8 work in flight
+   and no captured graph of such a call left to replay; rf_shutdown does the same.  Graphs that
+   captured rf_jbf_u8 on one stream share that stream's bytes: serialise their replays
+   (INTEGRATION.md). */
+int rf_jbf_release_scratch(void);
 
 /*
  * Joint bilateral filter, 8-bit.

@@ -72,6 +72,11 @@
  *                        exists for the default grey loop (gathers two steps ahead) and the colour loop, in
  *                        the tile and the slab kernel; under "jbf_lookahead1" (the round-4 grey loop) and
  *                        "jbf_compiler_loop" every wave keeps the mask, whatever this option says.
+ *   "jbf_no_two_wg"      joint bilateral, radius <= 36: grey tiles run in jbf_tile64_kernel at one workgroup
+ *                        per CU, as colour tiles do, in one launch (the default: a vote launch writes one
+ *                        byte per tile, jbf_tile64_kernel filters the tiles flagged as colour, and
+ *                        jbf_tile64x2_kernel the grey ones at two workgroups per CU - three launches, one
+ *                        where both buffers have one channel); identical bytes
  *   "colorize_chunk_px"  ragged colourise (rf_colorize_ragged_srgb_u8): pixels per workgroup chunk, a
  *                        multiple of 256 that replaces the plan rule (0 = the rule; anything else is
  *                        refused with RF_E_BADARG by the entry and the plan query); identical bytes.
@@ -149,6 +154,25 @@ int rf_debug_jbf_ragged_plan(int n, const int *heights, const int *widths, int j
 int rf_debug_jbf_ragged_slab_plan(int n, const int *heights, const int *widths, int joint_cn,
                                   int src_cn, int d, double sigma_color, double sigma_space, int flags,
                                   int *out, int cap);
+
+/* The route of rf_jbf_u8's grey tiles for a call of n images of h x w: the four ints {two-per-CU
+ * route taken (1 / 0), tile rows resident in the LDS (64 output rows + a slab's halo; 0 off the route),
+ * 64x64 tiles of the route's launches, bytes of the library's tile-flag buffer the call needs (one vote
+ * byte per tile, a power of two of at least 4 KiB; 0 where both buffers have one channel: no vote, one
+ * launch)} at out[0..3].  The resident rows are a slab window, not a ring: the tile is staged again for
+ * every slab.  Decided by the functions the entry launches from (the debug switches included); what the
+ * query cannot see - the LDS probes of the device, a capturing stream whose flag buffer would have to
+ * grow, more than 16 streams holding a buffer - sends a call down the one-per-CU path all the same:
+ * rf_debug_jbf_two_wg_calls counts the calls that really launched the route.
+ * Returns 1 on the route, 0 off it, or the entry's refusal code.  Host only: needs no device. */
+int rf_debug_jbf_two_wg_plan(int n, int h, int w, int joint_cn, int src_cn, int d, double sigma_color,
+                             double sigma_space, int flags, int *out);
+
+/* The number of rf_jbf_u8 calls of this process so far that launched the two-per-CU route (its vote
+ * launch where one is needed, jbf_tile64_kernel on the flagged tiles of a 3-channel src,
+ * jbf_tile64x2_kernel on the grey tiles), modulo 2^31.  A test that means to exercise the route asserts
+ * that the count moved. */
+int rf_debug_jbf_two_wg_calls(void);
 
 /* The launch plan of rf_colorize_ragged_srgb_u8 for images of these sizes: the ints {chunk_px,
  * workgroups} - the pixels one workgroup takes and the grid of the histogram and write kernels -

@@ -41,12 +41,14 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
            "rf_png_workspace_bytes", "rf_png_deflate_ragged_u8",
            "rf_png_unfilter_workspace_bytes", "rf_png_unfilter_ragged_u8",
            "rf_colorize_ragged_r8_srgb_u8", "rf_cnn_reflectance_f32",
-           "rf_cnn_reflectance_packed_f32")
+           "rf_cnn_reflectance_packed_f32", "rf_jbf_release_scratch")
 
 # include/reflectance_filtering_debug.h: test / benchmark switches, not part of the boundary
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
                  "rf_debug_jbf_points_plan", "rf_debug_jbf_ragged_plan",
-                 "rf_debug_jbf_ragged_slab_plan", "rf_debug_colorize_ragged_plan",
+                 "rf_debug_jbf_ragged_slab_plan", "rf_debug_jbf_two_wg_plan",
+                 "rf_debug_jbf_two_wg_calls",
+                 "rf_debug_colorize_ragged_plan",
                  "rf_debug_gf_ragged_plan", "rf_debug_png_plan")
 # switches that leave work out (wrong results, timing experiments only); all others keep the bytes
 RESULT_CHANGING_OPTIONS = ("jbf_stage_only", "gf_exp_skip")
@@ -81,6 +83,8 @@ def load_library():
         lib.rf_last_error.restype = ctypes.c_char_p
         lib.rf_shutdown.argtypes = []
         lib.rf_shutdown.restype = ci
+        lib.rf_jbf_release_scratch.argtypes = []
+        lib.rf_jbf_release_scratch.restype = ci
         lib.rf_jbf_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, cd, cd, ci, ci, vp]
         lib.rf_jbf_u8.restype = ci
         lib.rf_gf_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci]
@@ -166,6 +170,10 @@ def load_library():
         lib.rf_debug_jbf_ragged_plan.restype = ci
         lib.rf_debug_jbf_ragged_slab_plan.argtypes = [ci, vp, vp, ci, ci, ci, cd, cd, ci, vp, ci]
         lib.rf_debug_jbf_ragged_slab_plan.restype = ci
+        lib.rf_debug_jbf_two_wg_plan.argtypes = [ci, ci, ci, ci, ci, ci, cd, cd, ci, vp]
+        lib.rf_debug_jbf_two_wg_plan.restype = ci
+        lib.rf_debug_jbf_two_wg_calls.argtypes = []
+        lib.rf_debug_jbf_two_wg_calls.restype = ci
         lib.rf_debug_colorize_ragged_plan.argtypes = [ci, vp, vp, vp, ci]
         lib.rf_debug_colorize_ragged_plan.restype = ci
         lib.rf_debug_gf_ragged_plan.argtypes = [ci, vp, vp, ci, ci, ci, ci, vp, ci]
@@ -293,6 +301,21 @@ def jbf_ragged_slab_plan(sizes, joint_cn, src_cn, d, sigma_color, sigma_space, f
     if rc < 0:
         check(rc, "rf_debug_jbf_ragged_slab_plan")
     return tuple(int(v) for v in out)
+
+
+def jbf_two_wg_plan(n, h, w, joint_cn, src_cn, d, sigma_color, sigma_space, flags=0):
+    """The route of rf_jbf_u8's grey tiles for n images of h x w (rf_debug_jbf_two_wg_plan, host
+    only): (tile rows resident in the LDS, tiles of the launch, bytes of the tile-flag buffer) on the
+    two-workgroups-per-CU route, None off it."""
+    import numpy as np
+    lib = load_library()
+    out = np.zeros(4, dtype=np.int32)
+    rc = lib.rf_debug_jbf_two_wg_plan(int(n), int(h), int(w), int(joint_cn), int(src_cn), int(d),
+                                      float(sigma_color), float(sigma_space), int(flags),
+                                      out.ctypes.data)
+    if rc < 0:
+        check(rc, "rf_debug_jbf_two_wg_plan")
+    return tuple(int(v) for v in out[1:]) if rc == 1 else None
 
 
 def colorize_ragged_plan(sizes):

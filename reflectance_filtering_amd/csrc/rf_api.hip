@@ -9,6 +9,7 @@
 namespace rf {
 
 void jbf_shutdown();
+void jbf_scratch_release();
 void cnn_shutdown();
 void gf_shutdown();
 
@@ -45,7 +46,8 @@ extern "C" int rf_debug_option(const char *name, int value)
                                                       "gf_s1_cap",         "gf_s1_min_wgs",
                                                       "jbf_lookahead1",    "gf_s1_legacy_strips",
                                                       "gf_exact_all_flagged", "gf_cw_chan_run",   "gf_exact",
-                                                      "jbf_no_msad",       "colorize_chunk_px"};
+                                                      "jbf_no_msad",       "colorize_chunk_px",
+                                                      "jbf_no_two_wg"};
     static_assert(sizeof(names) / sizeof(names[0]) == rf::kDbgCount, "one name per DebugOption");
     if (name)
         for (int i = 0; i < rf::kDbgCount; i++)
@@ -104,6 +106,7 @@ extern "C" const char *rf_last_error(void) { return rf::last_error_buf(); }
 extern "C" int rf_shutdown(void)
 {
     rf::jbf_shutdown();
+    rf::jbf_scratch_release();
     rf::cnn_shutdown();
     rf::gf_shutdown();
     return RF_OK;

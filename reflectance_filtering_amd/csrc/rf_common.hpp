@@ -109,6 +109,7 @@ enum DebugOption {
     kDbgGfExact,           // guided filter: exact-row stage 2 (off by default: measured slower, profiles/r06_gf_exact.md)
     kDbgJbfNoMsad,         // joint bilateral: every wave takes the tap loop with the mask (none the masked-SAD form)
     kDbgColorizeChunkPx,   // ragged colourise: pixels per workgroup chunk (a multiple of 256; 0 = the plan rule)
+    kDbgJbfNoTwoWg,        // joint bilateral: grey tiles at one workgroup per CU (jbf_tile64_kernel), as before the two-per-CU route
     kDbgCount
 };
 int debug_get(int id);

@@ -33,6 +33,7 @@
 //   rf_jbf_common.hpp    the argument rules and per-pixel pieces shared with rf_jbf_points.hip.
 //   rf_jbf_f32.hip       the CV_32F filter (rf_jbf_f32): its own kernels, the same tap tables.
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <vector>
 
@@ -52,6 +53,7 @@ constexpr int kJbfMaxTiledR4 = 468;  // radius (rounded up to 4) the slab kernel
 constexpr int kJbfStageOnly = 0x1000, kJbfCompilerLoop = 0x2000, kJbfTile64Only = 0x4000;
 constexpr int kJbfLookahead1 = 0x8000;  // grey asm loop with its gathers one column step ahead (round-4 form)
 constexpr int kJbfNoMsad = 0x10000;     // every wave takes the tap loop with the mask (none the masked-SAD form)
+constexpr int kJbfVoteOnly = 0x20000;   // jbf_tile64x2_kernel: write the tiles' vote bytes and leave (set by its launcher only)
 
 // the test / benchmark switches (rf_debug_option) as they travel to the kernels: private flag bits
 int jbf_debug_flags()
@@ -394,17 +396,35 @@ struct JbfTilesArg<true> {
     using type = const JbfTileRec *__restrict__;
 };
 
+// The last argument of jbf_tile64_kernel: nothing, or (kFlagged: the colour-tile launch of the
+// two-workgroups-per-CU route, jbf_tile64x2_kernel below) one vote byte per tile - the workgroup of a
+// tile whose bit 0 is clear (a grey src) leaves at once.
+struct JbfNoTileFlags {};
+template <bool kFlagged>
+struct JbfTileFlagsArg {
+    using type = JbfNoTileFlags;
+};
+template <>
+struct JbfTileFlagsArg<true> {
+    using type = const uint8_t *__restrict__;
+};
+
 // TH = tile rows: 64 (64x64 tile), or 32 / 16 for the 32x128 and 16x256 strips that cover the
 // last h % 64 rows (same 1024 lanes, same tap loops, less padding; 3-channel sources only have
 // the 32-row strip, whose colour tile still fits the LDS in one pass).
-template <int SCN, int GREP, int CREP, int TLW, int TH = 64, bool kRagged = false>
+template <int SCN, int GREP, int CREP, int TLW, int TH = 64, bool kRagged = false, bool kFlagged = false>
 __global__ __launch_bounds__(1024) void jbf_tile64_kernel(
     const uint8_t *__restrict__ joint, const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
     int h, int w, int jcn, int radius, int border, const float *__restrict__ lut, int nz,
     const int *__restrict__ hwtab, const float *__restrict__ swsym, int sw_len,
     typename JbfTilesArg<kRagged>::type tiles_x, int tiles_per_img, int flags, int crows, int y_base,
-    int x_base)
+    int x_base, typename JbfTileFlagsArg<kFlagged>::type tile_flags)
 {
+    if constexpr (kFlagged) {
+        // (the same tile index as the first launch gave this workgroup: same grid, same mapping)
+        if ((tile_flags[xcd_contiguous_tile((int)blockIdx.x, (int)gridDim.x)] & 1) == 0)
+            return;
+    }
     constexpr int NT = 1024;
     constexpr int QW = NT / TH;   // lanes (4-pixel quads) per tile row
     constexpr int TW = 4 * QW;    // tile width
@@ -694,6 +714,33 @@ __global__ void lds_oob_probe_kernel(uint32_t *out)
         atomicOr(out, 1u);
 }
 
+// LDS of a workgroup of jbf_tile64x2_kernel (below): half of a CU's, so that two are resident.
+constexpr int kT64x2Lds = 81920;
+
+// The same probe for an allocation of half the LDS with a second workgroup resident on the CU: a read
+// beyond the workgroup's own allocation must return 0 although the address lies inside the CU's LDS,
+// where the neighbour (or, the LDS not being cleared between workgroups, an earlier one) has written
+// the pattern.  Launched with several workgroups per CU slot.
+__global__ __launch_bounds__(256) void lds_oob_probe_half_kernel(uint32_t *out)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    uint32_t *w = reinterpret_cast<uint32_t *>(smem);
+    for (int i = threadIdx.x; i < kT64x2Lds / 4; i += blockDim.x)
+        w[i] = 0xdeadbeefu;
+    __syncthreads();
+    uint32_t bad = 0;
+    const uint32_t addrs[5] = {(uint32_t)kT64x2Lds + 4u * threadIdx.x, (uint32_t)kT64x2Lds + 61056u,
+                               (uint32_t)kT64Lds - 4u, 262140u, (uint32_t)kT64x2Lds - 4u};
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        uint32_t v;
+        asm volatile("ds_read_b32 %0, %1\n s_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addrs[k]));
+        bad |= (k < 4) ? (v != 0u) : (v != 0xdeadbeefu);
+    }
+    if (bad)
+        atomicOr(out, 2u);
+}
+
 struct Tiled2Config {
     int th, lutrep;
     bool full_lut;  // stage all 256*jcn LUT entries and skip the per-tap clamp
@@ -733,15 +780,19 @@ int launch_tiled2(const JbfTables &t, bool full_lut, const uint8_t *joint, const
 std::mutex g_oob_mu;
 std::vector<int> g_oob_ok;  // per device: -1 unknown, 0 no, 1 yes (guarded by g_oob_mu)
 
-// Runs the probe once per device.  Synchronises the device (only on the first JBF call).
-int lds_oob_reads_zero(int dev, bool *ok)
+// Runs the probes once per device.  Synchronises the device (only on the first JBF call).
+// *ok: the rule holds for a workgroup that owns the whole LDS; *ok_half (if asked for): also for one
+// of two workgroups that own half of it each.
+int lds_oob_reads_zero(int dev, bool *ok, bool *ok_half = nullptr)
 {
     {
         std::lock_guard<std::mutex> lock(g_oob_mu);
         if ((int)g_oob_ok.size() <= dev)
             g_oob_ok.resize(dev + 1, -1);
         if (g_oob_ok[dev] >= 0) {
-            *ok = g_oob_ok[dev] == 1;
+            *ok = (g_oob_ok[dev] & 1) != 0;
+            if (ok_half)
+                *ok_half = (g_oob_ok[dev] & 2) != 0;
             return RF_OK;
         }
     }
@@ -761,13 +812,18 @@ int lds_oob_reads_zero(int dev, bool *ok)
     RF_HIP_CHECK(hipFuncSetAttribute((const void *)lds_oob_probe_kernel,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, kT64Lds));
     hipLaunchKernelGGL(lds_oob_probe_kernel, dim3(8), dim3(256), kT64Lds, ps, d_flag);
-    uint32_t flag = 1;
+    RF_HIP_CHECK(hipFuncSetAttribute((const void *)lds_oob_probe_half_kernel,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, kT64x2Lds));
+    hipLaunchKernelGGL(lds_oob_probe_half_kernel, dim3(2048), dim3(256), kT64x2Lds, ps, d_flag);
+    uint32_t flag = 3;
     RF_HIP_CHECK(hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, ps));
     RF_HIP_CHECK(hipStreamSynchronize(ps));
     (void)hipFree(d_flag);
     std::lock_guard<std::mutex> lock(g_oob_mu);
-    g_oob_ok[dev] = flag == 0 ? 1 : 0;
-    *ok = flag == 0;
+    g_oob_ok[dev] = (int)(~flag & 3u);  // bit 0: whole-LDS probe passed, bit 1: half-LDS probe passed
+    *ok = (flag & 1u) == 0;
+    if (ok_half)
+        *ok_half = (flag & 2u) == 0;
     return RF_OK;
 }
 
@@ -819,7 +875,7 @@ int launch_tile64(const JbfTables &t, int nz, int crows, const uint8_t *joint, c
                                      kT64Lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(1024), kT64Lds, stream, joint, src, dst,
                        h, w, jcn, t.radius, border, t.d_lut, nz, t.d_hw, t.d_swsym, t.sw_len,
-                       tiles_x, tiles_x * tiles_y, flags, crows, y_base, x_base);
+                       tiles_x, tiles_x * tiles_y, flags, crows, y_base, x_base, JbfNoTileFlags{});
     return RF_OK;
 }
 
@@ -867,12 +923,13 @@ Tile64Areas tile64_areas(const JbfTables &t, int nz, int grep, int crep, int scn
 template <int SCN, int GREP, int CREP>
 int launch_tile64_rows(const JbfTables &t, int nz, int crows, const uint8_t *joint,
                        const uint8_t *src, uint8_t *dst, int n, int h, int w, int jcn, int border,
-                       int flags, hipStream_t stream)
+                       int flags, hipStream_t stream, bool strips_only = false)
 {
+    // (strips_only: the 64x64 tiles of the main area have been launched by the two-per-CU route)
     const Tile64Areas a = tile64_areas(t, nz, GREP, CREP, SCN, flags, h, w);
     const int rows_main = a.rows_main, cols_main = a.cols_main, s32 = a.s32, s16 = a.s16, sx = a.sx;
     int rc = RF_OK;
-    if (rows_main > 0 && cols_main > 0)
+    if (rows_main > 0 && cols_main > 0 && !strips_only)
         rc = launch_tile64<SCN, GREP, CREP, 144>(t, nz, crows, joint, src, dst, n, h, w, jcn,
                                                  border, flags, stream, 0, rows_main, 0, cols_main);
     if (rc == RF_OK && s32)
@@ -995,7 +1052,7 @@ int launch_tile64_ragged(const JbfTables &t, int nz, int crows, const uint8_t *j
                                      kT64Lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(1024), kT64Lds, stream, joint, src, dst, 0,
                        0, jcn, t.radius, border, t.d_lut, nz, t.d_hw, t.d_swsym, t.sw_len, d_recs, 0,
-                       flags, crows, 0, 0);
+                       flags, crows, 0, 0, JbfNoTileFlags{});
     return RF_OK;
 }
 
@@ -1278,8 +1335,339 @@ int launch_slab_ragged(const JbfTables &t, int nz, const SlabShape &s, const uin
     return RF_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Two workgroups per CU (radius <= 36, pitch 144, 32 LUT replicas): the grey tiles of a call - a
+// single-channel src, or a 3-channel src whose tile and halo are grey, the metric's case - in
+// workgroups of 81,920 B of LDS and at most 64 VGPRs, so that a CU holds two of them: 8 waves per SIMD
+// in the tap loop, and one workgroup's staging, vote and stores behind the other's loop.  The kernel
+// holds the grey loop only.  The LUT sits at the end of the allocation (reads beyond it return 0:
+// lds_oob_probe_half_kernel), the rows in front of it hold 64 output rows plus a slab of the disk's tap
+// rows, walked as in jbf_slab_kernel: same loop (SLAB), accumulators in registers from slab to slab,
+// every pixel's taps in row-major order - the bytes of jbf_tile64_kernel.  The vote over the tile's
+// texels (a scan of tile and halo, the region jbf_tile64_kernel votes on) is a launch of this kernel of
+// its own (kJbfVoteOnly) that writes one byte per tile into tile_flags - every byte, so no memset - and
+// comes first; a grey joint is then staged in the J1 form at once.  A tile whose src is not grey is
+// not filtered here: a launch of jbf_tile64_kernel<.., kFlagged> over the same grid filters exactly
+// those tiles, and the filtering launch of this kernel leaves them after one scalar load.  Three
+// launches then - vote, flagged colour tiles, grey tiles, in this order: for a grey batch the last one
+// does the work.  Single-channel buffers need no vote (one launch).
+// ------------------------------------------------------------------------------------------
+// rows of the tile in front of the LUT, and the tap rows of a slab (0: no room)
+int tile64x2_slab_rows(int nz, int grep, int tlw)
+{
+    // (nothing beside tile and LUT: at sigma_color 20 the LUT's 289 entries leave exactly 78 rows of pitch 144)
+    const int rows = (kT64x2Lds - nz * grep * 4) / (tlw * 4);
+    return rows >= 64 ? rows - 64 + 1 : 0;
+}
+
+// (the second launch bound is waves per SIMD: two workgroups of 16 waves on a CU's four SIMDs)
+template <int GREP, int TLW>
+__global__ __launch_bounds__(1024, 8) void jbf_tile64x2_kernel(
+    const uint8_t *__restrict__ joint, const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
+    int h, int w, int jcn, int scn, int radius, int border, const float *__restrict__ lut, int nz,
+    const int *__restrict__ hwtab, const float *__restrict__ swsym, int sw_len, int tiles_x,
+    int tiles_per_img, int flags, int slab_rows, uint8_t *__restrict__ tile_flags)
+{
+    constexpr int NT = 1024, Q4 = TLW / 4, QW = 16;
+    static_assert(TLW % 32 == 16, "row pitch keeps the rows of a half-wave on disjoint banks");
+    extern __shared__ __align__(16) unsigned char smem[];
+    // the vote's word lies in the tile's first texel: the vote is over (every lane has read the word) before
+    // the barrier in front of the first staging
+    int *flag_word = reinterpret_cast<int *>(smem);
+    uint32_t *tile4 = reinterpret_cast<uint32_t *>(smem);
+    const int tid = threadIdx.x;
+    if (tid == 0)
+        *flag_word = 3;
+    __syncthreads();
+    const int tile_id = xcd_contiguous_tile((int)blockIdx.x, (int)gridDim.x);
+    const int img_idx = tile_id / tiles_per_img;
+    const int t_in_img = tile_id - img_idx * tiles_per_img;
+    const int tile_y0 = (t_in_img / tiles_x) * 64;
+    const int tile_x0 = (t_in_img % tiles_x) * 64;
+    const size_t img = (size_t)img_idx * h * w;
+    const int r4 = (radius + 3) & ~3;
+    const int tx = tid % QW, ty = tid / QW;
+    // the vote of jbf_tile64_kernel, in a launch of its own (kJbfVoteOnly) in front of the filtering ones: is
+    // every src texel of tile and halo grey (B = G = R), and every joint texel?  The tile's byte: bit 0 = the
+    // src is NOT grey, bit 1 = the joint is.  (1-channel buffers need no look: no vote launch, no bytes.)
+    int grey_joint = 1;
+    if (flags & kJbfVoteOnly) {
+        int grey = 1;
+        const int rows_all = 64 + 2 * radius;
+        for (int item = tid; item < rows_all * Q4; item += NT) {
+            const int ry = item / Q4, k = item - ry * Q4;
+            const int gy = border_interpolate(tile_y0 - radius + ry, h, border);
+            uint32_t jv[4], sv[4];
+            load_tile_quad(joint, src, img, gy, tile_x0 - r4 + 4 * k, w, jcn, scn, border, jv, sv);
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                if (scn == 3)
+                    grey &= (int)(((sv[u] ^ (sv[u] >> 8)) & 0xffffu) == 0u);
+                if (jcn == 3)
+                    grey_joint &= (int)(((jv[u] ^ (jv[u] >> 8)) & 0xffffu) == 0u);
+            }
+        }
+        // (the same word in every lane; said so, or the slab bounds - scalar-load addresses - count as divergent)
+        const int bits = block_all2(grey, grey_joint, flag_word);  // (barrier inside)
+        if (tid == 0)
+            tile_flags[tile_id] = (uint8_t)(((bits & 1) ? 0 : 1) | (bits & 2));
+        return;
+    }
+    if (tile_flags) {
+        // (one scalar load; the same byte in every lane - the slab bounds below are scalar-load addresses)
+        const int byte = __builtin_amdgcn_readfirstlane((int)tile_flags[tile_id]);
+        if (byte & 1)
+            return;  // a colour tile: jbf_tile64_kernel<.., kFlagged> filters it
+        grey_joint = (byte >> 1) & 1;
+    }
+    float *lut_g = reinterpret_cast<float *>(smem + kT64x2Lds - nz * GREP * 4);
+    for (int i = tid; i < nz * GREP; i += NT)
+        lut_g[i] = lut[i / GREP];
+    const uint32_t lut_lane_addr = lds_addr(lut_g) + (uint32_t)(tid & (GREP - 1)) * 4u;
+    const uint32_t tile_lane_addr = lds_addr(tile4) + (uint32_t)tx * 4u;
+    // grey src and grey joint: the joint field of a texel holds the value times the LUT's byte stride
+    // (jbf_tile64_kernel's j1 / j1_late), which turns the SAD of the tap loop into the gather address
+    const bool j1 = grey_joint != 0;
+    const uint32_t j1_scale = (uint32_t)(jcn == 1 ? 1 : 3) * (GREP * 4u);
+    // the lane's four centre pixels (their joint values; border arithmetic as in the tile)
+    uint32_t jc[kPix];
+    float sum1[kPix][1], wsum[kPix];
+    {
+        uint32_t jv[4], sv[4];
+        load_tile_quad(joint, src, img, border_interpolate(tile_y0 + ty, h, border), tile_x0 + 4 * tx, w, jcn,
+                       scn, border, jv, sv);
+#pragma unroll
+        for (int p = 0; p < kPix; p++) {
+            jc[p] = j1 ? (jv[p] & 0xffu) * j1_scale : jv[p] & 0x00ffffffu;
+            sum1[p][0] = 0.f;
+            wsum[p] = 0.f;
+        }
+    }
+    // per wave, for all its slabs: the masked-SAD form of the loop unless a centre has a zero channel
+    const bool msad = !j1 && !(flags & kJbfNoMsad) && jbf_wave_takes_msad(jc);
+    for (int i0 = -radius; i0 <= radius; i0 += slab_rows) {
+        const int i1 = min(i0 + slab_rows - 1, radius);
+        const int tlh = 64 + (i1 - i0);
+        __syncthreads();  // everyone is done with the previous contents of the tile
+        for (int item = tid; item < tlh * Q4; item += NT) {
+            const int ry = item / Q4, k = item - ry * Q4;
+            const int gy = border_interpolate(tile_y0 + i0 + ry, h, border);
+            uint32_t jv[4], sv[4];
+            load_tile_quad(joint, src, img, gy, tile_x0 - r4 + 4 * k, w, jcn, scn, border, jv, sv);
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const uint32_t jfield = j1 ? (jv[u] & 0xffu) * j1_scale : jv[u];
+                tile4[ry * TLW + u * Q4 + k] = jfield | (sv[u] << 24);
+            }
+        }
+        __syncthreads();
+        if (j1)
+            jbf_tap_loop_grey4_la2<GREP, TLW, true, true>(lut_lane_addr, swsym, tile_lane_addr, jc, ty,
+                                                          radius, r4, sw_len, hwtab, sum1, wsum, i0, i1, -i0);
+        else if (msad)
+            jbf_tap_loop_grey4_la2<GREP, TLW, false, true, true>(lut_lane_addr, swsym, tile_lane_addr, jc,
+                                                                 ty, radius, r4, sw_len, hwtab, sum1, wsum,
+                                                                 i0, i1, -i0);
+        else
+            jbf_tap_loop_grey4_la2<GREP, TLW, false, true>(lut_lane_addr, swsym, tile_lane_addr, jc, ty,
+                                                           radius, r4, sw_len, hwtab, sum1, wsum, i0, i1,
+                                                           -i0);
+    }
+    if (scn == 1)
+        store_quad<1, 1>(dst, img, tile_y0 + ty, tile_x0 + 4 * tx, h, w, sum1, wsum, flags);
+    else
+        store_quad<1, 3>(dst, img, tile_y0 + ty, tile_x0 + 4 * tx, h, w, sum1, wsum, flags);
+}
+
+// The flag bytes of the two-launch route: one library-owned buffer per (device, stream), kept from
+// call to call and enlarged only outside a stream capture.  An outgrown buffer is kept until
+// rf_jbf_release_scratch / rf_shutdown: a captured graph may still name it.
+struct TileFlagBuf {
+    int dev;
+    hipStream_t stream;
+    uint8_t *p;
+    size_t bytes;
+};
+std::mutex g_tf_mu;
+std::vector<TileFlagBuf> g_tf;        // (guarded by g_tf_mu)
+std::vector<uint8_t *> g_tf_retired;  // (guarded by g_tf_mu)
+constexpr size_t kTileFlagStreams = 16;  // (device, stream) pairs that hold a buffer; further ones take the old path
+std::atomic<int> g_two_wg_calls{0};      // calls that launched the route (rf_debug_jbf_two_wg_calls)
+
+// bytes of the buffer that serves a launch of `tiles` tiles: the power of two >= tiles, 4 KiB at least
+size_t tile_flag_bytes(size_t tiles)
+{
+    size_t b = 4096;
+    while (b < tiles)
+        b <<= 1;
+    return b;
+}
+
+// *out = nullptr: no buffer of that size and none may be made now (the stream is capturing, or
+// kTileFlagStreams other streams hold one)
+int get_tile_flags(int dev, hipStream_t stream, size_t tiles, uint8_t **out)
+{
+    *out = nullptr;
+    std::lock_guard<std::mutex> lock(g_tf_mu);
+    size_t at = g_tf.size();
+    for (size_t i = 0; i < g_tf.size(); i++)
+        if (g_tf[i].dev == dev && g_tf[i].stream == stream)
+            at = i;
+    if (at < g_tf.size() && g_tf[at].bytes >= tiles) {
+        *out = g_tf[at].p;
+        return RF_OK;
+    }
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return RF_OK;
+    }
+    // a stream beyond the kTileFlagStreams that hold a buffer gets none (no buffer is taken from a stream: a
+    // captured graph may name it), so what the library holds is bounded: per stream the sizes it grew through
+    if (at == g_tf.size() && g_tf.size() >= kTileFlagStreams)
+        return RF_OK;
+    uint8_t *p = nullptr;
+    {
+        CaptureRelax relax;  // (another thread of the process may be capturing in the global mode)
+        RF_HIP_CHECK(hipMalloc(&p, tile_flag_bytes(tiles)));
+    }
+    if (at < g_tf.size()) {
+        g_tf_retired.push_back(g_tf[at].p);
+        g_tf.erase(g_tf.begin() + at);
+    }
+    g_tf.push_back(TileFlagBuf{dev, stream, p, tile_flag_bytes(tiles)});
+    *out = p;
+    return RF_OK;
+}
+
+// Does a call take the two-workgroups-per-CU route?  Decided from the tables and the flags alone.
+// *slab_rows: tap rows per slab (the tile holds 64 + slab_rows - 1 rows).
+bool two_wg_choose(const JbfTables &t, int nz, int src_cn, int flags, int *slab_rows)
+{
+    *slab_rows = 0;
+    if (debug_get(kDbgJbfNoTwoWg) || debug_get(kDbgJbfTune) ||
+        (flags & (RF_JBF_FORCE_GENERIC | kJbfStageOnly | kJbfCompilerLoop | kJbfLookahead1)))
+        return false;
+    Tile64Shape shape;
+    if (t.r4 > 36 || !tile64_choose(t, nz, src_cn, flags, &shape) || shape.tlw != 144 || shape.grep != 32)
+        return false;
+    *slab_rows = tile64x2_slab_rows(nz, 32, 144);
+    return *slab_rows >= 8;
+}
+
+// The 64x64 tiles of the main area [0, rows) x [0, cols) of every image: with kJbfVoteOnly in flags the
+// launch that writes their vote bytes, without it the launch that filters the grey ones (tile_flags may
+// be NULL then: single-channel buffers, every tile grey).
+int launch_tile64x2(const JbfTables &t, int nz, int slab_rows, const uint8_t *joint, const uint8_t *src,
+                    uint8_t *dst, int n, int h, int w, int jcn, int scn, int border, int flags,
+                    hipStream_t stream, int rows, int cols, uint8_t *tile_flags)
+{
+    const int tiles_x = ceil_div(cols, 64), tiles_y = ceil_div(rows, 64);
+    const long long blocks = (long long)tiles_x * tiles_y * n;
+    auto kern = jbf_tile64x2_kernel<32, 144>;
+    RF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kT64x2Lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(1024), kT64x2Lds, stream, joint, src, dst, h, w,
+                       jcn, scn, t.radius, border, t.d_lut, nz, t.d_hw, t.d_swsym, t.sw_len, tiles_x,
+                       tiles_x * tiles_y, flags, slab_rows, tile_flags);
+    return RF_OK;
+}
+
+template <int CREP>
+int launch_tile64_flagged(const JbfTables &t, int nz, int crows, const uint8_t *joint, const uint8_t *src,
+                          uint8_t *dst, int n, int h, int w, int jcn, int border, int flags,
+                          hipStream_t stream, int rows, int cols, const uint8_t *tile_flags)
+{
+    const int tiles_x = ceil_div(cols, 64), tiles_y = ceil_div(rows, 64);
+    const long long blocks = (long long)tiles_x * tiles_y * n;
+    auto kern = jbf_tile64_kernel<3, 32, CREP, 144, 64, false, true>;
+    RF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     kT64Lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(1024), kT64Lds, stream, joint, src, dst, h, w,
+                       jcn, t.radius, border, t.d_lut, nz, t.d_hw, t.d_swsym, t.sw_len, tiles_x,
+                       tiles_x * tiles_y, flags, crows, 0, 0, tile_flags);
+    return RF_OK;
+}
+
+// A call on the two-per-CU route: the vote (3-channel src or joint), the flagged tiles of a 3-channel src
+// in jbf_tile64_kernel, the grey tiles in jbf_tile64x2_kernel, the strips as ever.  *done = false (nothing
+// launched): no main area, or no flag buffer may be made now - the caller takes the one-per-CU path.
+int launch_two_wg(const JbfTables &t, int nz, const Tile64Shape &shape, int slab_rows,
+                  const uint8_t *joint, const uint8_t *src, uint8_t *dst, int n, int h, int w, int jcn,
+                  int scn, int border, int flags, hipStream_t stream, bool *done)
+{
+    *done = false;
+    const Tile64Areas a = tile64_areas(t, nz, shape.grep, shape.crep, scn, flags, h, w);
+    if (a.rows_main <= 0 || a.cols_main <= 0)
+        return RF_OK;
+    const long long blocks = (long long)ceil_div(a.cols_main, 64) * ceil_div(a.rows_main, 64) * n;
+    if (blocks > 0x7fffffffLL)
+        return fail(RF_E_UNSUPPORTED, "rf_jbf_u8: batch too large for one launch");
+    // launch order: the vote, the flagged colour tiles, the grey tiles - the launch that does a grey batch's
+    // work comes last (a profile that takes a call's last launch for the call reads the metric kernel)
+    uint8_t *tile_flags = nullptr;
+    int rc = RF_OK;
+    if (scn == 3 || jcn == 3) {
+        if (int bad = get_tile_flags(t.device, stream, (size_t)blocks, &tile_flags))
+            return bad;
+        if (!tile_flags)
+            return RF_OK;
+        rc = launch_tile64x2(t, nz, slab_rows, joint, src, dst, n, h, w, jcn, scn, border, flags | kJbfVoteOnly,
+                             stream, a.rows_main, a.cols_main, tile_flags);
+    }
+    if (rc == RF_OK && scn == 3)
+        rc = shape.crep == 32 ? launch_tile64_flagged<32>(t, nz, shape.crows, joint, src, dst, n, h, w, jcn,
+                                                          border, flags, stream, a.rows_main, a.cols_main,
+                                                          tile_flags)
+                              : launch_tile64_flagged<16>(t, nz, shape.crows, joint, src, dst, n, h, w, jcn,
+                                                          border, flags, stream, a.rows_main, a.cols_main,
+                                                          tile_flags);
+    if (rc == RF_OK)
+        rc = launch_tile64x2(t, nz, slab_rows, joint, src, dst, n, h, w, jcn, scn, border, flags, stream,
+                             a.rows_main, a.cols_main, tile_flags);
+    if (rc == RF_OK && (a.s32 || a.s16 || a.sx)) {
+        if (scn == 3)
+            rc = shape.crep == 32 ? launch_tile64_rows<3, 32, 32>(t, nz, shape.crows, joint, src, dst, n, h, w,
+                                                                  jcn, border, flags, stream, true)
+                                  : launch_tile64_rows<3, 32, 16>(t, nz, shape.crows, joint, src, dst, n, h, w,
+                                                                  jcn, border, flags, stream, true);
+        else
+            rc = shape.crep == 32 ? launch_tile64_rows<1, 32, 32>(t, nz, shape.crows, joint, src, dst, n, h, w,
+                                                                  jcn, border, flags, stream, true)
+                                  : launch_tile64_rows<1, 32, 16>(t, nz, shape.crows, joint, src, dst, n, h, w,
+                                                                  jcn, border, flags, stream, true);
+    }
+    *done = rc == RF_OK;
+    if (*done)
+        g_two_wg_calls.fetch_add(1, std::memory_order_relaxed);
+    return rc;
+}
+
 }  // namespace
+
+void jbf_scratch_release()
+{
+    std::lock_guard<std::mutex> lock(g_tf_mu);
+    for (const TileFlagBuf &b : g_tf)
+        (void)hipFree(b.p);
+    for (uint8_t *p : g_tf_retired)
+        (void)hipFree(p);
+    g_tf.clear();
+    g_tf_retired.clear();
+}
+
 }  // namespace rf
+
+extern "C" int rf_debug_jbf_two_wg_calls(void)
+{
+    return rf::g_two_wg_calls.load(std::memory_order_relaxed) & 0x7fffffff;
+}
+
+extern "C" int rf_jbf_release_scratch(void)
+{
+    rf::jbf_scratch_release();
+    return RF_OK;
+}
 
 extern "C" int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst, int n, int h,
                          int w, int joint_cn, int src_cn, int d, double sigma_color,
@@ -1330,8 +1718,8 @@ extern "C" int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst,
     // tune 7 forces the 64x64 kernel, tune 1..6 the 64xTH kernel
     bool done = false;
     if (!(flags & RF_JBF_FORCE_GENERIC) && t.r4 <= kJbfMaxTiledR4 && (tune == 0 || tune == 7)) {
-        bool oob_ok = false;
-        rc = lds_oob_reads_zero(t.device, &oob_ok);
+        bool oob_ok = false, oob_half = false;
+        rc = lds_oob_reads_zero(t.device, &oob_ok, &oob_half);
         if (rc != RF_OK)
             return rc;
         // table entries before the zero tail (the whole table if it has none)
@@ -1339,8 +1727,16 @@ extern "C" int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst,
         if (oob_ok) {
             Tile64Shape shape;
             if (tile64_choose(t, nz, src_cn, flags, &shape)) {
+                // pitch 144 at 32 replicas: grey tiles at two workgroups per CU
+                int slab2 = 0;
+                if (oob_half && two_wg_choose(t, nz, src_cn, flags, &slab2)) {
+                    rc = launch_two_wg(t, nz, shape, slab2, joint, src, dst, n, h, w, jcn_kernel, src_cn,
+                                       border, flags, stream, &done);
+                    if (rc != RF_OK)
+                        return rc;
+                }
 #define RF_T64(G_, C_, W_)                                                                        \
-    if (shape.grep == G_ && shape.crep == C_ && shape.tlw == W_) {                                \
+    if (!done && shape.grep == G_ && shape.crep == C_ && shape.tlw == W_) {                       \
         if (W_ == 144)                                                                            \
             rc = src_cn == 3 ? launch_tile64_rows<3, G_, C_>(t, nz, shape.crows, joint, src, dst, \
                                                              n, h, w, jcn_kernel, border, flags,  \
@@ -1541,6 +1937,40 @@ extern "C" int rf_debug_jbf_ragged_slab_plan(int n, const int *heights, const in
                                (int)std::min<size_t>(plan.recs[0].size(), 0x7fffffff)};
         std::copy(record, record + 7, out);
     }
+    return 1;
+}
+
+extern "C" int rf_debug_jbf_two_wg_plan(int n, int h, int w, int joint_cn, int src_cn, int d,
+                                        double sigma_color, double sigma_space, int flags, int *out)
+{
+    using namespace rf;
+    const char *who = "rf_debug_jbf_two_wg_plan";
+    size_t px, tiles;
+    if (n < 1 || !out)
+        return fail(RF_E_BADARG, "%s: bad n=%d or NULL out", who, n);
+    if (int bad = ragged_check(who, 1, &h, &w, joint_cn, src_cn, d, sigma_space, RF_BORDER_DEFAULT, flags,
+                               &px, &tiles))
+        return bad;
+    std::vector<float> lut;
+    const JbfTables t = jbf_host_tables(jbf_radius(d, jbf_sigma(sigma_space)),
+                                        jbf_table_cn(joint_cn, flags), jbf_sigma(sigma_color),
+                                        jbf_sigma(sigma_space), lut);
+    flags |= jbf_debug_flags();
+    const int nz = t.lut_len < 256 * t.joint_cn ? t.lut_len - 1 : t.lut_len;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    int slab_rows = 0;
+    Tile64Shape shape;
+    if (t.r4 > kJbfMaxTiledR4 || !two_wg_choose(t, nz, src_cn, flags, &slab_rows) ||
+        !tile64_choose(t, nz, src_cn, flags, &shape))
+        return 0;
+    const Tile64Areas a = tile64_areas(t, nz, shape.grep, shape.crep, src_cn, flags, h, w);
+    const long long blocks = (long long)ceil_div(a.cols_main, 64) * ceil_div(a.rows_main, 64) * n;
+    if (a.rows_main <= 0 || a.cols_main <= 0 || blocks > 0x7fffffffLL)
+        return 0;
+    out[0] = 1;
+    out[1] = 64 + slab_rows - 1;
+    out[2] = (int)blocks;
+    out[3] = src_cn == 3 || joint_cn == 3 ? (int)tile_flag_bytes((size_t)blocks) : 0;
     return 1;
 }
 

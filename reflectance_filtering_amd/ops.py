@@ -20,7 +20,10 @@ _png_decode_workspaces = {}
 
 def release_workspaces():
     """Drop the cached guided-filter, ragged-bilateral, ragged-colourise, ragged-guided and PNG-encode
-    scratch buffers and CNN constants (device memory)."""
+    scratch buffers and CNN constants (device memory), and the tile-flag bytes the library keeps for
+    joint_bilateral_u8 (rf_jbf_release_scratch: no such call may be in flight)."""
+    if _ffi._lib is not None:
+        _ffi._lib.rf_jbf_release_scratch()
     _png_workspaces.clear()
     _png_decode_workspaces.clear()
     del _png_host[:]
