@@ -12,6 +12,20 @@
  * (H x W x C), tightly packed, batched along the leading dimension n; every
  * image of a batch is filtered independently (no inter-image or inter-GPU
  * traffic; shard batches across GPUs by giving each process its own slice).
+ *
+ * Buffers (held for every entry by tests/test_gpu_buffer_contract.py, with every buffer at odd and
+ * even offsets from a 256-byte boundary, guard bytes around each and 0x00 / 0xA5 / 0xFF in a workspace
+ * of exactly the queried size):
+ *   - an image, point, weight or result buffer may start at any address that is a multiple of its
+ *     element size (uint8 images at any byte: a slice of a batch of odd-sized images is a valid
+ *     argument); only a workspace has an alignment rule - 16 bytes, stated with each entry - and where
+ *     an entry says "scratch" it means this;
+ *   - the contents of a workspace on entry are arbitrary: a call initialises every counter, flag and
+ *     table it reads, so a workspace need not be cleared and may be reused call after call;
+ *   - a call writes nothing outside its outputs and the workspace_bytes bytes it was given (the size
+ *     query's answer is always enough), and no result depends on the bytes around an input;
+ *   - a call leaves its inputs alone, except where an entry says otherwise (dst == src of the guided
+ *     filter, `raw` of rf_png_unfilter_ragged_u8).
  */
 #ifndef REFLECTANCE_FILTERING_H
 #define REFLECTANCE_FILTERING_H
@@ -122,8 +136,10 @@ int rf_jbf_ragged_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst, int
  *   same exact integers).  rf_gf_workspace_bytes sizes the workspace for the radius it is given.
  *   iterations >= 1: the filter is applied `iterations` times with the same guide, the uint8
  *   result of one pass being the src of the next (the reference's "3x GF" chain of CLI runs).
- *   workspace: device scratch of at least rf_gf_workspace_bytes(1, ...) bytes; larger
- *   workspaces let more images of the batch be in flight at once.
+ *   workspace: device scratch of at least rf_gf_workspace_bytes(1, ...) bytes, 16-byte aligned (not
+ *   checked: its parts are laid out at multiples of 16 bytes from its start, and the float route
+ *   keeps double row sums among them);
+ *   larger workspaces let more images of the batch be in flight at once.
  *   stream: all work is ordered after what `stream` holds at the call and before what is
  *   enqueued on it afterwards; inside, half of a batch may run on a side stream of the library
  *   that is forked from and joined back into `stream` with events (graph capture keeps working).
@@ -281,7 +297,9 @@ int rf_cnn_reflectance_packed_f32(const float *x, float *r_out, uint8_t *r_u8_ou
  *                trunc(((1.055*x)^(1/2.4) - 0.055) * 255) >= k under the HOST's pow (all finite;
  *                k >= 247 lie above 1);
  *                this makes the bytes exact for the libm the reference would have used
- *   workspace    device scratch, rf_colorize_workspace_bytes(n) bytes
+ *   workspace    device scratch, rf_colorize_workspace_bytes(n) bytes, 16-byte aligned (not checked:
+ *                it holds the selection state of each image - 64-bit keys and ranks, a 256-bin
+ *                histogram - which the call initialises itself)
  */
 size_t rf_colorize_workspace_bytes(int n);
 int rf_colorize_srgb_u8(const uint8_t *bgr, const float *r, uint8_t *refl_out, uint8_t *shading_out,
@@ -349,6 +367,9 @@ int rf_colorize_ragged_r8_srgb_u8(const uint8_t *bgr, const uint8_t *r8, uint8_t
  *     image returns RF_E_UNSUPPORTED (OpenCV switches to a Gaussian blur there), and so does
  *     BORDER_CONSTANT (its zero padding indexes OpenCV's table out of bounds).
  *   rf_gf_f32: guidedFilter on float guide/src, float result (no rounding), `iterations` chained.
+ *   Both workspaces: device scratch of at least the size query's bytes, 16-byte aligned (not checked:
+ *   rf_jbf_f32 keeps 32-bit range words and its float tables there, rf_gf_f32 double row sums and
+ *   float planes, laid out from the workspace's start).
  */
 size_t rf_jbf_f32_workspace_bytes(int n, int joint_cn);
 int rf_jbf_f32(const float *joint, const float *src, float *dst, int n, int h, int w, int joint_cn,
@@ -385,7 +406,9 @@ int rf_whdr_f32(const float *refl, int n, int c, int h, int w, const int *points
  *                  (sigma_color[p], sigma_space[p]); sets may differ in sigma_space, i.e. in radius
  *   out            n_params*total_points*src_cn uint8 device, must not overlap an input
  *   workspace      device scratch of at least rf_jbf_points_workspace_bytes(n_params, sigma_space,
- *                  d, joint_cn, flags) bytes (0 there = arguments the call refuses)
+ *                  d, joint_cn, flags) bytes (0 there = arguments the call refuses), 16-byte aligned
+ *                  (not checked: chunk records, 8-byte taps and float tables, each part at a multiple
+ *                  of 256 bytes from its start)
  * out[p][k][c] is, byte for byte, what rf_jbf_u8(joint, src, ..., d, sigma_color[p],
  * sigma_space[p], border, flags) writes at pixel points[k] of its image: the same radius rule,
  * sigma <= 0 rule and refusals, the same per-pixel arithmetic (taps in row-major disk order,
@@ -417,7 +440,7 @@ int rf_jbf_points_u8(const uint8_t *joint, const uint8_t *src, int n, int h, int
  *                  sigma_space, d, joint_cn, flags) bytes: rf_jbf_points_workspace_bytes of the same
  *                  arguments plus one 256-byte-aligned block of 16 * n bytes (a record of first
  *                  pixel, height and width per image, staged with the tables in the call's one copy);
- *                  0 = arguments the call refuses
+ *                  0 = arguments the call refuses; 16-byte aligned like rf_jbf_points_u8's
  * Everything else is rf_jbf_points_u8's contract: out[p][k][c] is, byte for byte, what rf_jbf_u8 on
  * image i alone (n = 1, heights[i], widths[i]) writes at pixel points[k]; the same radius, sigma,
  * flag and border rules and refusals; out must not overlap an input (judged on the summed pixel
