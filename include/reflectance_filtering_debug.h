@@ -73,10 +73,18 @@
  *                        the tile and the slab kernel; under "jbf_lookahead1" (the round-4 grey loop) and
  *                        "jbf_compiler_loop" every wave keeps the mask, whatever this option says.
  *   "jbf_no_two_wg"      joint bilateral, radius <= 36: grey tiles run in jbf_tile64_kernel at one workgroup
- *                        per CU, as colour tiles do, in one launch (the default: a vote launch writes one
- *                        byte per tile, jbf_tile64_kernel filters the tiles flagged as colour, and
- *                        jbf_tile64x2_kernel the grey ones at two workgroups per CU - three launches, one
- *                        where both buffers have one channel); identical bytes
+ *                        per CU, as colour tiles do, in one launch (the default: the grey map - a clearing
+ *                        launch and one pass over the images - writes one byte per tile, jbf_tile64_kernel
+ *                        filters the tiles flagged as colour, and jbf_tile64x2_kernel the grey ones at two
+ *                        workgroups per CU - four launches, three with a single-channel src, one where both
+ *                        buffers have one channel); identical bytes
+ *   "jbf_vote_scan"      joint bilateral, two-per-CU route: the tile bytes come from one launch of
+ *                        jbf_tile64x2_kernel in which every tile scans its own region, tile and halo (the
+ *                        form before the grey map, which reads every texel 4.6 times at radius 33; a call
+ *                        with a WRAP border takes it without the switch); identical tile bytes, identical bytes
+ *   "jbf_no_dead_skip"   joint bilateral, two-per-CU route: the waves of a tile whose four rows all lie
+ *                        below the image walk the tap loop like the others (the default: they stage, meet
+ *                        the barriers and skip the loop); identical bytes
  *   "colorize_chunk_px"  ragged colourise (rf_colorize_ragged_srgb_u8): pixels per workgroup chunk, a
  *                        multiple of 256 that replaces the plan rule (0 = the rule; anything else is
  *                        refused with RF_E_BADARG by the entry and the plan query); identical bytes.
@@ -157,8 +165,8 @@ int rf_debug_jbf_ragged_slab_plan(int n, const int *heights, const int *widths, 
 
 /* The route of rf_jbf_u8's grey tiles for a call of n images of h x w: the four ints {two-per-CU
  * route taken (1 / 0), tile rows resident in the LDS (64 output rows + a slab's halo; 0 off the route),
- * 64x64 tiles of the route's launches, bytes of the library's tile-flag buffer the call needs (one vote
- * byte per tile, a power of two of at least 4 KiB; 0 where both buffers have one channel: no vote, one
+ * 64x64 tiles of the route's launches, bytes of the library's tile-flag buffer the call needs (one
+ * byte per tile, a power of two of at least 4 KiB; 0 where both buffers have one channel: no bytes, one
  * launch)} at out[0..3].  The resident rows are a slab window, not a ring: the tile is staged again for
  * every slab.  Decided by the functions the entry launches from (the debug switches included); what the
  * query cannot see - the LDS probes of the device, a capturing stream whose flag buffer would have to
@@ -168,11 +176,20 @@ int rf_debug_jbf_ragged_slab_plan(int n, const int *heights, const int *widths, 
 int rf_debug_jbf_two_wg_plan(int n, int h, int w, int joint_cn, int src_cn, int d, double sigma_color,
                              double sigma_space, int flags, int *out);
 
-/* The number of rf_jbf_u8 calls of this process so far that launched the two-per-CU route (its vote
- * launch where one is needed, jbf_tile64_kernel on the flagged tiles of a 3-channel src,
- * jbf_tile64x2_kernel on the grey tiles), modulo 2^31.  A test that means to exercise the route asserts
- * that the count moved. */
+/* The number of rf_jbf_u8 calls of this process so far that launched the two-per-CU route (the grey map
+ * that writes the tile bytes where a buffer has three channels - or, under "jbf_vote_scan", the scan
+ * launch -, jbf_tile64_kernel on the flagged tiles of a 3-channel src, jbf_tile64x2_kernel on the grey
+ * tiles), modulo 2^31.  A test that means to exercise the route asserts that the count moved. */
 int rf_debug_jbf_two_wg_calls(void);
+
+/* The tile bytes of the two-per-CU route as the last call on `stream` (on the current device) left them:
+ * copies min(cap, size of the stream's tile-flag buffer) bytes to the HOST array out and returns that
+ * number, 0 where the stream holds no buffer.  Byte t belongs to tile t of the route's launches (image
+ * by image, row by row of the main area's 64x64 tiles): bit 0 = the src is not grey somewhere in the
+ * tile's region (tile and halo as staged, through the border rule), bit 1 = the joint is grey
+ * everywhere in it; bytes beyond the last call's tiles are whatever earlier calls left.  SYNCHRONISES
+ * the stream and cannot be captured into a graph (RF_E_UNSUPPORTED on a capturing stream). */
+int rf_debug_jbf_tile_flags(void *stream, unsigned char *out, int cap);
 
 /* The launch plan of rf_colorize_ragged_srgb_u8 for images of these sizes: the ints {chunk_px,
  * workgroups} - the pixels one workgroup takes and the grid of the histogram and write kernels -

@@ -47,7 +47,7 @@ EXPORTS = ("rf_version", "rf_last_error", "rf_shutdown", "rf_jbf_u8", "rf_gf_wor
 DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info",
                  "rf_debug_jbf_points_plan", "rf_debug_jbf_ragged_plan",
                  "rf_debug_jbf_ragged_slab_plan", "rf_debug_jbf_two_wg_plan",
-                 "rf_debug_jbf_two_wg_calls",
+                 "rf_debug_jbf_two_wg_calls", "rf_debug_jbf_tile_flags",
                  "rf_debug_colorize_ragged_plan",
                  "rf_debug_gf_ragged_plan", "rf_debug_png_plan")
 # switches that leave work out (wrong results, timing experiments only); all others keep the bytes
@@ -174,6 +174,8 @@ def load_library():
         lib.rf_debug_jbf_two_wg_plan.restype = ci
         lib.rf_debug_jbf_two_wg_calls.argtypes = []
         lib.rf_debug_jbf_two_wg_calls.restype = ci
+        lib.rf_debug_jbf_tile_flags.argtypes = [vp, vp, ci]
+        lib.rf_debug_jbf_tile_flags.restype = ci
         lib.rf_debug_colorize_ragged_plan.argtypes = [ci, vp, vp, vp, ci]
         lib.rf_debug_colorize_ragged_plan.restype = ci
         lib.rf_debug_gf_ragged_plan.argtypes = [ci, vp, vp, ci, ci, ci, ci, vp, ci]
@@ -316,6 +318,21 @@ def jbf_two_wg_plan(n, h, w, joint_cn, src_cn, d, sigma_color, sigma_space, flag
     if rc < 0:
         check(rc, "rf_debug_jbf_two_wg_plan")
     return tuple(int(v) for v in out[1:]) if rc == 1 else None
+
+
+def jbf_tile_flags(stream, tiles):
+    """The first `tiles` tile bytes of the two-per-CU route as the last rf_jbf_u8 call on `stream` (a
+    pointer, as current_stream_ptr gives it) left them (rf_debug_jbf_tile_flags: synchronises the
+    stream): a uint8 array, bit 0 = the tile's src is not grey, bit 1 = its joint is."""
+    import numpy as np
+    lib = load_library()
+    out = np.zeros(int(tiles), dtype=np.uint8)
+    rc = lib.rf_debug_jbf_tile_flags(stream, out.ctypes.data, int(tiles))
+    if rc < 0:
+        check(rc, "rf_debug_jbf_tile_flags")
+    if rc != int(tiles):
+        raise RFError("rf_debug_jbf_tile_flags: %d bytes where %d tiles were asked for" % (rc, tiles))
+    return out
 
 
 def colorize_ragged_plan(sizes):

@@ -47,7 +47,8 @@ extern "C" int rf_debug_option(const char *name, int value)
                                                       "jbf_lookahead1",    "gf_s1_legacy_strips",
                                                       "gf_exact_all_flagged", "gf_cw_chan_run",   "gf_exact",
                                                       "jbf_no_msad",       "colorize_chunk_px",
-                                                      "jbf_no_two_wg"};
+                                                      "jbf_no_two_wg",     "jbf_vote_scan",
+                                                      "jbf_no_dead_skip"};
     static_assert(sizeof(names) / sizeof(names[0]) == rf::kDbgCount, "one name per DebugOption");
     if (name)
         for (int i = 0; i < rf::kDbgCount; i++)

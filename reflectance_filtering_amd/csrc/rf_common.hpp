@@ -110,6 +110,8 @@ enum DebugOption {
     kDbgJbfNoMsad,         // joint bilateral: every wave takes the tap loop with the mask (none the masked-SAD form)
     kDbgColorizeChunkPx,   // ragged colourise: pixels per workgroup chunk (a multiple of 256; 0 = the plan rule)
     kDbgJbfNoTwoWg,        // joint bilateral: grey tiles at one workgroup per CU (jbf_tile64_kernel), as before the two-per-CU route
+    kDbgJbfVoteScan,       // joint bilateral, two-per-CU route: the tile bytes from a scan of every tile's region (the launch before the grey map)
+    kDbgJbfNoDeadSkip,     // joint bilateral, two-per-CU route: waves wholly below the image walk the tap loop all the same
     kDbgCount
 };
 int debug_get(int id);

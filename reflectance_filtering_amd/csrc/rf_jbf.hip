@@ -54,6 +54,7 @@ constexpr int kJbfStageOnly = 0x1000, kJbfCompilerLoop = 0x2000, kJbfTile64Only 
 constexpr int kJbfLookahead1 = 0x8000;  // grey asm loop with its gathers one column step ahead (round-4 form)
 constexpr int kJbfNoMsad = 0x10000;     // every wave takes the tap loop with the mask (none the masked-SAD form)
 constexpr int kJbfVoteOnly = 0x20000;   // jbf_tile64x2_kernel: write the tiles' vote bytes and leave (set by its launcher only)
+constexpr int kJbfNoDeadSkip = 0x40000; // jbf_tile64x2_kernel: waves wholly below the image walk the tap loop all the same
 
 // the test / benchmark switches (rf_debug_option) as they travel to the kernels: private flag bits
 int jbf_debug_flags()
@@ -62,7 +63,8 @@ int jbf_debug_flags()
            (debug_get(kDbgJbfCompilerLoop) ? kJbfCompilerLoop : 0) |
            (debug_get(kDbgJbfTile64Only) ? kJbfTile64Only : 0) |
            (debug_get(kDbgJbfLookahead1) ? kJbfLookahead1 : 0) |
-           (debug_get(kDbgJbfNoMsad) ? kJbfNoMsad : 0);
+           (debug_get(kDbgJbfNoMsad) ? kJbfNoMsad : 0) |
+           (debug_get(kDbgJbfNoDeadSkip) ? kJbfNoDeadSkip : 0);
 }
 
 // Four consecutive pixels (cn interleaved bytes each, any alignment) -> four packed dwords.
@@ -1343,14 +1345,15 @@ int launch_slab_ragged(const JbfTables &t, int nz, const SlabShape &s, const uin
 // holds the grey loop only.  The LUT sits at the end of the allocation (reads beyond it return 0:
 // lds_oob_probe_half_kernel), the rows in front of it hold 64 output rows plus a slab of the disk's tap
 // rows, walked as in jbf_slab_kernel: same loop (SLAB), accumulators in registers from slab to slab,
-// every pixel's taps in row-major order - the bytes of jbf_tile64_kernel.  The vote over the tile's
-// texels (a scan of tile and halo, the region jbf_tile64_kernel votes on) is a launch of this kernel of
-// its own (kJbfVoteOnly) that writes one byte per tile into tile_flags - every byte, so no memset - and
-// comes first; a grey joint is then staged in the J1 form at once.  A tile whose src is not grey is
+// every pixel's taps in row-major order - the bytes of jbf_tile64_kernel.  What jbf_tile64_kernel votes on
+// (are the texels of tile and halo grey?) is one byte per tile in tile_flags here, written first: by the
+// grey map (jbf_grey_map_kernel, rf_jbf_greymap.hip: one pass over the images, in front of it the launch that
+// clears the bytes), or under "jbf_vote_scan" by a launch of this kernel of its own (kJbfVoteOnly) in which every tile
+// scans its region; a grey joint is then staged in the J1 form at once.  A tile whose src is not grey is
 // not filtered here: a launch of jbf_tile64_kernel<.., kFlagged> over the same grid filters exactly
-// those tiles, and the filtering launch of this kernel leaves them after one scalar load.  Three
-// launches then - vote, flagged colour tiles, grey tiles, in this order: for a grey batch the last one
-// does the work.  Single-channel buffers need no vote (one launch).
+// those tiles, and the filtering launch of this kernel leaves them after one scalar load.  The launches
+// then - clear, grey map, flagged colour tiles (3-channel src only), grey tiles, in this order: for a grey
+// batch the last one does the work.  Single-channel buffers need no bytes (one launch).
 // ------------------------------------------------------------------------------------------
 // rows of the tile in front of the LUT, and the tap rows of a slab (0: no room)
 int tile64x2_slab_rows(int nz, int grep, int tlw)
@@ -1445,6 +1448,12 @@ __global__ __launch_bounds__(1024, 8) void jbf_tile64x2_kernel(
     }
     // per wave, for all its slabs: the masked-SAD form of the loop unless a centre has a zero channel
     const bool msad = !j1 && !(flags & kJbfNoMsad) && jbf_wave_takes_msad(jc);
+    // a wave whose four tile rows all lie below the image (at 1080 rows two of sixteen in the last row of
+    // tiles) has nothing to store: it stages and meets every barrier, and walks no taps.  (Per wave and by rows
+    // only: a tile that overhangs the image's right edge - any width that is no multiple of 64 - has dead
+    // lanes in every wave, never a dead wave.)
+    const bool live_wave =
+        __builtin_amdgcn_readfirstlane(tile_y0 + (ty & ~3)) < h || (flags & kJbfNoDeadSkip) != 0;
     for (int i0 = -radius; i0 <= radius; i0 += slab_rows) {
         const int i1 = min(i0 + slab_rows - 1, radius);
         const int tlh = 64 + (i1 - i0);
@@ -1461,6 +1470,8 @@ __global__ __launch_bounds__(1024, 8) void jbf_tile64x2_kernel(
             }
         }
         __syncthreads();
+        if (!live_wave)
+            continue;
         if (j1)
             jbf_tap_loop_grey4_la2<GREP, TLW, true, true>(lut_lane_addr, swsym, tile_lane_addr, jc, ty,
                                                           radius, r4, sw_len, hwtab, sum1, wsum, i0, i1, -i0);
@@ -1589,7 +1600,7 @@ int launch_tile64_flagged(const JbfTables &t, int nz, int crows, const uint8_t *
     return RF_OK;
 }
 
-// A call on the two-per-CU route: the vote (3-channel src or joint), the flagged tiles of a 3-channel src
+// A call on the two-per-CU route: the tile bytes (3-channel src or joint), the flagged tiles of a 3-channel src
 // in jbf_tile64_kernel, the grey tiles in jbf_tile64x2_kernel, the strips as ever.  *done = false (nothing
 // launched): no main area, or no flag buffer may be made now - the caller takes the one-per-CU path.
 int launch_two_wg(const JbfTables &t, int nz, const Tile64Shape &shape, int slab_rows,
@@ -1603,8 +1614,9 @@ int launch_two_wg(const JbfTables &t, int nz, const Tile64Shape &shape, int slab
     const long long blocks = (long long)ceil_div(a.cols_main, 64) * ceil_div(a.rows_main, 64) * n;
     if (blocks > 0x7fffffffLL)
         return fail(RF_E_UNSUPPORTED, "rf_jbf_u8: batch too large for one launch");
-    // launch order: the vote, the flagged colour tiles, the grey tiles - the launch that does a grey batch's
-    // work comes last (a profile that takes a call's last launch for the call reads the metric kernel)
+    // launch order: the tile bytes (cleared, then the grey map's pass over the images), the flagged colour
+    // tiles, the grey tiles - the launch that does a grey batch's work comes last (a profile that takes a
+    // call's last launch for the call reads the metric kernel)
     uint8_t *tile_flags = nullptr;
     int rc = RF_OK;
     if (scn == 3 || jcn == 3) {
@@ -1612,8 +1624,14 @@ int launch_two_wg(const JbfTables &t, int nz, const Tile64Shape &shape, int slab
             return bad;
         if (!tile_flags)
             return RF_OK;
-        rc = launch_tile64x2(t, nz, slab_rows, joint, src, dst, n, h, w, jcn, scn, border, flags | kJbfVoteOnly,
-                             stream, a.rows_main, a.cols_main, tile_flags);
+        const int tiles_x = ceil_div(a.cols_main, 64), tiles_y = ceil_div(a.rows_main, 64);
+        // "jbf_vote_scan", a WRAP border or a region the map's blocks do not reach: every tile scans its region
+        if (debug_get(kDbgJbfVoteScan) || !jbf_grey_map_serves(h, w, t.radius, border, tiles_x, tiles_y))
+            rc = launch_tile64x2(t, nz, slab_rows, joint, src, dst, n, h, w, jcn, scn, border,
+                                 flags | kJbfVoteOnly, stream, a.rows_main, a.cols_main, tile_flags);
+        else
+            rc = jbf_launch_grey_map(joint, src, n, h, w, jcn, scn, t.radius, border, stream, tiles_x, tiles_y,
+                                     tile_flags);
     }
     if (rc == RF_OK && scn == 3)
         rc = shape.crep == 32 ? launch_tile64_flagged<32>(t, nz, shape.crows, joint, src, dst, n, h, w, jcn,
@@ -1661,6 +1679,34 @@ void jbf_scratch_release()
 extern "C" int rf_debug_jbf_two_wg_calls(void)
 {
     return rf::g_two_wg_calls.load(std::memory_order_relaxed) & 0x7fffffff;
+}
+
+extern "C" int rf_debug_jbf_tile_flags(void *stream_, unsigned char *out, int cap)
+{
+    using namespace rf;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (cap < 0 || (!out && cap))
+        return fail(RF_E_BADARG, "rf_debug_jbf_tile_flags: NULL out or a negative cap");
+    if (stream_is_capturing(stream))
+        return fail(RF_E_UNSUPPORTED, "rf_debug_jbf_tile_flags: synchronises its stream and cannot be "
+                                      "captured into a graph");
+    int dev = 0;
+    RF_HIP_CHECK(hipGetDevice(&dev));
+    const uint8_t *p = nullptr;
+    size_t bytes = 0;
+    {
+        std::lock_guard<std::mutex> lock(g_tf_mu);
+        for (const TileFlagBuf &b : g_tf)
+            if (b.dev == dev && b.stream == stream)
+                p = b.p, bytes = b.bytes;
+    }
+    if (bytes > (size_t)cap)
+        bytes = (size_t)cap;
+    if (bytes) {
+        RF_HIP_CHECK(hipMemcpyAsync(out, p, bytes, hipMemcpyDeviceToHost, stream));
+        RF_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    return (int)bytes;
 }
 
 extern "C" int rf_jbf_release_scratch(void)

@@ -48,6 +48,14 @@ inline int jbf_check_format(const char *who, int joint_cn, int src_cn, int borde
     return RF_OK;
 }
 
+// The grey map of rf_jbf_u8's two-workgroups-per-CU route (rf_jbf_greymap.hip): the route's byte per 64x64
+// tile from one pass over the images.  jbf_grey_map_serves: may a call take it (else every tile scans its
+// region); jbf_launch_grey_map: the launch that sets the bytes to "grey" and the pass, on `stream`.
+bool jbf_grey_map_serves(int h, int w, int radius, int border, int tiles_x, int tiles_y);
+int jbf_launch_grey_map(const uint8_t *joint, const uint8_t *src, int n, int h, int w, int jcn, int scn,
+                        int radius, int border, hipStream_t stream, int tiles_x, int tiles_y,
+                        uint8_t *tile_flags);
+
 // Colour weights exp(i^2 * -0.5 / sigma_color^2) rounded to float, i = 0 .. 256*joint_cn - 1,
 // computed in double with libm's exp like jointBilateralFilter_8u.  Returns the number of entries
 // up to and including the first exact zero (the table is non-increasing: every later entry is 0).
