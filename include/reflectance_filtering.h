@@ -26,6 +26,22 @@
  *     query's answer is always enough), and no result depends on the bytes around an input;
  *   - a call leaves its inputs alone, except where an entry says otherwise (dst == src of the guided
  *     filter, `raw` of rf_png_unfilter_ragged_u8).
+ *
+ * Streams (held for every entry by tests/test_gpu_stream_contract.py, on a non-blocking side stream kept
+ * busy in front of the call, with inputs that arrive on that stream just before it and are overwritten
+ * on it right after it):
+ *   - everything a call enqueues - helper launches, staging copies, work on a side stream of the
+ *     library - is ordered after what `stream` holds at the call and before what is enqueued on it
+ *     afterwards; a parameter table that is uploaded on a stream of the library is resident before the
+ *     call launches anything that reads it;
+ *   - a call whose parameter tables are cached returns without waiting for the device, however much
+ *     work is queued in front of it, unless its entry says "SYNCHRONISES THE STREAM"; such an entry waits
+ *     once, for its own stream alone - never for the work of another non-blocking stream (rf_jbf_f32
+ *     uploads its tables with two blocking copies on the null stream after its wait: like every use of
+ *     the null stream they are ordered against streams created WITHOUT hipStreamNonBlocking);
+ *   - what the library keeps per caller stream (side streams of the guided filter, vote bytes of
+ *     rf_jbf_u8, packed-weight slots of the CNN: 16 each) may be used from more streams than are kept:
+ *     a further stream is served by a recycled idle entry or by a route that needs none.
  */
 #ifndef REFLECTANCE_FILTERING_H
 #define REFLECTANCE_FILTERING_H
@@ -109,8 +125,11 @@ int rf_jbf_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst, int n, int
  * are rf_jbf_u8's; n == 0 is RF_OK whatever the pointers are.
  * Radius <= 52 (the paper's c20 s22 and c15 s28 among them): the tiles of all images run in one
  * launch per tile shape - at most four - from one record per tile (first pixel, height, width, tile
- * origin), staged in the workspace by one copy.  For that copy the call SYNCHRONISES THE STREAM once.
- * Every other route of rf_jbf_u8 (radius 53 and up, RF_JBF_FORCE_GENERIC, a device whose LDS probe
+ * origin), staged in the workspace by one copy.  Radius 53..468: the tiles of all images run in ONE
+ * launch of tap-row slabs, from the same records staged the same way.  For that copy the call
+ * SYNCHRONISES THE STREAM once, on both routes (its own stream only: it waits for no other stream's
+ * work).
+ * Every other route of rf_jbf_u8 (radius 469 and up, RF_JBF_FORCE_GENERIC, a device whose LDS probe
  * fails, the "jbf_tune" debug switch) is taken by calling rf_jbf_u8 once per image: the same bytes
  * with n launches and no synchronisation.  Either way the call is refused (RF_E_UNSUPPORTED) on a
  * stream that is being captured into a graph.
@@ -347,8 +366,9 @@ int rf_colorize_ragged_srgb_u8(const uint8_t *bgr, const float *r, uint8_t *refl
  *                the shading is +inf, a black pixel gives NaN, and a result holding a NaN is written
  *                without normalisation.
  * Every other argument, the workspace (rf_colorize_ragged_workspace_bytes), the refusals - all
- * decided before any device work -, the one synchronisation of `stream`, the refusal on a capturing
- * stream and n == 0 are those of rf_colorize_ragged_srgb_u8.  The bytes written are, for every input,
+ * decided before any device work -, the refusal on a capturing stream and n == 0 are those of
+ * rf_colorize_ragged_srgb_u8, and like it the call SYNCHRONISES THE STREAM once (for the copy of the
+ * image table).  The bytes written are, for every input,
  * those of rf_colorize_ragged_srgb_u8 given the float32 array (float)r8[i] / 255.0f.
  */
 int rf_colorize_ragged_r8_srgb_u8(const uint8_t *bgr, const uint8_t *r8, uint8_t *refl_out,

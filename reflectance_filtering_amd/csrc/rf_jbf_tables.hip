@@ -80,8 +80,9 @@ struct JbfTableOwner {
 std::mutex g_mu;
 std::vector<JbfTables> g_tables;
 // Owners that left the cache (evicted entries, entries a finishing call held the last reference
-// to): their arrays are freed by the next call whose stream is NOT capturing - hipFree inside a
-// capture invalidates it - or by rf_shutdown.
+// to): their arrays are freed by the next call that builds a set of tables on a stream that is NOT
+// capturing - hipFree inside a capture invalidates it, and it waits for the whole device, which a call
+// that finds its tables cached must not do - or by rf_shutdown.
 std::vector<std::shared_ptr<void>> g_retired;
 
 void drain_retired(hipStream_t stream)
@@ -138,7 +139,6 @@ int get_tables(int radius, int joint_cn, double sigma_color, double sigma_space,
 {
     int dev = 0;
     RF_HIP_CHECK(hipGetDevice(&dev));
-    drain_retired(stream);
     {
         std::lock_guard<std::mutex> lock(g_mu);
         for (const JbfTables &t : g_tables)
@@ -152,6 +152,11 @@ int get_tables(int radius, int joint_cn, double sigma_color, double sigma_space,
         note_use_on(*out, stream);
         return RF_OK;
     }
+    // Tables that left the cache are freed here, where a new set is built and the host waits anyway:
+    // hipFree waits for the whole device, and a call that finds its tables cached must not (the header's
+    // stream rules; tests/test_gpu_stream_contract.py).  A build evicts at most one entry, so the bin
+    // stays small.
+    drain_retired(stream);
     std::vector<float> lut;
     JbfTables t = jbf_host_tables(radius, joint_cn, sigma_color, sigma_space, lut);
     t.device = dev;
