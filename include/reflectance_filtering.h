@@ -42,6 +42,34 @@
  *   - what the library keeps per caller stream (side streams of the guided filter, vote bytes of
  *     rf_jbf_u8, packed-weight slots of the CNN: 16 each) may be used from more streams than are kept:
  *     a further stream is served by a recycled idle entry or by a route that needs none.
+ *
+ * Sizes (held by tests/test_gpu_size_contract.py, whose buffers pass 2^31 and 2^32 bytes, and by
+ * tests/test_launch_limits_abi.py.  Within 32 GiB per call, one-channel 8-bit buffers pass pixel index 2^32
+ * too - those of the colourise entries 2^31, those of rf_gf_ragged_u8 2^30 - and float buffers element
+ * index 2^31, those of the CNN entries 2^32):
+ *   - n, h, w and the counts are ints; every offset into a caller's buffer is formed in 64 bits, so a
+ *     buffer may be as large as the device holds, up to these caps: 2^60 pixels in a list of
+ *     rf_jbf_ragged_u8 or rf_jbf_points_ragged_u8, 2^58 in one of rf_gf_ragged_u8, 2^46 in one of the
+ *     ragged colourise entries (and 3 h w < 2^32 per image); w < 2^27 for the guided filter; raw stream and
+ *     pixels below 2^31 per image of rf_png_unfilter_ragged_u8, a stream bound below 2^31 for
+ *     rf_png_deflate_ragged_u8;
+ *   - a call whose work does not fit one launch is refused with RF_E_UNSUPPORTED ("... for one launch";
+ *     the ragged colourise entries and the unpack grid of rf_png_unfilter_ragged_u8 say "... than one
+ *     grid takes")
+ *     before any device work (rf_jbf_u8 alone may have uploaded the parameter tables of its sigmas by
+ *     then; it launches nothing): the runtime takes no launch of 2^32 work-items or more.  That is 4,194,303
+ *     tiles of 64 x 64 for rf_jbf_u8 and rf_jbf_ragged_u8 (17 gigapixels of whole tiles; for a ragged
+ *     list every image counts ceil(h / 64) ceil(w / 64) tiles, so 4,194,303 images at most);
+ *     16,777,215 stage-1 strips, 64-row blocks or column blocks for rf_gf_ragged_u8; 16,777,215
+ *     workgroups and 8,388,607 images for the ragged colourise entries; 67,108,860 waves for the point
+ *     entries (a wave takes 64 / n_params points of one group of sigma_space, at most); 67,108,863 for n
+ *     of rf_whdr_f32 and n * n_sets of rf_whdr_points_u8; 4,194,303 images and 16,777,215 blocks of 4096
+ *     pixels for rf_png_unfilter_ragged_u8; n <= 65535 for rf_colorize_srgb_u8, rf_jbf_f32 and the
+ *     untiled route of rf_jbf_u8 (RF_JBF_FORCE_GENERIC, radius above 468).  The CNN entries run a
+ *     grid of fixed size.  rf_gf_u8, rf_gf_ex_u8 and rf_gf_f32 split a batch themselves: they work in
+ *     chunks of at most 16383 (8-bit kernels) or 65535 images (float kernels), and of no more images
+ *     than their launches take, however large the workspace is; they refuse only an image that is
+ *     itself too large for a launch (16,777,215 / src_cn blocks of 64 rows, for instance).
  */
 #ifndef REFLECTANCE_FILTERING_H
 #define REFLECTANCE_FILTERING_H

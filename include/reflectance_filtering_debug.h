@@ -208,6 +208,13 @@ int rf_debug_colorize_ragged_plan(int n, const int *heights, const int *widths, 
 int rf_debug_gf_ragged_plan(int n, const int *heights, const int *widths, int guide_cn, int src_cn,
                             int radius, int flags, int *out, int cap);
 
+/* The images rf_gf_u8, rf_gf_ex_u8 (float_kernels = 0: radius <= 128; 1: beyond) and rf_gf_f32
+ * (float_kernels = 1) run at once where the workspace has room for `chunk` images of h x w: at most 16383
+ * (float kernels: 65535), and no more than the launches that fold the chunk into gridDim.x take (fewer
+ * than 2^32 work-items each).  0: one such image is too large for a launch, and the entries refuse it
+ * (RF_E_UNSUPPORTED).  Decided by the function the entries take their chunk from.  Host only. */
+int rf_debug_gf_launch_chunk(int chunk, int h, int w, int src_cn, int float_kernels);
+
 /* The plan of rf_png_deflate_ragged_u8 for images of these sizes: the ints {chunk length in raw
  * bytes (one library-wide constant), chunks of all images} followed by each image's number of chunks
  * (ceil(h * (1 + w * c_out) / chunk length)), as many of these 2 + n ints as `cap` holds, at out.

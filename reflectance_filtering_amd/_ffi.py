@@ -49,7 +49,7 @@ DEBUG_EXPORTS = ("rf_debug_option", "rf_debug_clock_probe", "rf_debug_build_info
                  "rf_debug_jbf_ragged_slab_plan", "rf_debug_jbf_two_wg_plan",
                  "rf_debug_jbf_two_wg_calls", "rf_debug_jbf_tile_flags",
                  "rf_debug_colorize_ragged_plan",
-                 "rf_debug_gf_ragged_plan", "rf_debug_png_plan")
+                 "rf_debug_gf_ragged_plan", "rf_debug_gf_launch_chunk", "rf_debug_png_plan")
 # switches that leave work out (wrong results, timing experiments only); all others keep the bytes
 RESULT_CHANGING_OPTIONS = ("jbf_stage_only", "gf_exp_skip")
 
@@ -180,6 +180,8 @@ def load_library():
         lib.rf_debug_colorize_ragged_plan.restype = ci
         lib.rf_debug_gf_ragged_plan.argtypes = [ci, vp, vp, ci, ci, ci, ci, vp, ci]
         lib.rf_debug_gf_ragged_plan.restype = ci
+        lib.rf_debug_gf_launch_chunk.argtypes = [ci, ci, ci, ci, ci]
+        lib.rf_debug_gf_launch_chunk.restype = ci
         # RF_DEBUG_OPTIONS="name=value,...": preset the test / benchmark switches of
         # include/reflectance_filtering_debug.h for a whole process (timing experiments only).
         # Every preset is announced on stderr - loudly for the switches that change results.

@@ -62,6 +62,16 @@ __device__ inline uint8_t saturate_u8(float v)
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// The runtime's launch rule (hip_runtime_api.h at hipModuleLaunchKernel): no launch whose gridDim x
+// blockDim reaches 2^32 work-items in a dimension.  Does a grid of `workgroups` in x, `threads` each,
+// fit one launch?  (gridDim.x itself stays below 2^31.)
+inline bool launch_fits(unsigned long long workgroups, unsigned threads)
+{
+    return workgroups <= 0x7fffffffull && workgroups * threads < (1ull << 32);
+}
+// ... and the largest gridDim.y or gridDim.z (an image index, where a launch puts n there)
+constexpr int kMaxGridYZ = 65535;
+
 // Do the byte ranges [a, a + na) and [b, b + nb) intersect?
 inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
 {

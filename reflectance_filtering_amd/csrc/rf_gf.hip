@@ -1050,6 +1050,40 @@ __global__ __launch_bounds__(256) void gff_algebra_kernel(float *__restrict__ P,
         base[(size_t)e * npx] = ab[e];
 }
 
+// The launch rule for a chunk of the uniform guided filter: the row and column walks fold the chunk's
+// images into gridDim.x.  Does a chunk of m images of h x w fit every such launch (launch_fits)?
+//   8-bit kernels: gf_rowstate_kernel m * src_cn * ceil(h / 64) workgroups of 256, gf_rowsum_kernel<4>
+//   (two-kernel stage 2) four times as many of 64, gf_colwalk_kernel at most 8 * (ceil(m * nb / 8) + run) *
+//   src_cn of 128 (its items per XCD rounded up to whole channel runs of 64, or of what the debug option
+//   "gf_cw_chan_run" says), and under the debug option "gf_chained" the chained walk's 8 * ceil(m / 8) * src_cn *
+//   nb of 128;
+//   float kernels: gf_rowsum_kernel<1> m * (9 + 4 * src_cn) * ceil(h / 64) workgroups of 64.
+bool gf_chunk_fits(int m, int h, int w, int src_cn, bool float_kernels)
+{
+    const unsigned long long mm = (unsigned long long)m, rb = (unsigned long long)ceil_div(h, kBRows);
+    if (float_kernels)
+        return launch_fits(mm * (9 + 4 * src_cn) * rb, 64);
+    const unsigned long long nb = (unsigned long long)ceil_div(w, kSB);
+    const unsigned long long run = (unsigned long long)std::max(64, debug_get(kDbgGfCwChanRun));
+    return launch_fits(mm * src_cn * rb, 256) && launch_fits(mm * 4 * src_cn * rb, 64) &&
+           launch_fits(8 * ((mm * nb + 7) / 8 + run) * src_cn, 128) &&
+           (!debug_get(kDbgGfChained) || launch_fits(8 * ((mm + 7) / 8) * src_cn * nb, 128));
+}
+
+// The largest chunk of at most `chunk` images that fits (0: not even one image does).
+int gf_launch_chunk(int chunk, int h, int w, int src_cn, bool float_kernels)
+{
+    int lo = 0, hi = chunk;  // lo fits (or is 0), everything above hi does not
+    while (lo < hi) {
+        const int mid = lo + (hi - lo + 1) / 2;
+        if (gf_chunk_fits(mid, h, w, src_cn, float_kernels))
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
 template <int SCN>
 int gf_f32_chunk(const float *guide, const float *src, float *dst, int m, int h, int w, int radius,
                  float eps_f, int eps_small, int iterations, float *P, double *rows,
@@ -1475,6 +1509,10 @@ int gf_u8_entry(const char *fn, const uint8_t *guide, const uint8_t *src, uint8_
         // (kGfF32Slack: the float kernels' scratch starts with double row sums, so the float copies
         //  in front of it are rounded up to 16 bytes - an odd pixel count would leave it 4-aligned)
         int chunk = (int)std::min<size_t>((size_t)n, (workspace_bytes - header - kGfF32Slack) / per_img_f);
+        // gf_f32_chunk puts the image index in gridDim.y / .z and folds the chunk into gridDim.x
+        chunk = gf_launch_chunk(std::min(chunk, kMaxGridYZ), h, w, src_cn, true);
+        if (chunk == 0)
+            return fail(RF_E_UNSUPPORTED, "%s: an image of %d x %d is too large for one launch", fn, w, h);
         char *ws0 = static_cast<char *>(workspace) + header;
         for (int i0 = 0; i0 < n; i0 += chunk) {
             const int m = std::min(chunk, n - i0);
@@ -1574,8 +1612,11 @@ int gf_u8_entry(const char *fn, const uint8_t *guide, const uint8_t *src, uint8_
     const size_t per_img_used = (fused ? per_img_fused : per_img) + (keep_gs ? gs_bytes : 0) +
                                 cmp_bytes + cmp3_bytes + (exact ? exact_bytes : 0);
     int chunk = (int)std::min<size_t>((size_t)n, (workspace_bytes - header) / per_img_used);
-    if (chunk > 16383)
-        chunk = 16383;
+    // at most 16383 images (gridDim.y holds image x channel), and no more than the row and column walks'
+    // launches take, which fold the chunk into gridDim.x
+    chunk = gf_launch_chunk(std::min(chunk, 16383), h, w, src_cn, false);
+    if (chunk == 0)
+        return fail(RF_E_UNSUPPORTED, "%s: an image of %d x %d is too large for one launch", fn, w, h);
     // chained column walk: a part's images are dealt to 8 ticket queues (one per XCD), so parts of
     // a multiple of 8 images - chunks of a multiple of 16 - load the queues evenly
     if (chained && chunk >= 16 && n > chunk)
@@ -2072,7 +2113,9 @@ int gf_ragged_plan(const char *who, int n, const int *heights, const int *widths
         st0 += (size_t)4 * I.nb * h;
         blocks += (size_t)I.nb;
     }
-    if (plan->s1.size() > 0x7fffffffu || plan->rs.size() > 0x7fffffffu || blocks + 8 > 0x7fffffffu)
+    // stage 1 and the row states: 256 threads per item; the column walk: 128 per block, rounded up to 8 runs
+    if (!launch_fits(plan->s1.size(), stage1_threads(1)) || !launch_fits(plan->rs.size(), 256) ||
+        !launch_fits(blocks + 8, 128))
         return fail(RF_E_UNSUPPORTED, "%s: too many work items for one launch", who);
     // column walk: each XCD (workgroup id mod 8) takes a contiguous run of ceil(blocks / 8) items in
     // list order - balanced by count, not by walk length
@@ -2096,6 +2139,15 @@ extern "C" size_t rf_gf_ragged_workspace_bytes(int n, const int *heights, const 
         gf_ragged_plan(who, n, heights, widths, guide_cn, src_cn, radius, flags, &plan) != RF_OK)
         return 0;
     return plan.bytes;
+}
+
+extern "C" int rf_debug_gf_launch_chunk(int chunk, int h, int w, int src_cn, int float_kernels)
+{
+    if (chunk < 0 || h <= 0 || w <= 0 || (src_cn != 1 && src_cn != 3))
+        return rf::fail(RF_E_BADARG, "rf_debug_gf_launch_chunk: bad chunk=%d h=%d w=%d src_cn=%d", chunk, h, w,
+                        src_cn);
+    return rf::gf_launch_chunk(std::min(chunk, float_kernels ? rf::kMaxGridYZ : 16383), h, w, src_cn,
+                               float_kernels != 0);
 }
 
 extern "C" int rf_debug_gf_ragged_plan(int n, const int *heights, const int *widths, int guide_cn,
@@ -2271,8 +2323,10 @@ extern "C" int rf_gf_f32(const float *guide, const float *src, float *dst, int n
                     workspace_bytes, per_img);
     hipStream_t stream = (hipStream_t)stream_;
     int chunk = (int)std::min<size_t>((size_t)n, workspace_bytes / per_img);
-    if (chunk > 65535)
-        chunk = 65535;
+    // gf_f32_chunk puts the image index in gridDim.y / .z and folds the chunk into gridDim.x
+    chunk = gf_launch_chunk(std::min(chunk, kMaxGridYZ), h, w, src_cn, true);
+    if (chunk == 0)
+        return fail(RF_E_UNSUPPORTED, "rf_gf_f32: an image of %d x %d is too large for one launch", w, h);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         double *rows = reinterpret_cast<double *>(workspace);

@@ -766,7 +766,7 @@ int launch_tiled2(const JbfTables &t, bool full_lut, const uint8_t *joint, const
     const size_t lds = tiled2_lds_bytes(t, TH, LUTREP, full_lut);
     const int tiles_x = ceil_div(w, kTileW), tiles_y = ceil_div(h, TH);
     const long long blocks = (long long)tiles_x * tiles_y * n;
-    if (blocks > 0x7fffffffLL)
+    if (!launch_fits(blocks, 16 * TH))
         return fail(RF_E_UNSUPPORTED, "rf_jbf_u8: batch too large for one launch");
     auto kern = clamp ? jbf_tiled2_kernel<SCN, TH, LUTREP, true>
                       : jbf_tiled2_kernel<SCN, TH, LUTREP, false>;
@@ -870,7 +870,7 @@ int launch_tile64(const JbfTables &t, int nz, int crows, const uint8_t *joint, c
         cols = w;
     const int tiles_x = ceil_div(cols, 4 * (1024 / TH)), tiles_y = ceil_div(rows, TH);
     const long long blocks = (long long)tiles_x * tiles_y * n;
-    if (blocks > 0x7fffffffLL)
+    if (!launch_fits(blocks, 1024))
         return fail(RF_E_UNSUPPORTED, "rf_jbf_u8: batch too large for one launch");
     auto kern = jbf_tile64_kernel<SCN, GREP, CREP, TLW, TH>;
     RF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1047,7 +1047,7 @@ int launch_tile64_ragged(const JbfTables &t, int nz, int crows, const uint8_t *j
 {
     if (ntiles == 0)
         return RF_OK;
-    if (ntiles > (size_t)0x7fffffff)
+    if (!launch_fits(ntiles, 1024))
         return fail(RF_E_UNSUPPORTED, "rf_jbf_ragged_u8: too many tiles for one launch");
     auto kern = jbf_tile64_kernel<SCN, GREP, CREP, TLW, TH, true>;
     RF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1307,7 +1307,7 @@ int launch_slab(const JbfTables &t, int nz, int crows, int slab_rows, int crows_
 {
     const int tiles_x = ceil_div(w, 64), tiles_y = ceil_div(h, 64);
     const long long blocks = (long long)tiles_x * tiles_y * n;
-    if (blocks > 0x7fffffffLL)
+    if (!launch_fits(blocks, 1024))
         return fail(RF_E_UNSUPPORTED, "rf_jbf_u8: batch too large for one launch");
     auto kern = jbf_slab_kernel<GREP, TLW>;
     RF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1326,7 +1326,7 @@ int launch_slab_ragged(const JbfTables &t, int nz, const SlabShape &s, const uin
 {
     if (ntiles == 0)
         return RF_OK;
-    if (ntiles > (size_t)0x7fffffff)
+    if (!launch_fits(ntiles, 1024))
         return fail(RF_E_UNSUPPORTED, "rf_jbf_ragged_u8: too many tiles for one launch");
     auto kern = jbf_slab_kernel<GREP, TLW, true>;
     RF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1612,7 +1612,7 @@ int launch_two_wg(const JbfTables &t, int nz, const Tile64Shape &shape, int slab
     if (a.rows_main <= 0 || a.cols_main <= 0)
         return RF_OK;
     const long long blocks = (long long)ceil_div(a.cols_main, 64) * ceil_div(a.rows_main, 64) * n;
-    if (blocks > 0x7fffffffLL)
+    if (!launch_fits(blocks, 1024))
         return fail(RF_E_UNSUPPORTED, "rf_jbf_u8: batch too large for one launch");
     // launch order: the tile bytes (cleared, then the grey map's pass over the images), the flagged colour
     // tiles, the grey tiles - the launch that does a grey batch's work comes last (a profile that takes a
@@ -1874,8 +1874,8 @@ namespace rf {
 namespace {
 
 // The checks of both ragged entries and of the plan query that need no device: sizes, channels,
-// flags, radius.  *px = pixels of all images, *tiles = their 64x64-tile count (no plan has more
-// tiles: a strip is only taken where it saves workgroups).
+// flags, radius, the launch rule (launch_fits).  *px = pixels of all images, *tiles = their 64x64-tile
+// count (no plan has more tiles: a strip is only taken where it saves workgroups).
 int ragged_check(const char *who, int n, const int *heights, const int *widths, int joint_cn,
                  int src_cn, int d, double sigma_space, int border, int flags, size_t *px,
                  size_t *tiles)
@@ -1901,6 +1901,10 @@ int ragged_check(const char *who, int n, const int *heights, const int *widths, 
     const int radius = jbf_radius(d, jbf_sigma(sigma_space));
     if (radius > kJbfMaxRadius)
         return fail(RF_E_UNSUPPORTED, "%s: radius %d too large", who, radius);
+    // every tile kernel runs 1024 threads per tile, and the tile records of all classes share one launch
+    // rule: refused here, before any table, copy or launch
+    if (!launch_fits(*tiles, 1024))
+        return fail(RF_E_UNSUPPORTED, "%s: too many tiles for one launch", who);
     return RF_OK;
 }
 
@@ -2011,7 +2015,7 @@ extern "C" int rf_debug_jbf_two_wg_plan(int n, int h, int w, int joint_cn, int s
         return 0;
     const Tile64Areas a = tile64_areas(t, nz, shape.grep, shape.crep, src_cn, flags, h, w);
     const long long blocks = (long long)ceil_div(a.cols_main, 64) * ceil_div(a.rows_main, 64) * n;
-    if (a.rows_main <= 0 || a.cols_main <= 0 || blocks > 0x7fffffffLL)
+    if (a.rows_main <= 0 || a.cols_main <= 0 || !launch_fits(blocks, 1024))
         return 0;
     out[0] = 1;
     out[1] = 64 + slab_rows - 1;

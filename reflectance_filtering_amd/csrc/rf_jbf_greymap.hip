@@ -232,7 +232,7 @@ int jbf_launch_grey_map(const uint8_t *joint, const uint8_t *src, int n, int h, 
 {
     const int blocks_x = ceil_div(w, 256), blocks_y = ceil_div(h, 64);
     const long long blocks = (long long)blocks_x * blocks_y * n;
-    if (blocks > 0x7fffffffLL)
+    if (!launch_fits(blocks, 256))
         return fail(RF_E_UNSUPPORTED, "rf_jbf_u8: batch too large for one launch");
     const int nwords = (int)(((long long)tiles_x * tiles_y * n + 3) / 4);  // (whole words: the buffer's size rule)
     uint32_t *words = reinterpret_cast<uint32_t *>(tile_flags);

@@ -147,8 +147,11 @@ int plan_points(const char *who, int n_params, const double *sigma_space, int d,
     return RF_OK;
 }
 
-// The launch addresses its waves with an int.
-bool plan_fits_one_launch(const PtsPlan &plan) { return plan.items <= 0x7fffffffLL - kPtsWaves; }
+// One launch of kPtsWaves waves per workgroup takes every item (a wave each).
+bool plan_fits_one_launch(const PtsPlan &plan)
+{
+    return launch_fits((unsigned long long)(plan.items + kPtsWaves - 1) / kPtsWaves, 64 * kPtsWaves);
+}
 
 // One image of a ragged call (rf_jbf_points_ragged_u8): where its pixels start in the packed
 // buffers, and its size.

@@ -340,6 +340,8 @@ int plan_decode(const char *who, int n, const int *heights, const int *widths, c
         return fail(RF_E_BADARG, "%s: bad size n=%d", who, n);
     if (n > 0 && (!heights || !widths || !formats))
         return fail(RF_E_BADARG, "%s: NULL pointer", who);
+    if (!launch_fits((unsigned long long)n, kUnfilterThreads))   // the unfilter kernel: a workgroup per image
+        return fail(RF_E_UNSUPPORTED, "%s: too many images for one launch", who);
     plan->images.resize((size_t)n);
     plan->pixels = plan->blocks = 0;
     for (int i = 0; i < n; i++) {
@@ -365,7 +367,7 @@ int plan_decode(const char *who, int n, const int *heights, const int *widths, c
         if (raw_offsets && ctype == 3 && !palettes)
             return fail(RF_E_BADARG, "%s: NULL pointer: image %d has a palette", who, i);
         const unsigned long long nblk = (px + kUnpackPx - 1) / kUnpackPx;
-        if (plan->blocks + nblk >= (1ull << 31))
+        if (!launch_fits(plan->blocks + nblk, kUnpackThreads))
             return fail(RF_E_UNSUPPORTED, "%s: more pixels than one grid takes", who);
         DecImage &im = plan->images[i];
         im.raw0 = raw_offsets ? raw_offsets[i] : 0;

@@ -137,6 +137,8 @@ extern "C" int rf_whdr_f32(const float *refl, int n, int c, int h, int w, const 
         return fail(RF_E_UNSUPPORTED, "rf_whdr_f32: 1 or 3 channels (got %d)", c);
     if (!(delta >= 0))
         return fail(RF_E_BADARG, "rf_whdr_f32: delta must be >= 0");
+    if (!launch_fits((unsigned long long)n, 64))
+        return fail(RF_E_UNSUPPORTED, "rf_whdr_f32: n too large for one launch");
     const float thresh = (float)(1.0 + delta);
     hipLaunchKernelGGL(whdr_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream_, refl, c, h, w,
                        points, weights, offsets, thresh, out);
@@ -157,7 +159,7 @@ extern "C" int rf_whdr_points_u8(const uint8_t *samples, int n_sets, long long s
     if (n < 0 || n_sets <= 0 || set_stride <= 0)
         return fail(RF_E_BADARG, "rf_whdr_points_u8: bad size n=%d n_sets=%d set_stride=%lld", n,
                     n_sets, set_stride);
-    if ((long long)n * n_sets > 0x7fffffffLL)
+    if (!launch_fits((unsigned long long)n * n_sets, 64))
         return fail(RF_E_UNSUPPORTED, "rf_whdr_points_u8: n * n_sets too large for one launch");
     if (c != 1 && c != 3)
         return fail(RF_E_UNSUPPORTED, "rf_whdr_points_u8: 1 or 3 channels (got %d)", c);

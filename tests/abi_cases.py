@@ -12,6 +12,12 @@ bytes).  Index-like inputs (INDEX_LIKE) have none: whatever a call reads of them
 Shapes: S1 = 2 x 67 x 131 (w % 4 = 3, h % 64 = 3: 64x64 tiles with right and bottom strips; an image
 is 26,331 or 8,777 bytes, both odd), S2 = 3 x 5 x 7 (smaller than every tile and window; 105 bytes),
 S3 = 1 x 1 x 1, MIXED the ragged entries' list.
+
+tests/size_cases.py runs the same cases over buffers that pass 2^31 and 2^32 bytes: for that a builder
+takes `first` (the images behind the usual ones: another period of the same kind), the ragged ones
+`sizes`, and a Case carries `sized(k)`: the same call over k periods, a period being the case's own
+images (n of them for a uniform entry, the whole list for a ragged one), with the workspace it needs.
+Buffers named in PER_CALL do not grow with the periods.
 """
 import zlib
 
@@ -23,6 +29,7 @@ from tests import synth
 S1, S2, S3 = (2, 67, 131), (3, 5, 7), (1, 1, 1)
 MIXED = ((67, 131), (5, 7), (5, 7), (67, 131), (5, 7))     # the ragged entries' list
 INDEX_LIKE = ("points", "offsets", "point_offsets", "comps", "comp_offsets")
+PER_CALL = ("weights", "lut", "steps", "packed", "ws")      # one per call, however many images it has
 
 
 class Buf(object):
@@ -48,11 +55,13 @@ class Case(object):
     arrays where only part of an output is specified); check(outs): the L0 outputs against the oracle;
     around: a context manager factory held during the call (debug switches); entries: the header's
     entries the call goes through; sync: their header text says the call synchronises its stream;
-    two_wg: the call takes rf_jbf_u8's two-workgroups-per-CU route (None: not such a call)."""
+    two_wg: the call takes rf_jbf_u8's two-workgroups-per-CU route (None: not such a call);
+    sized(k) -> (call, workspace bytes): the call over k periods of this case's images (module docstring)."""
 
     def __init__(self, bufs, call, outputs, check, around=None, after=None, entries=(), sync=False,
-                 two_wg=None):
+                 two_wg=None, sized=None):
         self.bufs, self.call, self.outputs, self.check = bufs, call, outputs, check
+        self.sized = sized
         self.around, self.after = around, after
         self.entries, self.sync, self.two_wg = tuple(entries), bool(sync), two_wg
 
@@ -85,19 +94,20 @@ def _inv(a):
 _cache = {}
 
 
-def _images(shape, kind):
-    """uint8 [n,h,w,c]: "colour" (3 channels), "grey3" (3 equal channels), "grey1", "joint1"."""
-    key = (shape, kind)
+def _images(shape, kind, first=0):
+    """uint8 [n,h,w,c]: "colour" (3 channels), "grey3" (3 equal channels), "grey1", "joint1"; image i
+    is number first + i of its kind."""
+    key = (shape, kind, first)
     if key not in _cache:
         n, h, w = shape
         if kind == "colour":
-            imgs = [synth.scene_u8(h, w, 900 + i) for i in range(n)]
+            imgs = [synth.scene_u8(h, w, 900 + first + i) for i in range(n)]
         elif kind == "grey3":
-            imgs = [synth.reflectance_like_u8(h, w, 910 + i) for i in range(n)]
+            imgs = [synth.reflectance_like_u8(h, w, 910 + first + i) for i in range(n)]
         elif kind == "grey1":
-            imgs = [synth.reflectance_like_u8(h, w, 910 + i)[:, :, :1] for i in range(n)]
+            imgs = [synth.reflectance_like_u8(h, w, 910 + first + i)[:, :, :1] for i in range(n)]
         else:
-            imgs = [synth.scene_u8(h, w, 920 + i)[:, :, 1:2] for i in range(n)]
+            imgs = [synth.scene_u8(h, w, 920 + first + i)[:, :, 1:2] for i in range(n)]
         _cache[key] = np.ascontiguousarray(np.stack(imgs))
     return _cache[key]
 
@@ -111,11 +121,11 @@ def _floats(shape, c, seed, scale=1.0):
     return _cache[key]
 
 
-def _packed(kind, sizes=MIXED):
+def _packed(kind, sizes=MIXED, first=0):
     """The images of `sizes` packed one after another, [total pixels, c]."""
-    key = ("packed", kind, sizes)
+    key = ("packed", kind, sizes, first)
     if key not in _cache:
-        parts = [_images((1, h, w), kind)[0].reshape(h * w, -1) for h, w in sizes]
+        parts = [_images((1, h, w), kind, first)[0].reshape(h * w, -1) for h, w in sizes]
         _cache[key] = np.ascontiguousarray(np.concatenate(parts))
     return _cache[key]
 
@@ -140,8 +150,9 @@ JBF_PAIRS = {   # name: (joint kind, src kind, flags)
     "joint1_as_bgr": ("joint1", "grey1", 4),
 }
 JBF_ROUTES = {  # name: (d, sigma_space, extra flags): radius 33 (two workgroups per CU for grey tiles),
-                # 42 (the 37..52 tile kernel), 54 (slabs), 33 untiled, 1 (two workgroups per CU again)
+                # 42 (the 37..52 tile kernel), 54 (slabs), 33 untiled, 1 (two workgroups per CU again), 1 untiled
     "s22": (-1, 22.0, 0), "s28": (-1, 28.0, 0), "s36": (-1, 36.0, 0), "generic": (-1, 22.0, 2), "d3": (3, 22.0, 0),
+    "generic_d3": (3, 22.0, 2),
 }
 
 
@@ -158,26 +169,31 @@ def _jbf_oracle(co, joint, src, d, sc, ss, flags):
     return np.stack(out)
 
 
-def jbf_u8(env, pair, route, shape, sigma_color=20.0, images=None):
+def jbf_u8(env, pair, route, shape, sigma_color=20.0, images=None, first=0):
     """images: (joint, src) uint8 [n,h,w,c] in place of the synthetic ones of `pair` (its flags stay)."""
     rf, co, torch = env
     lib = rf._ffi.load_library()
     jkind, skind, flags = JBF_PAIRS[pair]
     d, ss, extra = JBF_ROUTES[route]
     flags |= extra
-    joint, src = images if images is not None else (_images(shape, jkind), _images(shape, skind))
+    joint, src = images if images is not None else (_images(shape, jkind, first), _images(shape, skind, first))
     n, h, w = shape
     assert joint.shape[:3] == shape and src.shape[:3] == shape
     jcn, scn, sc = joint.shape[3], src.shape[3], sigma_color
     on_route = rf._ffi.jbf_two_wg_plan(n, h, w, jcn, scn, d, sc, ss, flags) is not None
     if route == "s22" and shape == S1 and pair in ("colour_grey3", "colour_grey1"):
         assert on_route, "the plan no longer puts this case on the two-workgroups-per-CU route"
-    if route in ("s28", "s36", "generic"):
+    if route in ("s28", "s36", "generic", "generic_d3"):
         assert not on_route
     count = [lib.rf_debug_jbf_two_wg_calls()]
 
-    def call(lib, p, stream):
-        return lib.rf_jbf_u8(p["joint"], p["src"], p["dst"], n, h, w, jcn, scn, d, sc, ss, 4, flags, stream)
+    def sized(k):
+        assert (rf._ffi.jbf_two_wg_plan(k * n, h, w, jcn, scn, d, sc, ss, flags) is not None) == on_route
+
+        def call(lib, p, stream):
+            return lib.rf_jbf_u8(p["joint"], p["src"], p["dst"], k * n, h, w, jcn, scn, d, sc, ss, 4, flags, stream)
+        return call, 0
+    call = sized(1)[0]
 
     def after():
         now = lib.rf_debug_jbf_two_wg_calls()
@@ -193,7 +209,7 @@ def jbf_u8(env, pair, route, shape, sigma_color=20.0, images=None):
     return Case([Buf("joint", "in", data=joint, decoy=_inv(joint)), Buf("src", "in", data=src, decoy=_inv(src)),
                  Buf("dst", "out", nbytes=src.nbytes)],
                 call, {"dst": (np.uint8, src.shape)}, check, after=after, entries=("rf_jbf_u8",),
-                two_wg=on_route)
+                two_wg=on_route, sized=sized)
 
 
 # ---- rf_gf_u8, rf_gf_ex_u8 ---------------------------------------------------------------------------------
@@ -210,26 +226,32 @@ def _gf_oracle(co, guide, src, radius, eps, iterations, grey_guide=False):
 
 
 def gf_u8(env, shape, skind, radius, iterations, two_kernel=False, ws_images=None, in_place=False,
-          grey_guide=False, options=None):
-    """options: debug switches held during the call ({"gf_force_two_streams": 1}, ...)."""
+          grey_guide=False, options=None, first=0):
+    """options: debug switches held during the call ({"gf_force_two_streams": 1}, ...); ws_images: the
+    workspace is sized for that many images, whatever n is."""
     rf, co, torch = env
     lib = rf._ffi.load_library()
     n, h, w = shape
-    guide = _images(shape, "joint1" if grey_guide else "colour")
-    src = _images(shape, skind)
+    guide = _images(shape, "joint1" if grey_guide else "colour", first)
+    src = _images(shape, skind, first)
     gcn, scn, eps = guide.shape[3], src.shape[3], 3.0
     need = lib.rf_gf_workspace_bytes(n if ws_images is None else ws_images, h, w, 3, scn, radius)
     assert need > 0
     if ws_images is not None and ws_images < n:
         assert need < lib.rf_gf_workspace_bytes(n, h, w, 3, scn, radius)
 
-    def call(lib, p, stream):
-        dst = p["src"] if in_place else p["dst"]
-        if grey_guide:
-            return lib.rf_gf_ex_u8(p["guide"], p["src"], dst, n, h, w, gcn, scn, radius, eps, iterations,
-                                   rf._ffi.GF_GREY_AS_BGR, p["ws"], need, stream)
-        return lib.rf_gf_u8(p["guide"], p["src"], dst, n, h, w, gcn, scn, radius, eps, iterations, p["ws"],
-                            need, stream)
+    def sized(k):
+        ws = need if ws_images is not None else lib.rf_gf_workspace_bytes(k * n, h, w, 3, scn, radius)
+
+        def call(lib, p, stream):
+            dst = p["src"] if in_place else p["dst"]
+            if grey_guide:
+                return lib.rf_gf_ex_u8(p["guide"], p["src"], dst, k * n, h, w, gcn, scn, radius, eps, iterations,
+                                       rf._ffi.GF_GREY_AS_BGR, p["ws"], ws, stream)
+            return lib.rf_gf_u8(p["guide"], p["src"], dst, k * n, h, w, gcn, scn, radius, eps, iterations, p["ws"],
+                                ws, stream)
+        return call, ws
+    call = sized(1)[0]
 
     out_name = "src" if in_place else "dst"
     oracle = _once(lambda: _gf_oracle(co, guide, src, radius, eps, iterations, grey_guide))
@@ -248,7 +270,7 @@ def gf_u8(env, shape, skind, radius, iterations, two_kernel=False, ws_images=Non
         opts["gf_two_kernel"] = 1
     around = (lambda: rf._ffi.debug_options(**opts)) if opts else None
     return Case(bufs, call, {out_name: (np.uint8, src.shape)}, check, around=around,
-                entries=("rf_gf_ex_u8" if grey_guide else "rf_gf_u8",))
+                entries=("rf_gf_ex_u8" if grey_guide else "rf_gf_u8",), sized=sized)
 
 
 # ---- the CNN -------------------------------------------------------------------------------------------
@@ -265,12 +287,12 @@ def _cnn_check(co, rf, bgr, outs):
             assert d8.max() <= 1 and np.mean(d8 != 0) < 1e-4
 
 
-def cnn_reflectance(env, entry, want, shape, packed=False):
+def cnn_reflectance(env, entry, want, shape, packed=False, first=0):
     """packed: the weights go through rf_cnn_pack_weights into a caller-owned buffer and the forward pass
     is the packed twin of `entry`, both on the call's stream."""
     rf, co, torch = env
     n, h, w = shape
-    bgr = _images(shape, "colour")
+    bgr = _images(shape, "colour", first)
     lut = rf.image_utils.srgb_byte_lut().astype(np.float32)
     wts = np.ascontiguousarray(rf.weights.load_weights(), dtype=np.float32).ravel()
     assert wts.size == rf._ffi.CNN_NPARAMS and lut.size == 256
@@ -294,23 +316,29 @@ def cnn_reflectance(env, entry, want, shape, packed=False):
         outputs["r8"] = (np.uint8, (n, h, w))
     layout = rf._ffi.CNN_NCHW_RGB if entry == "f32_nchw_rgb" else rf._ffi.CNN_NHWC_BGR
 
-    def call(lib, p, stream):
-        if packed:
-            rc = lib.rf_cnn_pack_weights(p["weights"], p["packed"], stream)
-            if rc != rf._ffi.RF_OK:
-                return rc
+    def sized(k):
+        m = k * n
+
+        def call(lib, p, stream):
+            if packed:
+                rc = lib.rf_cnn_pack_weights(p["weights"], p["packed"], stream)
+                if rc != rf._ffi.RF_OK:
+                    return rc
+                if entry == "u8":
+                    return lib.rf_cnn_reflectance_packed_u8(p["x"], p.get("r"), p.get("r8"), m, h, w, p["packed"],
+                                                            p["lut"], stream)
+                return lib.rf_cnn_reflectance_packed_f32(p["x"], p.get("r"), p.get("r8"), m, h, w, layout,
+                                                         p["packed"], stream)
             if entry == "u8":
-                return lib.rf_cnn_reflectance_packed_u8(p["x"], p.get("r"), p.get("r8"), n, h, w, p["packed"],
-                                                        p["lut"], stream)
-            return lib.rf_cnn_reflectance_packed_f32(p["x"], p.get("r"), p.get("r8"), n, h, w, layout,
-                                                     p["packed"], stream)
-        if entry == "u8":
-            return lib.rf_cnn_reflectance_u8(p["x"], p.get("r"), p.get("r8"), n, h, w, p["weights"], p["lut"], stream)
-        return lib.rf_cnn_reflectance_f32(p["x"], p.get("r"), p.get("r8"), n, h, w, layout, p["weights"], stream)
+                return lib.rf_cnn_reflectance_u8(p["x"], p.get("r"), p.get("r8"), m, h, w, p["weights"], p["lut"],
+                                                 stream)
+            return lib.rf_cnn_reflectance_f32(p["x"], p.get("r"), p.get("r8"), m, h, w, layout, p["weights"], stream)
+        return call, 0
+    call = sized(1)[0]
 
     forward = "rf_cnn_reflectance_%s%s" % ("packed_" if packed else "", "u8" if entry == "u8" else "f32")
     return Case(bufs, call, outputs, lambda outs: _cnn_check(co, rf, bgr, outs),
-                entries=(("rf_cnn_pack_weights",) if packed else ()) + (forward,))
+                entries=(("rf_cnn_pack_weights",) if packed else ()) + (forward,), sized=sized)
 
 
 # ---- colourise -----------------------------------------------------------------------------------------
@@ -329,14 +357,14 @@ def _steps(iu):
     return Buf("steps", "in", data=steps, decoy=steps * 0.5)
 
 
-def colorize_srgb_u8(env, want, shape):
+def colorize_srgb_u8(env, want, shape, first=0):
     from oracle import colorize_numpy as oc
     rf, co, torch = env
     lib = rf._ffi.load_library()
     iu = rf.image_utils
     n, h, w = shape
-    bgr = _images(shape, "colour")
-    r = _r_map(n * h * w, 930).reshape(n, h, w)
+    bgr = _images(shape, "colour", first)
+    r = _r_map(n * h * w, 930 + 7 * first).reshape(n, h, w)
     need = lib.rf_colorize_workspace_bytes(n)
     bufs = [Buf("bgr", "in", data=bgr, decoy=_inv(bgr)), Buf("r", "in", data=r, decoy=_r_decoy(r)), _steps(iu)]
     outputs = {}
@@ -348,10 +376,15 @@ def colorize_srgb_u8(env, want, shape):
         outputs["shad"] = (np.uint8, (n, h, w))
     bufs.append(Buf("ws", "ws", nbytes=need, elem=16))
 
-    def call(lib, p, stream):
-        return lib.rf_colorize_srgb_u8(p["bgr"], p["r"], p.get("refl"), p.get("shad"), n, h, w,
-                                       iu.percentile_rank(3 * h * w), iu.percentile_rank(h * w), p["steps"],
-                                       p["ws"], need, stream)
+    def sized(k):
+        ws = lib.rf_colorize_workspace_bytes(k * n)
+
+        def call(lib, p, stream):
+            return lib.rf_colorize_srgb_u8(p["bgr"], p["r"], p.get("refl"), p.get("shad"), k * n, h, w,
+                                           iu.percentile_rank(3 * h * w), iu.percentile_rank(h * w), p["steps"],
+                                           p["ws"], ws, stream)
+        return call, ws
+    call = sized(1)[0]
 
     oracle = _once(lambda: [oc.colorize_srgb_u8(bgr[i], r[i]) for i in range(n)])
 
@@ -363,7 +396,7 @@ def colorize_srgb_u8(env, want, shape):
             if "shad" in outs:
                 assert np.array_equal(outs["shad"][i], want_shad), i
 
-    return Case(bufs, call, outputs, check, entries=("rf_colorize_srgb_u8",))
+    return Case(bufs, call, outputs, check, entries=("rf_colorize_srgb_u8",), sized=sized)
 
 
 # ---- the float filters ---------------------------------------------------------------------------------
@@ -373,17 +406,23 @@ def _flipped(x):
     return np.ascontiguousarray(x[:, ::-1, ::-1, :])
 
 
-def jbf_f32(env, cn, d=-1, sigma_color=0.1, sigma_space=4.0):
+def jbf_f32(env, cn, d=-1, sigma_color=0.1, sigma_space=4.0, shape=S1, first=0):
     rf, co, torch = env
     lib = rf._ffi.load_library()
-    n, h, w = S1
-    joint, src = _floats(S1, cn, 940), _floats(S1, cn, 950)
+    n, h, w = shape
+    joint, src = _floats(shape, cn, 940 + first), _floats(shape, cn, 950 + first)
     sc, ss = sigma_color, sigma_space
     need = lib.rf_jbf_f32_workspace_bytes(n, cn)
     assert need > 0
 
-    def call(lib, p, stream):
-        return lib.rf_jbf_f32(p["joint"], p["src"], p["dst"], n, h, w, cn, cn, d, sc, ss, 4, p["ws"], need, stream)
+    def sized(k):
+        ws = lib.rf_jbf_f32_workspace_bytes(k * n, cn)
+
+        def call(lib, p, stream):
+            return lib.rf_jbf_f32(p["joint"], p["src"], p["dst"], k * n, h, w, cn, cn, d, sc, ss, 4, p["ws"], ws,
+                                  stream)
+        return call, ws
+    call = sized(1)[0]
 
     oracle = _once(lambda: [co.joint_bilateral_filter_f32(joint[i], src[i], d, sc, ss).reshape(src[i].shape)
                             for i in range(n)])
@@ -394,20 +433,27 @@ def jbf_f32(env, cn, d=-1, sigma_color=0.1, sigma_space=4.0):
 
     return Case([Buf("joint", "in", data=joint, decoy=_flipped(joint)), Buf("src", "in", data=src, decoy=_flipped(src)),
                  Buf("dst", "out", nbytes=src.nbytes, elem=4), Buf("ws", "ws", nbytes=need, elem=16)],
-                call, {"dst": (np.float32, src.shape)}, check, entries=("rf_jbf_f32",), sync=True)
+                call, {"dst": (np.float32, src.shape)}, check, entries=("rf_jbf_f32",), sync=True, sized=sized)
 
 
-def gf_f32(env, cn, radius):
+def gf_f32(env, cn, radius, shape=S1, first=0):
     rf, co, torch = env
     lib = rf._ffi.load_library()
-    n, h, w = S1
-    guide, src = _floats(S1, 3, 960), _floats(S1, cn, 970)
+    n, h, w = shape
+    guide, src = _floats(shape, 3, 960 + first), _floats(shape, cn, 970 + first)
     eps = 1e-3
     need = lib.rf_gf_f32_workspace_bytes(n, h, w, 3, cn, radius)
     assert need > 0
 
-    def call(lib, p, stream):
-        return lib.rf_gf_f32(p["guide"], p["src"], p["dst"], n, h, w, 3, cn, radius, eps, 1, p["ws"], need, stream)
+    def sized(k):
+        """(the workspace of 64 images at most: a longer batch runs in chunks)"""
+        ws = lib.rf_gf_f32_workspace_bytes(min(k * n, 64), h, w, 3, cn, radius)
+
+        def call(lib, p, stream):
+            return lib.rf_gf_f32(p["guide"], p["src"], p["dst"], k * n, h, w, 3, cn, radius, eps, 1, p["ws"], ws,
+                                 stream)
+        return call, ws
+    call = sized(1)[0]
 
     oracle = _once(lambda: [co.guided_filter_f32(guide[i], src[i], radius, eps).reshape(src[i].shape)
                             for i in range(n)])
@@ -418,7 +464,7 @@ def gf_f32(env, cn, radius):
 
     return Case([Buf("guide", "in", data=guide, decoy=_flipped(guide)), Buf("src", "in", data=src, decoy=_flipped(src)),
                  Buf("dst", "out", nbytes=src.nbytes, elem=4), Buf("ws", "ws", nbytes=need, elem=16)],
-                call, {"dst": (np.float32, src.shape)}, check, entries=("rf_gf_f32",))
+                call, {"dst": (np.float32, src.shape)}, check, entries=("rf_gf_f32",), sized=sized)
 
 
 # ---- the point sweep -----------------------------------------------------------------------------------
@@ -446,42 +492,52 @@ def _points_want(co, joints, srcs, pts, offs):
     return np.stack(want)
 
 
-def jbf_points(env, ragged):
-    rf, co, torch = env
-    lib = rf._ffi.load_library()
-    if ragged:
-        sizes = MIXED
-        joint, src = _packed("colour"), _packed("grey3")
-        joints, srcs = _split(joint), _split(src)
-        per = 60
-    else:
-        n, h, w = S1
-        sizes = ((h, w),) * n
-        joint, src = _images(S1, "colour"), _images(S1, "grey3")
-        joints, srcs = list(joint), list(src)
-        per = 150
+def points_call(lib, ragged, sizes, jcn, scn, total):
+    """(call, workspace bytes) of the point entry - ragged or uniform - over the images `sizes` ((h, w) each,
+    all alike for the uniform entry) with `total` points and POINT_PARAMS."""
     n = len(sizes)
-    pts, offs = _points(sizes, per, 980)
-    total = pts.shape[0]
-    assert total == 300
     sc = np.array([p[0] for p in POINT_PARAMS], np.float64)
     ss = np.array([p[1] for p in POINT_PARAMS], np.float64)
-    hs, wd = _i32([s[0] for s in sizes]), _i32([s[1] for s in sizes])
+    hs, wd = _sizes_arrays(sizes)
     if ragged:
-        need = lib.rf_jbf_points_ragged_workspace_bytes(n, len(POINT_PARAMS), ss.ctypes.data, -1, 3, 0)
+        need = lib.rf_jbf_points_ragged_workspace_bytes(n, len(POINT_PARAMS), ss.ctypes.data, -1, jcn, 0)
     else:
-        need = lib.rf_jbf_points_workspace_bytes(len(POINT_PARAMS), ss.ctypes.data, -1, 3, 0)
+        assert len(set(sizes)) == 1
+        need = lib.rf_jbf_points_workspace_bytes(len(POINT_PARAMS), ss.ctypes.data, -1, jcn, 0)
     assert need > 0
-    shape = (len(POINT_PARAMS), total, 3)
 
     def call(lib, p, stream):
         if ragged:
-            return lib.rf_jbf_points_ragged_u8(p["joint"], p["src"], n, hs.ctypes.data, wd.ctypes.data, 3, 3,
+            return lib.rf_jbf_points_ragged_u8(p["joint"], p["src"], n, hs.ctypes.data, wd.ctypes.data, jcn, scn,
                                                p["points"], p["offsets"], total, len(POINT_PARAMS), sc.ctypes.data,
                                                ss.ctypes.data, -1, 4, 0, p["out"], p["ws"], need, stream)
-        return lib.rf_jbf_points_u8(p["joint"], p["src"], n, sizes[0][0], sizes[0][1], 3, 3, p["points"],
+        return lib.rf_jbf_points_u8(p["joint"], p["src"], n, sizes[0][0], sizes[0][1], jcn, scn, p["points"],
                                     p["offsets"], total, len(POINT_PARAMS), sc.ctypes.data, ss.ctypes.data, -1, 4,
                                     0, p["out"], p["ws"], need, stream)
+    return call, need
+
+
+def jbf_points(env, ragged, sizes=None, jkind="colour", skind="grey3", first=0):
+    """sizes: the images ((h, w) each; MIXED for the ragged entry, S1's for the uniform one)."""
+    rf, co, torch = env
+    lib = rf._ffi.load_library()
+    if ragged:
+        sizes = MIXED if sizes is None else sizes
+        joint, src = _packed(jkind, sizes, first), _packed(skind, sizes, first)
+        joints, srcs = _split(joint, sizes), _split(src, sizes)
+        per = 60
+    else:
+        sizes = ((S1[1], S1[2]),) * S1[0] if sizes is None else sizes
+        shape = (len(sizes),) + tuple(sizes[0])
+        joint, src = _images(shape, jkind, first), _images(shape, skind, first)
+        joints, srcs = list(joint), list(src)
+        per = 150
+    jcn, scn = joints[0].shape[2], srcs[0].shape[2]
+    pts, offs = _points(sizes, per, 980 + 7 * first)
+    total = pts.shape[0]
+    assert total == per * len(sizes)
+    call, need = points_call(lib, ragged, sizes, jcn, scn, total)
+    shape = (len(POINT_PARAMS), total, scn)
 
     oracle = _once(lambda: _points_want(co, joints, srcs, pts, offs))
 
@@ -512,11 +568,11 @@ def _comparisons(n, h, w, per_image, seed):
     return out
 
 
-def whdr_f32(env, c):
+def whdr_f32(env, c, shape=S1, first=0):
     rf, co, torch = env
-    n, h, w = S1
-    refl = np.ascontiguousarray(_floats(S1, c, 990).transpose(0, 3, 1, 2))        # planar [n][c][h][w]
-    comps = _comparisons(n, h, w, 130, 991)
+    n, h, w = shape
+    refl = np.ascontiguousarray(_floats(shape, c, 990 + first).transpose(0, 3, 1, 2))        # planar [n][c][h][w]
+    comps = _comparisons(n, h, w, 130, 991 + 7 * first)
     allc = np.concatenate(comps)
     pts, wts = _i32(allc[:, :5]), np.ascontiguousarray(allc[:, 5])
     offs = _i32(np.arange(n + 1) * 130)
@@ -534,13 +590,13 @@ def whdr_f32(env, c):
                 call, {"out": (np.float64, (n,))}, check, entries=("rf_whdr_f32",))
 
 
-def whdr_points_u8(env, c):
+def whdr_points_u8(env, c, shape=S1, first=0):
     """Two sets of whole images taken as point lists (pixel y * w + x of image i behind i * h * w)."""
     rf, co, torch = env
-    n, h, w = S1
-    sets = np.stack([_images(S1, "colour")[..., :c], _images(S1, "grey3")[..., :c]])     # [2][n][h][w][c]
+    n, h, w = shape
+    sets = np.stack([_images(shape, "colour", first)[..., :c], _images(shape, "grey3", first)[..., :c]])  # [2][n][h][w][c]
     samples = np.ascontiguousarray(sets.reshape(2, n * h * w, c))
-    comps = _comparisons(n, h, w, 130, 992)
+    comps = _comparisons(n, h, w, 130, 992 + 7 * first)
     allc = np.concatenate(comps).astype(np.int64)
     idx = _i32(np.stack([allc[:, 1] * w + allc[:, 0], allc[:, 3] * w + allc[:, 2], allc[:, 4]], axis=1))
     wts = np.ascontiguousarray(np.concatenate(comps)[:, 5])
@@ -566,91 +622,118 @@ def whdr_points_u8(env, c):
 
 # ---- the ragged entries: one mixed list each -------------------------------------------------------------
 
-def _sizes_arrays():
-    return _i32([s[0] for s in MIXED]), _i32([s[1] for s in MIXED])
+def _sizes_arrays(sizes=MIXED):
+    return _i32([s[0] for s in sizes]), _i32([s[1] for s in sizes])
 
 
-def jbf_ragged_u8(env, sigma_space=22.0):
+def jbf_ragged_u8(env, sigma_space=22.0, sizes=MIXED, skind="grey3", first=0):
     """sigma_space 22: radius 33, the tile classes; 36: radius 54, the slab launch."""
     rf, co, torch = env
     lib = rf._ffi.load_library()
-    joint, src = _packed("colour"), _packed("grey3")
-    hs, wd = _sizes_arrays()
-    n, d, sc, ss = len(MIXED), -1, 20.0, sigma_space
-    need = lib.rf_jbf_ragged_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, 3, 3, d, ss, 0)
+    joint, src = _packed("colour", sizes, first), _packed(skind, sizes, first)
+    scn = src.shape[1]
+    hs, wd = _sizes_arrays(sizes)
+    n, d, sc, ss = len(sizes), -1, 20.0, sigma_space
+    need = lib.rf_jbf_ragged_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, 3, scn, d, ss, 0)
     if int(np.rint(ss * 1.5)) <= 52:
-        assert need > 0 and rf._ffi.jbf_ragged_plan(MIXED, 3, 3, d, sc, ss) is not None
+        assert need > 0 and rf._ffi.jbf_ragged_plan(sizes, 3, scn, d, sc, ss) is not None
     else:
-        assert need > 0 and rf._ffi.jbf_ragged_slab_plan(MIXED, 3, 3, d, sc, ss) is not None
+        assert need > 0 and rf._ffi.jbf_ragged_slab_plan(sizes, 3, scn, d, sc, ss) is not None
 
-    def call(lib, p, stream):
-        return lib.rf_jbf_ragged_u8(p["joint"], p["src"], p["dst"], n, hs.ctypes.data, wd.ctypes.data, 3, 3, d, sc,
-                                    ss, 4, 0, p["ws"], need, stream)
+    def sized(k):
+        hk, wk = np.tile(hs, k), np.tile(wd, k)
+        ws = lib.rf_jbf_ragged_workspace_bytes(k * n, hk.ctypes.data, wk.ctypes.data, 3, scn, d, ss, 0)
+        assert ws > 0
 
-    oracle = _once(lambda: [co.joint_bilateral_filter(j, s, d, sc, ss) for j, s in zip(_split(joint), _split(src))])
+        def call(lib, p, stream):
+            return lib.rf_jbf_ragged_u8(p["joint"], p["src"], p["dst"], k * n, hk.ctypes.data, wk.ctypes.data, 3, scn,
+                                        d, sc, ss, 4, 0, p["ws"], ws, stream)
+        return call, ws
+    call = sized(1)[0]
+
+    oracle = _once(lambda: [co.joint_bilateral_filter(j, s, d, sc, ss).reshape(s.shape)
+                            for j, s in zip(_split(joint, sizes), _split(src, sizes))])
 
     def check(outs):
-        for i, got in enumerate(_split(outs["dst"])):
+        for i, got in enumerate(_split(outs["dst"], sizes)):
             assert np.array_equal(got, oracle()[i]), i
 
     return Case([Buf("joint", "in", data=joint, decoy=_inv(joint)), Buf("src", "in", data=src, decoy=_inv(src)),
                  Buf("dst", "out", nbytes=src.nbytes), Buf("ws", "ws", nbytes=need, elem=16)],
-                call, {"dst": (np.uint8, src.shape)}, check, entries=("rf_jbf_ragged_u8",), sync=True)
+                call, {"dst": (np.uint8, src.shape)}, check, entries=("rf_jbf_ragged_u8",), sync=True, sized=sized)
 
 
-def gf_ragged_u8(env):
+def gf_ragged_u8(env, sizes=MIXED, grey_guide=False, first=0):
+    """grey_guide: a one-channel guide under RF_GF_GREY_AS_BGR."""
     rf, co, torch = env
     lib = rf._ffi.load_library()
-    guide, src = _packed("colour"), _packed("grey1")
-    hs, wd = _sizes_arrays()
-    n, radius, eps, iterations = len(MIXED), 9, 3.0, 2
-    need = lib.rf_gf_ragged_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, 3, 1, radius, 0)
-    assert need > 0 and rf._ffi.gf_ragged_plan(MIXED, 3, 1, radius) is not None
+    guide, src = _packed("joint1" if grey_guide else "colour", sizes, first), _packed("grey1", sizes, first)
+    gcn, flags = guide.shape[1], (rf._ffi.GF_GREY_AS_BGR if grey_guide else 0)
+    hs, wd = _sizes_arrays(sizes)
+    n, radius, eps, iterations = len(sizes), 9, 3.0, 2
+    need = lib.rf_gf_ragged_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, gcn, 1, radius, flags)
+    assert need > 0
+    if not grey_guide:
+        assert rf._ffi.gf_ragged_plan(sizes, 3, 1, radius) is not None
 
-    def call(lib, p, stream):
-        return lib.rf_gf_ragged_u8(p["guide"], p["src"], p["dst"], n, hs.ctypes.data, wd.ctypes.data, 3, 1, radius,
-                                   eps, iterations, 0, p["ws"], need, stream)
+    def sized(k):
+        hk, wk = np.tile(hs, k), np.tile(wd, k)
+        ws = lib.rf_gf_ragged_workspace_bytes(k * n, hk.ctypes.data, wk.ctypes.data, gcn, 1, radius, flags)
+        assert ws > 0
 
-    oracle = _once(lambda: [_gf_oracle(co, [g], [s], radius, eps, iterations)[0]
-                            for g, s in zip(_split(guide), _split(src))])
+        def call(lib, p, stream):
+            return lib.rf_gf_ragged_u8(p["guide"], p["src"], p["dst"], k * n, hk.ctypes.data, wk.ctypes.data, gcn, 1,
+                                       radius, eps, iterations, flags, p["ws"], ws, stream)
+        return call, ws
+    call = sized(1)[0]
+
+    oracle = _once(lambda: [_gf_oracle(co, [g], [s], radius, eps, iterations, grey_guide)[0]
+                            for g, s in zip(_split(guide, sizes), _split(src, sizes))])
 
     def check(outs):
-        for i, got in enumerate(_split(outs["dst"])):
+        for i, got in enumerate(_split(outs["dst"], sizes)):
             assert np.array_equal(got, oracle()[i]), i
 
     return Case([Buf("guide", "in", data=guide, decoy=_inv(guide)), Buf("src", "in", data=src, decoy=_inv(src)),
                  Buf("dst", "out", nbytes=src.nbytes), Buf("ws", "ws", nbytes=need, elem=16)],
-                call, {"dst": (np.uint8, src.shape)}, check, entries=("rf_gf_ragged_u8",), sync=True)
+                call, {"dst": (np.uint8, src.shape)}, check, entries=("rf_gf_ragged_u8",), sync=True, sized=sized)
 
 
-def colorize_ragged(env, entry):
+def colorize_ragged(env, entry, sizes=MIXED, first=0):
     from oracle import colorize_numpy as oc
     rf, co, torch = env
     lib = rf._ffi.load_library()
     iu = rf.image_utils
-    bgr = _packed("colour")
+    bgr = _packed("colour", sizes, first)
     npx = bgr.shape[0]
-    hs, wd = _sizes_arrays()
-    n = len(MIXED)
+    hs, wd = _sizes_arrays(sizes)
+    n = len(sizes)
     if entry.endswith("r8_srgb_u8"):
-        r_in = np.random.default_rng(931).integers(13, 256, npx).astype(np.uint8)
+        r_in = np.random.default_rng(931 + 7 * first).integers(13, 256, npx).astype(np.uint8)
         r = r_in.astype(np.float32) / np.float32(255)
         r_decoy = (268 - r_in.astype(np.int64)).astype(np.uint8)          # 13..255 again
     else:
-        r_in = r = _r_map(npx, 932)
+        r_in = r = _r_map(npx, 932 + 7 * first)
         r_decoy = _r_decoy(r_in)
-    k_refl = np.array([iu.percentile_rank(3 * h * w) for h, w in MIXED], np.uint64)
-    k_shad = np.array([iu.percentile_rank(h * w) for h, w in MIXED], np.uint64)
+    k_refl = np.array([iu.percentile_rank(3 * h * w) for h, w in sizes], np.uint64)
+    k_shad = np.array([iu.percentile_rank(h * w) for h, w in sizes], np.uint64)
     need = lib.rf_colorize_ragged_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data)
     assert need > 0
 
-    def call(lib, p, stream):
-        return getattr(lib, entry)(p["bgr"], p["r"], p["refl"], p["shad"], n, hs.ctypes.data, wd.ctypes.data,
-                                   k_refl.ctypes.data, k_shad.ctypes.data, p["steps"], p["ws"], need, stream)
+    def sized(k):
+        hk, wk, kr, ks = np.tile(hs, k), np.tile(wd, k), np.tile(k_refl, k), np.tile(k_shad, k)
+        ws = lib.rf_colorize_ragged_workspace_bytes(k * n, hk.ctypes.data, wk.ctypes.data)
+        assert ws > 0
+
+        def call(lib, p, stream):
+            return getattr(lib, entry)(p["bgr"], p["r"], p["refl"], p["shad"], k * n, hk.ctypes.data, wk.ctypes.data,
+                                       kr.ctypes.data, ks.ctypes.data, p["steps"], p["ws"], ws, stream)
+        return call, ws
+    call = sized(1)[0]
 
     def want_all():
         out, at = [], 0
-        for h, w in MIXED:
+        for h, w in sizes:
             out.append(oc.colorize_srgb_u8(bgr[at:at + h * w].reshape(h, w, 3), r[at:at + h * w].reshape(h, w)))
             at += h * w
         return out
@@ -658,7 +741,7 @@ def colorize_ragged(env, entry):
 
     def check(outs):
         at = 0
-        for i, (h, w) in enumerate(MIXED):
+        for i, (h, w) in enumerate(sizes):
             want_refl, want_shad = oracle()[i]
             assert np.array_equal(outs["refl"][at:at + h * w].reshape(h, w, 3), want_refl), i
             assert np.array_equal(outs["shad"][at:at + h * w].reshape(h, w), want_shad), i
@@ -667,7 +750,8 @@ def colorize_ragged(env, entry):
     return Case([Buf("bgr", "in", data=bgr, decoy=_inv(bgr)), Buf("r", "in", data=r_in, decoy=r_decoy), _steps(iu),
                  Buf("refl", "out", nbytes=3 * npx), Buf("shad", "out", nbytes=npx),
                  Buf("ws", "ws", nbytes=need, elem=16)],
-                call, {"refl": (np.uint8, (npx, 3)), "shad": (np.uint8, (npx,))}, check, entries=(entry,), sync=True)
+                call, {"refl": (np.uint8, (npx, 3)), "shad": (np.uint8, (npx,))}, check, entries=(entry,), sync=True,
+                sized=sized)
 
 
 def png_deflate_ragged_u8(env):
@@ -706,13 +790,13 @@ def png_deflate_ragged_u8(env):
                 call, outputs, check, entries=("rf_png_deflate_ragged_u8",), sync=True)
 
 
-def png_unfilter_ragged_u8(env):
+def png_unfilter_ragged_u8(env, first=0):
     """raw is reconstructed in place, so it is an output; its bytes are not compared across layouts."""
     rf, co, torch = env
     lib = rf._ffi.load_library()
     iu = rf.image_utils
-    rng = np.random.default_rng(995)
-    other = np.random.default_rng(996)          # the decoy streams: other samples behind the same filter bytes
+    rng = np.random.default_rng(995 + 7 * first)
+    other = np.random.default_rng(996 + 7 * first)          # the decoy streams: other samples behind the same filter bytes
     formats = ((8, 2), (16, 6), (8, 3), (8, 0), (16, 0))
     datas, want, decoys = [], [], []
     for (h, w), (depth, ctype) in zip(MIXED, formats):
@@ -746,10 +830,18 @@ def png_unfilter_ragged_u8(env):
     need = lib.rf_png_unfilter_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, fm.ctypes.data)
     assert need > 0
 
-    def call(lib, p, stream):
-        return lib.rf_png_unfilter_ragged_u8(p["raw"], offs.ctypes.data, n, hs.ctypes.data, wd.ctypes.data,
-                                             fm.ctypes.data, p["palettes"], p["images"], p["flags"], p["ws"], need,
-                                             stream)
+    def sized(k):
+        hk, wk, fk = np.tile(hs, k), np.tile(wd, k), np.tile(fm, k)
+        ok = np.concatenate([offs[:-1] + np.uint64(i) * offs[-1] for i in range(k)] + [offs[-1:] * np.uint64(k)])
+        ws = lib.rf_png_unfilter_workspace_bytes(k * n, hk.ctypes.data, wk.ctypes.data, fk.ctypes.data)
+        assert ws > 0 and ok.dtype == np.uint64 and ok.size == k * n + 1
+
+        def call(lib, p, stream):
+            return lib.rf_png_unfilter_ragged_u8(p["raw"], ok.ctypes.data, k * n, hk.ctypes.data, wk.ctypes.data,
+                                                 fk.ctypes.data, p["palettes"], p["images"], p["flags"], p["ws"], ws,
+                                                 stream)
+        return call, ws
+    call = sized(1)[0]
 
     def check(outs):
         for i, (got, exp) in enumerate(zip(_split(outs["images"]), want)):
@@ -761,4 +853,4 @@ def png_unfilter_ragged_u8(env):
                  Buf("images", "out", nbytes=3 * npx), Buf("flags", "out", nbytes=n),
                  Buf("ws", "ws", nbytes=need, elem=16)],
                 call, {"images": (np.uint8, (npx, 3)), "flags": (np.uint8, (n,))}, check,
-                entries=("rf_png_unfilter_ragged_u8",), sync=True)
+                entries=("rf_png_unfilter_ragged_u8",), sync=True, sized=sized)
