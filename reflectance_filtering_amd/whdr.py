@@ -364,6 +364,169 @@ def sweep_guided_packed(src, joint, sizes, dedup, pairs, delta=0.1, grey_as_bgr=
     return out
 
 
+# bytes of full-pass results held at once by the bilateral half of a chain (two buffers per pair)
+SWEEP_CHAIN_BYTES = 1 << 30
+
+
+def _empty(shape, like):
+    """An uninitialised uint8 tensor of `shape` on the device of `like`."""
+    import torch
+    return torch.empty(tuple(shape), dtype=torch.uint8, device=like.device)
+
+
+def _sample(results, index):
+    """The pixels `index` (device int64 [total]) of every result (tensors of equal shape whose last
+    dimension is the channel): uint8 [len(results), total, C]."""
+    import torch
+    return torch.stack([r.view(-1, r.shape[-1])[index] for r in results]).contiguous()
+
+
+def _index(values, like):
+    """Host int64 indices on the device of `like`."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(values, dtype=np.int64)).to(like.device)
+
+
+def _cat(parts):
+    import torch
+    return torch.cat(list(parts)).contiguous()
+
+
+def _point_pixels(dedup, sizes):
+    """Where the deduplicated points of images packed one after another lie: (image_offsets int64
+    [n+1], the first pixel of every image; pixels int64 [total points], y * w_i + x behind it)."""
+    pts, point_offsets = dedup[0], np.asarray(dedup[1], dtype=np.int64)
+    image_offsets = np.concatenate([[0], np.cumsum([int(h) * int(w) for h, w in sizes],
+                                                   dtype=np.int64)])
+    widths = np.repeat(np.array([int(w) for _, w in sizes], dtype=np.int64), np.diff(point_offsets))
+    return image_offsets, pts[:, 1].astype(np.int64) * widths + pts[:, 0].astype(np.int64)
+
+
+def _pixel_comps(dedup, pixels):
+    """The comparisons re-indexed from their image's points to its pixels (the whole image as the
+    point list, as sweep_guided_packed scores a full pass)."""
+    point_offsets, comps, comp_offsets = (np.asarray(dedup[k], dtype=np.int64) for k in (1, 2, 4))
+    first = np.repeat(point_offsets[:-1], np.diff(comp_offsets))    # first point of a comparison's image
+    px = dedup[2].copy()
+    px[:, :2] = pixels[first[:, None] + comps[:, :2]]
+    return px
+
+
+def _chain_guided(src, sizes, dedup, pairs, iterations, delta, one_pass):
+    """The guided chain on images that lie one after another in `src` (a packed list [total pixels,
+    C], or a batch [N,H,W,C] with sizes = N x (H, W)): float64 [K, P, n].  Pairs are grouped by radius
+    and equal (radius, eps) pairs computed once, as in sweep_guided_packed;
+    one_pass(cur, radius, eps, out) filters cur into out once and returns the result, which is the
+    src of that pair's next pass.  Every pass of a chunk of eps is scored by one WHDR call on the
+    filtered images as point lists; a chunk's filtered bytes - the pass being written and the one it
+    reads - stay under SWEEP_GUIDED_BYTES."""
+    pts, point_offsets, comps, weights, comp_offsets = dedup
+    out = np.zeros((iterations, pairs.shape[0], len(sizes)), dtype=np.float64)
+    if comps.shape[0] == 0:
+        return out
+    image_offsets, pixels = _point_pixels(dedup, sizes)
+    px_comps = _pixel_comps(dedup, pixels)
+    by_radius = {}      # radius -> {eps: [rows of pairs]}, both in order of first appearance
+    for p, (sc, ss) in enumerate(pairs):
+        by_radius.setdefault(int(ss), {}).setdefault(float(sc), []).append(p)
+    shape = tuple(src.shape)
+    per = max(1, SWEEP_GUIDED_BYTES // max(1, 2 * int(np.prod(shape))))
+    for radius, rows in by_radius.items():
+        eps = list(rows)
+        for e0 in range(0, len(eps), per):
+            chunk = eps[e0:e0 + per]
+            cur = [src] * len(chunk)
+            for k in range(iterations):
+                filtered = _empty((len(chunk),) + shape, src)
+                cur = [one_pass(cur[j], radius, e, filtered[j]) for j, e in enumerate(chunk)]
+                res = whdr_points_u8(filtered.view(len(chunk), -1, shape[-1]), image_offsets,
+                                     px_comps, weights, comp_offsets, delta)
+                for j, e in enumerate(chunk):
+                    out[k, rows[e]] = res[j]
+    return out
+
+
+def _chain_bilateral(src, sizes, dedup, pairs, iterations, delta, full_pass, point_pass):
+    """The bilateral chain on images that lie one after another in `src` (as in _chain_guided):
+    float64 [K, P, n].  full_pass(cur, sigma_color, sigma_space, out) filters cur into out and returns
+    the result; point_pass(cur, sigma_color, sigma_space) evaluates one more pass at the deduplicated
+    points only: uint8 [1, total points, C].  Passes 1..K-1 of a pair ping-pong between two buffers
+    and are scored on their samples at the points, pass K is the point pass on the result of pass
+    K-1; the pairs of a group share each pass's WHDR call, and a group's buffers stay under
+    SWEEP_CHAIN_BYTES."""
+    pts, point_offsets, comps, weights, comp_offsets = dedup
+    out = np.zeros((iterations, pairs.shape[0], len(sizes)), dtype=np.float64)
+    if comps.shape[0] == 0:
+        return out
+    image_offsets, pixels = _point_pixels(dedup, sizes)
+    index = _index(pixels + np.repeat(image_offsets[:-1],
+                                      np.diff(np.asarray(point_offsets, dtype=np.int64))), src)
+    shape = tuple(src.shape)
+    n_bufs = min(iterations - 1, 2)
+    per = max(1, SWEEP_CHAIN_BYTES // max(1, n_bufs * int(np.prod(shape))))
+    for p0 in range(0, pairs.shape[0], per):
+        group = [(float(sc), float(ss)) for sc, ss in pairs[p0:p0 + per]]
+        rows = slice(p0, p0 + len(group))
+        bufs = _empty((len(group), n_bufs) + shape, src)
+        cur = [src] * len(group)
+        for k in range(iterations - 1):
+            cur = [full_pass(cur[g], sc, ss, bufs[g, k % 2]) for g, (sc, ss) in enumerate(group)]
+            out[k, rows] = whdr_points_u8(_sample(cur, index), point_offsets, comps, weights,
+                                          comp_offsets, delta)
+        last = _cat(point_pass(cur[g], sc, ss) for g, (sc, ss) in enumerate(group))
+        out[iterations - 1, rows] = whdr_points_u8(last, point_offsets, comps, weights, comp_offsets,
+                                                   delta)
+    return out
+
+
+def chain_packed(src, joint, sizes, dedup, pairs, iterations, delta=0.1, grey_as_bgr=False):
+    """sweep_packed for a chain of `iterations` >= 2 passes with the joint held fixed: float64
+    [K, P, n], slice k the WHDR after pass k + 1.  Per pair K - 1 full ragged passes
+    (ops.joint_bilateral_ragged_u8, the uint8 result of one the src of the next) and one point pass
+    (ops.joint_bilateral_points_ragged_u8 on the result of pass K - 1)."""
+    from . import ops
+    pairs = np.asarray(pairs, dtype=np.float64).reshape(-1, 2)
+    return _chain_bilateral(
+        src, sizes, dedup, pairs, iterations, delta,
+        lambda cur, sc, ss, out: ops.joint_bilateral_ragged_u8(
+            joint, cur, -1, sc, ss, grey_as_bgr=grey_as_bgr, sizes=sizes, out=out)[0],
+        lambda cur, sc, ss: ops.joint_bilateral_points_ragged_u8(
+            joint, cur, dedup[0], dedup[1], [(sc, ss)], d=-1, grey_as_bgr=grey_as_bgr, sizes=sizes))
+
+
+def chain_guided_packed(src, joint, sizes, dedup, pairs, iterations, delta=0.1, grey_as_bgr=False):
+    """sweep_guided_packed for a chain of `iterations` >= 2 passes with the guide held fixed: float64
+    [K, P, n], slice k the WHDR after pass k + 1.  Per distinct (radius, eps) one
+    ops.guided_filter_ragged_u8 call per pass, the packed result of one the src of the next."""
+    from . import ops
+    pairs = np.asarray(pairs, dtype=np.float64).reshape(-1, 2)
+    return _chain_guided(
+        src, sizes, dedup, pairs, iterations, delta,
+        lambda cur, radius, eps, out: ops.guided_filter_ragged_u8(
+            joint, cur, radius, eps, iterations=1, grey_as_bgr=grey_as_bgr, sizes=sizes, out=out)[0])
+
+
+def _chain_batch(filter_type, src, joint, comparisons_px, pairs, iterations, delta, grey_as_bgr):
+    """The chain on one device batch of equal-size images, through the uniform ops: float64
+    [K, P, N]."""
+    from . import ops
+    n, h, w, _ = src.shape
+    dedup = dedup_points(comparisons_px, h, w)
+    sizes = [(h, w)] * n
+    if filter_type == "bilateral":
+        return _chain_bilateral(
+            src, sizes, dedup, pairs, iterations, delta,
+            lambda cur, sc, ss, out: ops.joint_bilateral_u8(joint, cur, -1, sc, ss, out=out,
+                                                            grey_as_bgr=grey_as_bgr),
+            lambda cur, sc, ss: ops.joint_bilateral_points_u8(joint, cur, dedup[0], dedup[1],
+                                                              [(sc, ss)], d=-1,
+                                                              grey_as_bgr=grey_as_bgr))
+    return _chain_guided(
+        src, sizes, dedup, pairs, iterations, delta,
+        lambda cur, radius, eps, out: ops.guided_filter_u8(joint, cur, radius, eps, out=out,
+                                                           grey_as_bgr=grey_as_bgr))
+
+
 def _as3(image):
     return image.unsqueeze(-1) if image.dim() == 2 else image
 
@@ -388,9 +551,19 @@ def _stack(images):
     return torch.stack([p.cuda() for p in parts]).contiguous()
 
 
-def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_as_bgr=False):
+def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_as_bgr=False,
+          iterations=1):
     """WHDR of filter(joint, src) for every (sigma_color, sigma_space) pair: float64 [P, N] on the
     host, row p = pair p, column i = image i in the caller's order.
+
+    iterations = K > 1 scores a chain: float64 [K, P, N], slice k the WHDR after the filter has been
+    applied k + 1 times with the joint held fixed and the uint8 result of one pass the src of the
+    next (the rule of filter_reflectance.apply_filter_batch(iterations=)).  A chain takes the routes
+    described below pass by pass: 'guided' one full pass per distinct (radius, eps) at a time
+    (ops.guided_filter_ragged_u8(iterations=1) on a packed list, ops.guided_filter_u8 on a batch),
+    every pass scored; 'bilateral' K - 1 full passes per pair (ops.joint_bilateral_ragged_u8 /
+    ops.joint_bilateral_u8, two ping-pong buffers per pair, scored on their samples at the judgement
+    points) and pass K at the points only.
 
     src / joint: CUDA uint8 batches [N,H,W,C], or lists of N images (CUDA tensors or numpy
     arrays [H,W,C]) that may differ in size.  comparisons_px: N arrays [n_i,6] in pixel coordinates
@@ -418,12 +591,19 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
         raise ValueError("sigma_pairs is empty")
     for sc, ss in pairs:
         fr._check_params(filter_type, sc, ss)
+    iterations = int(iterations)
+    if iterations < 1:
+        raise ValueError("iterations must be >= 1")
+    chain = iterations > 1
     if torch.is_tensor(src):
         if not torch.is_tensor(joint) or src.dim() != 4:
             raise ValueError("src and joint must both be CUDA batches [N,H,W,C] or both lists")
         if len(comparisons_px) != src.shape[0]:
             raise ValueError("one comparison array per image")
         _ffi.require_gpu()
+        if chain:
+            return _chain_batch(filter_type, src, joint, comparisons_px, pairs, iterations, delta,
+                                grey_as_bgr)
         return _sweep_batch(filter_type, src, joint, comparisons_px, pairs, delta, grey_as_bgr)
     src, joint = list(src), list(joint)
     if len(src) != len(joint) or len(src) != len(comparisons_px):
@@ -436,7 +616,8 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
             raise ValueError("src and joint images must have the same size")
     _ffi.require_gpu()
 
-    out = np.zeros((pairs.shape[0], len(src)), dtype=np.float64)
+    # [K, P, N] throughout; a single pass hands back its only slice
+    out = np.zeros((iterations, pairs.shape[0], len(src)), dtype=np.float64)
 
     def key(i):   # (H, W, src channels, joint channels): equal keys batch together
         s_shape, j_shape = tuple(src[i].shape), tuple(joint[i].shape)
@@ -455,8 +636,10 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
             s_p = _pack_list([src[i] for i in pack], torch)
             j_p = s_p if all(joint[i] is src[i] for i in pack) else \
                 _pack_list([joint[i] for i in pack], torch)
-            out[:, pack] = sweep_packed(s_p, j_p, psizes, pdedup, pairs, delta, grey_as_bgr)
-        return out
+            out[:, :, pack] = chain_packed(s_p, j_p, psizes, pdedup, pairs, iterations, delta,
+                                           grey_as_bgr) if chain else \
+                sweep_packed(s_p, j_p, psizes, pdedup, pairs, delta, grey_as_bgr)[None]
+        return out if chain else out[0]
     # guided, a one-channel device list of more than one shape (the conditions of
     # filter_reflectance.apply_filter_list's ragged route): the pairs whose radius the ragged guided
     # filter takes run pack by pack, one ragged call per pack and distinct pair
@@ -475,11 +658,14 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
             s_p = _pack_list([src[i] for i in pack], torch)
             j_p = s_p if all(joint[i] is src[i] for i in pack) else \
                 _pack_list([joint[i] for i in pack], torch)
-            out[np.ix_(rows, pack)] = sweep_guided_packed(s_p, j_p, [sizes[i] for i in pack], pdedup,
-                                                          pairs[rows], delta, grey_as_bgr)
+            psizes = [sizes[i] for i in pack]
+            out[(slice(None),) + np.ix_(rows, pack)] = \
+                chain_guided_packed(s_p, j_p, psizes, pdedup, pairs[rows], iterations, delta,
+                                    grey_as_bgr) if chain else \
+                sweep_guided_packed(s_p, j_p, psizes, pdedup, pairs[rows], delta, grey_as_bgr)[None]
         rest = [p for p in range(pairs.shape[0]) if p not in rows]
         if not rest:
-            return out
+            return out if chain else out[0]
     else:
         rest = list(range(pairs.shape[0]))
     # everything else: equal shapes per pass, grouped wherever they stand in the list
@@ -490,6 +676,9 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
         j_b = _stack([joint[i] for i in run])
         if s_b.shape[:3] != j_b.shape[:3]:
             raise ValueError("src and joint images must have the same size")
-        out[np.ix_(rest, run)] = _sweep_batch(filter_type, s_b, j_b, [comparisons_px[i] for i in run],
-                                              pairs[rest], delta, grey_as_bgr)
-    return out
+        run_comps = [comparisons_px[i] for i in run]
+        out[(slice(None),) + np.ix_(rest, run)] = \
+            _chain_batch(filter_type, s_b, j_b, run_comps, pairs[rest], iterations, delta,
+                         grey_as_bgr) if chain else \
+            _sweep_batch(filter_type, s_b, j_b, run_comps, pairs[rest], delta, grey_as_bgr)[None]
+    return out if chain else out[0]
