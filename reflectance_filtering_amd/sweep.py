@@ -26,6 +26,9 @@ other as three), --guidance_files guides with a stored image such as the referen
 --iterations K chains the filter K times with the guidance held fixed and scores every pass (the
 JSON gains `passes`, the npz matrix a leading pass axis).  Photos, stored files and judgement files
 are read on batch.IO_THREADS threads; --png_decoder device leaves only inflate to them.
+
+run(..., src_coding="srgb") scores stored sources that are sRGB-coded (whdr.value_table); its command
+line, with the unfiltered row beside the sweep, is reflectance_filtering_amd.score.
 """
 from __future__ import division, print_function
 
@@ -39,6 +42,7 @@ import numpy as np
 FILTER_TYPES = ("bilateral", "guided")
 GUIDANCE = ("cnn", "image")
 PNG_DECODERS = ("host", "device")      # batch.PNG_DECODERS (batch imports the device ops)
+SRC_CODINGS = ("linear", "srgb")       # whdr.CODINGS: what a byte of a stored source stands for
 
 
 def _positive_int(text):
@@ -184,10 +188,12 @@ def _device_list(images, channels=3):
 
 
 def _sweep_stored(filter_type, pairs, comps, images, sources, grey_sources, guides, guidance, delta,
-                  iterations):
+                  iterations, values=None):
     """The sweep over stored sources: float64 [K, P, N].  Grey sources (three equal channels) are
     filtered and scored as one channel, the others as three; a list that mixes them is split by that
-    signature into one whdr.sweep call each, and the columns go back in the caller's order."""
+    signature into one whdr.sweep call each, and the columns go back in the caller's order.  values:
+    the value table the passes are scored with (whdr.sweep(values=)); None makes the calls of ever."""
+    coded = {} if values is None else {"values": values}
     from . import whdr
     out = np.zeros((iterations, pairs.shape[0], len(sources)), dtype=np.float64)
     groups = {}         # grey signature -> photo indices, in order of first appearance
@@ -202,26 +208,32 @@ def _sweep_stored(filter_type, pairs, comps, images, sources, grey_sources, guid
         else:       # the source guides itself
             joints, grey_as_bgr = srcs, grey
         res = whdr.sweep(filter_type, srcs, joints, [comps[i] for i in idx], pairs, delta,
-                         grey_as_bgr=grey_as_bgr, iterations=iterations)
+                         grey_as_bgr=grey_as_bgr, iterations=iterations, **coded)
         out[:, :, idx] = res if iterations > 1 else res[None]
     return out
 
 
 def run(photos, filter_type, sigma_color, sigma_spatial, guidance="cnn", delta=0.1, src_files=None,
-        guidance_files=None, iterations=1, png_decoder="host"):
+        guidance_files=None, iterations=1, png_decoder="host", src_coding="linear"):
     """The sweep over a list of photo files: returns (pairs [P,2], per_image float64 [P,N],
     has_judgements bool [N]); with iterations = K > 1 per_image is [K,P,N], slice k the WHDR after
     pass k + 1 of the chain (whdr.sweep).  src_files: a pattern (file_for) naming the stored
     reflectance of every photo, filtered instead of the CNN's prediction - the network is not
     called.  guidance_files: a pattern naming the image that guides, as it is read (three channels);
     it overrides `guidance`.  With src_files and guidance "cnn" the source guides itself.
-    png_decoder: "host" or "device" (load)."""
+    png_decoder: "host" or "device" (load).  src_coding: "linear" or "srgb", what a byte of a stored
+    source stands for when a pass is scored (whdr.value_table); the filters see the stored bytes
+    either way.  "srgb" needs src_files: the CNN's own prediction is linear."""
     import torch
     from . import ops, whdr
     pairs = grid_pairs(sigma_color, sigma_spatial)
     iterations = int(iterations)
     if iterations < 1:
         raise ValueError("iterations must be >= 1")
+    if src_coding not in SRC_CODINGS:
+        raise ValueError("src_coding must be one of %s" % ", ".join(SRC_CODINGS))
+    if src_coding != "linear" and not src_files:
+        raise ValueError("src_coding %r needs src_files: the CNN's prediction is linear" % src_coding)
     photos = list(photos)
     need_photos = not src_files or (not guidance_files and guidance == "image")
     images, sources, guides, judgements, grey_sources = load(photos, src_files, guidance_files,
@@ -230,8 +242,9 @@ def run(photos, filter_type, sigma_color, sigma_spatial, guidance="cnn", delta=0
     comps = [whdr.to_pixels(j, h, w) for j, (h, w) in zip(judgements, sizes)]
     has = np.array([c.shape[0] > 0 for c in comps], dtype=bool)
     if sources is not None:
+        coded = {} if src_coding == "linear" else {"values": whdr.value_table(src_coding)}
         per_image = _sweep_stored(filter_type, pairs, comps, images, sources, grey_sources, guides,
-                                  guidance, delta, iterations)
+                                  guidance, delta, iterations, **coded)
         return pairs, (per_image if iterations > 1 else per_image[0]), has
     # The network is per pixel, so the photos of a pack - whatever their sizes - go through it as
     # one image [1, 1, total pixels, 3], and the filters take the packed bytes as they come out.
@@ -297,6 +310,36 @@ def build_parser():
     return p
 
 
+def report(filter_type, guidance, delta, sigma_color, sigma_spatial, pairs, per_image, has,
+           iterations=1, src_files=None, guidance_files=None):
+    """What the tool writes about a run(): the JSON dictionary and the line it prints."""
+    def best_of(mean, best):
+        return {"sigma_color": float(pairs[best, 0]), "sigma_spatial": float(pairs[best, 1]),
+                "mean_whdr": float(mean[best])}
+
+    # a chain reports every pass; the keys of a single pass then hold the last one, the chain's result
+    passes = [summarise(pairs, m, has) for m in (per_image if iterations > 1 else [per_image])]
+    mean, best = passes[-1]
+    result = {
+        "filter_type": filter_type, "guidance": guidance, "delta": delta,
+        "sigma_color": sigma_color, "sigma_spatial": sigma_spatial,
+        "pairs": pairs.tolist(), "mean_whdr": mean.tolist(),
+        "best": best_of(mean, best),
+        "images": len(has), "images_with_judgements": int(has.sum()),
+    }
+    if iterations > 1:
+        result["iterations"] = iterations
+        result["passes"] = [{"pass": k + 1, "mean_whdr": m.tolist(), "best": best_of(m, b)}
+                            for k, (m, b) in enumerate(passes)]
+    if src_files:
+        result["src_files"] = src_files
+    if guidance_files:
+        result["guidance_files"] = guidance_files
+    line = ("best: sigma_color %g sigma_spatial %g mean WHDR %.6f over %d image(s)"
+            % (pairs[best, 0], pairs[best, 1], mean[best], int(has.sum())))
+    return result, line
+
+
 def main(argv=None):
     args = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
     from .batch import expand_inputs
@@ -307,36 +350,15 @@ def main(argv=None):
                                 args.guidance, args.delta, src_files=args.src_files,
                                 guidance_files=args.guidance_files, iterations=args.iterations,
                                 png_decoder=args.png_decoder)
-
-    def best_of(mean, best):
-        return {"sigma_color": float(pairs[best, 0]), "sigma_spatial": float(pairs[best, 1]),
-                "mean_whdr": float(mean[best])}
-
-    # a chain reports every pass; the keys of a single pass then hold the last one, the chain's result
-    passes = [summarise(pairs, m, has) for m in (per_image if args.iterations > 1 else [per_image])]
-    mean, best = passes[-1]
-    result = {
-        "filter_type": args.filter_type, "guidance": args.guidance, "delta": args.delta,
-        "sigma_color": args.sigma_color, "sigma_spatial": args.sigma_spatial,
-        "pairs": pairs.tolist(), "mean_whdr": mean.tolist(),
-        "best": best_of(mean, best),
-        "images": len(photos), "images_with_judgements": int(has.sum()),
-    }
-    if args.iterations > 1:
-        result["iterations"] = args.iterations
-        result["passes"] = [{"pass": k + 1, "mean_whdr": m.tolist(), "best": best_of(m, b)}
-                            for k, (m, b) in enumerate(passes)]
-    if args.src_files:
-        result["src_files"] = args.src_files
-    if args.guidance_files:
-        result["guidance_files"] = args.guidance_files
+    result, line = report(args.filter_type, args.guidance, args.delta, args.sigma_color,
+                          args.sigma_spatial, pairs, per_image, has, args.iterations, args.src_files,
+                          args.guidance_files)
     with open(args.out, "w") as fh:
         json.dump(result, fh, indent=1)
     if args.per_image:
         np.savez(args.per_image, whdr=per_image, pairs=pairs, has_judgements=has,
                  files=np.array(photos))
-    print("best: sigma_color %g sigma_spatial %g mean WHDR %.6f over %d image(s)"
-          % (pairs[best, 0], pairs[best, 1], mean[best], int(has.sum())))
+    print(line)
     return 0
 
 

@@ -180,13 +180,11 @@ def dedup_points(comparisons_px, height, width):
             comp_offsets.astype(np.int32))
 
 
-def whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta=0.1):
-    """WHDR of uint8 predictions sampled at points (rf_whdr_points_u8): samples is CUDA uint8
-    [S, total, C] (C = 1 or 3; e.g. ops.joint_bilateral_points_u8's output), the other arrays as
-    dedup_points returns them.  Each byte counts as float32(byte) / 255; returns float64 [S, n]
-    (host), equal bit for bit to whdr_batch on the float32 images bytes / 255."""
-    torch = _ffi.require_gpu()
-    lib = _ffi.load_library()
+def _check_point_arrays(torch, samples, point_offsets, comps, weights, comp_offsets):
+    """The checks of whdr_points_u8 and whdr_points_values_u8, before any device work: samples is a
+    contiguous CUDA uint8 [S, total, C] with C of 1 or 3, the arrays agree with each other, and every
+    comparison index stays inside its image's points (the device entries cannot check that).
+    Returns (point_offsets int64, comps int64 [m,3], weights float64, comp_offsets int64)."""
     if not (torch.is_tensor(samples) and samples.is_cuda and samples.dtype == torch.uint8
             and samples.is_contiguous() and samples.dim() == 3):
         raise ValueError("samples must be a contiguous CUDA uint8 tensor [S, total, C]")
@@ -201,12 +199,25 @@ def whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta=0
     if n < 0 or point_offsets.shape[0] < n or comps.shape[0] != weights.shape[0] \
             or comp_offsets[-1] != comps.shape[0]:
         raise ValueError("inconsistent point / comparison arrays")
-    # indices must stay inside their image's points (the device entry cannot check them)
     for i in range(n):
         k0, k1 = comp_offsets[i], comp_offsets[i + 1]
         size = (point_offsets[i + 1] if i + 1 < point_offsets.shape[0] else total) - point_offsets[i]
         if k1 > k0 and (comps[k0:k1, :2].min() < 0 or comps[k0:k1, :2].max() >= size):
             raise IndexError("comparison index outside the points of image %d" % i)
+    return point_offsets, comps, weights, comp_offsets
+
+
+def whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta=0.1):
+    """WHDR of uint8 predictions sampled at points (rf_whdr_points_u8): samples is CUDA uint8
+    [S, total, C] (C = 1 or 3; e.g. ops.joint_bilateral_points_u8's output), the other arrays as
+    dedup_points returns them.  Each byte counts as float32(byte) / 255; returns float64 [S, n]
+    (host), equal bit for bit to whdr_batch on the float32 images bytes / 255."""
+    torch = _ffi.require_gpu()
+    lib = _ffi.load_library()
+    point_offsets, comps, weights, comp_offsets = _check_point_arrays(
+        torch, samples, point_offsets, comps, weights, comp_offsets)
+    n_sets, total, c = samples.shape
+    n = comp_offsets.shape[0] - 1
     out = np.zeros((n_sets, n), dtype=np.float64)
     if n == 0 or n_sets == 0 or total == 0 or comps.shape[0] == 0:
         return out
@@ -222,11 +233,124 @@ def whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta=0
     return d_out.cpu().numpy().reshape(n_sets, n)
 
 
+CODINGS = ("linear", "srgb")
+
+
+def value_table(coding):
+    """float32[256]: the value a stored byte stands for when a result is scored.  "linear" is
+    byte / 255 in float32 (what whdr_points_u8 computes), "srgb" image_utils.srgb_byte_lut() (a
+    result saved as sRGB, the reference's load_image(..., is_srgb=True)); a caller's own float32[256]
+    array is taken as it is.  Anything else - another name, shape or dtype, a non-finite entry -
+    is a ValueError."""
+    if isinstance(coding, str):
+        if coding == "linear":
+            return np.arange(256, dtype=np.float32) / np.float32(255)
+        if coding == "srgb":
+            from .image_utils import srgb_byte_lut
+            return srgb_byte_lut()
+        raise ValueError("coding must be one of %s or a float32[256] array (got %r)"
+                         % (", ".join(CODINGS), coding))
+    if not (isinstance(coding, np.ndarray) and coding.dtype == np.float32 and coding.shape == (256,)):
+        raise ValueError("a value table is a float32 array of shape (256,)")
+    if not np.isfinite(coding).all():
+        raise ValueError("a value table holds finite values only")
+    return coding
+
+
+# bytes of float32 values staged by one rf_whdr_f32 call of whdr_points_values_u8, and the images one
+# launch of it accepts (one 64-lane workgroup per image, below 2^32 work-items)
+WHDR_VALUES_BYTES = 1 << 28
+WHDR_VALUES_IMAGES = (1 << 26) - 1
+
+
+def plan_value_chunks(counts, n_sets, channels):
+    """The rf_whdr_f32 calls of whdr_points_values_u8: counts[i] = distinct referenced points of
+    image i.  Returns [(i0, i1, s0, s1)]: images i0..i1-1 of sets s0..s1-1 as (s1 - s0) * (i1 - i0)
+    rows of channels * max(counts[i0:i1]) floats.  Images are taken in order while all sets of them
+    stay under WHDR_VALUES_BYTES and WHDR_VALUES_IMAGES rows; an image that alone exceeds either has
+    its sets cut (one set of one image over the byte limit is a call of its own).  Host only."""
+    counts = [int(k) for k in counts]
+    chunks, i0 = [], 0
+
+    def fits(rows, width):
+        return rows <= WHDR_VALUES_IMAGES and rows * channels * max(1, width) * 4 <= WHDR_VALUES_BYTES
+
+    while i0 < len(counts):
+        i1, width = i0 + 1, counts[i0]
+        while i1 < len(counts) and fits(n_sets * (i1 + 1 - i0), max(width, counts[i1])):
+            width = max(width, counts[i1])
+            i1 += 1
+        per = n_sets
+        while per > 1 and not fits(per * (i1 - i0), width):
+            per = (per + 1) // 2
+        chunks.extend((i0, i1, s0, min(s0 + per, n_sets)) for s0 in range(0, n_sets, per))
+        i0 = i1
+    return chunks
+
+
+def whdr_points_values_u8(samples, point_offsets, comps, weights, comp_offsets, values, delta=0.1):
+    """whdr_points_u8 with a value table: each byte counts as values[byte] (value_table).  Arguments,
+    checks and result are whdr_points_u8's; the value for set s, image i equals host `whdr` on the
+    float32 image values[bytes] (planar), bit for bit - with the "linear" table whdr_points_u8's value.
+
+    rf_whdr_points_u8 has no table argument, so the bytes go through the float entry: the points
+    that the comparisons reference are gathered (device work per distinct referenced point, whatever
+    `total` is - a guided sweep passes whole images), looked up in the table on the device, laid out
+    per (set, image) as a [C, 1, Pmax] float32 image padded to the call's largest point count, and
+    scored by whdr_batch (rf_whdr_f32) with comparisons (index 1, 0, index 2, 0, darker, weight).
+    plan_value_chunks cuts the call so that the floats stay under WHDR_VALUES_BYTES."""
+    torch = _ffi.require_gpu()
+    table = value_table(values)
+    point_offsets, comps, weights, comp_offsets = _check_point_arrays(
+        torch, samples, point_offsets, comps, weights, comp_offsets)
+    n_sets, total, c = samples.shape
+    n = comp_offsets.shape[0] - 1
+    out = np.zeros((n_sets, n), dtype=np.float64)
+    if n == 0 or n_sets == 0 or total == 0 or comps.shape[0] == 0:
+        return out
+    # distinct referenced points per image: keys sort by image, then by the point's place in a set
+    image = np.repeat(np.arange(n, dtype=np.int64), np.diff(comp_offsets))
+    place = point_offsets[image][:, None] + comps[:, :2]
+    if place.min() < 0 or place.max() >= total:
+        raise IndexError("comparison index outside the samples")
+    keys, inverse = np.unique(image[:, None] * total + place, return_inverse=True)
+    first = np.searchsorted(keys, np.arange(n + 1, dtype=np.int64) * total)
+    local = inverse.reshape(-1, 2) - first[image][:, None]
+    counts = np.diff(first)
+    rows = np.zeros((comps.shape[0], 6), dtype=np.float64)
+    rows[:, 0], rows[:, 2], rows[:, 4], rows[:, 5] = local[:, 0], local[:, 1], comps[:, 2], weights
+    chunks = plan_value_chunks(counts, n_sets, c)
+    # a call's comparisons are repeated per set behind rf_whdr_f32's int32 offsets
+    if any((s1 - s0) * (comp_offsets[i1] - comp_offsets[i0]) >= 2 ** 31 for i0, i1, s0, s1 in chunks):
+        raise ValueError("too many comparisons")
+    d_table = torch.from_numpy(table).to(samples.device)
+    for i0, i1, s0, s1 in chunks:
+        if comp_offsets[i1] == comp_offsets[i0]:
+            continue
+        width = int(counts[i0:i1].max())
+        gather = np.zeros((i1 - i0, width), dtype=np.int64)     # padding reads the set's first sample
+        for i in range(i0, i1):
+            gather[i - i0, :counts[i]] = keys[first[i]:first[i + 1]] - i * total
+        picked = samples[s0:s1].index_select(1, _index(gather.ravel(), samples))
+        planar = picked.view(s1 - s0, i1 - i0, width, c).permute(0, 1, 3, 2).contiguous()
+        floats = d_table.index_select(0, planar.view(-1).int()).view(-1, c, 1, width)
+        per_image =[rows[comp_offsets[i]:comp_offsets[i + 1]] for i in range(i0, i1)]
+        out[s0:s1, i0:i1] = whdr_batch(floats, per_image * (s1 - s0), delta).reshape(s1 - s0, i1 - i0)
+    return out
+
+
+def _score(samples, point_offsets, comps, weights, comp_offsets, delta, values):
+    """The WHDR call of a sweep: whdr_points_u8 as ever, whdr_points_values_u8 with a value table."""
+    if values is None:
+        return whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta)
+    return whdr_points_values_u8(samples, point_offsets, comps, weights, comp_offsets, values, delta)
+
+
 # bytes of filtered images held at once by the guided half of a sweep (one group of pairs)
 SWEEP_GUIDED_BYTES = 1 << 30
 
 
-def _sweep_batch(filter_type, src, joint, comparisons_px, pairs, delta, grey_as_bgr):
+def _sweep_batch(filter_type, src, joint, comparisons_px, pairs, delta, grey_as_bgr, values=None):
     """sweep() on one device batch of equal-size images: float64 [P, N]."""
     import torch
     from . import ops
@@ -238,7 +362,7 @@ def _sweep_batch(filter_type, src, joint, comparisons_px, pairs, delta, grey_as_
     if filter_type == "bilateral":
         samples = ops.joint_bilateral_points_u8(joint, src, pts, point_offsets, pairs, d=-1,
                                                 grey_as_bgr=grey_as_bgr)
-        return whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta)
+        return _score(samples, point_offsets, comps, weights, comp_offsets, delta, values)
     # guided: full passes (its window sums are sequential chains by contract, a point cannot be
     # evaluated on its own); the whole images are the point lists: pixel index y * w + x
     npx = h * w
@@ -257,9 +381,9 @@ def _sweep_batch(filter_type, src, joint, comparisons_px, pairs, delta, grey_as_
         for j, (sc, ss) in enumerate(chunk):
             ops.guided_filter_u8(joint, src, int(ss), float(sc), out=filtered[j],
                                  grey_as_bgr=grey_as_bgr)
-        out[p0:p0 + chunk.shape[0]] = whdr_points_u8(
+        out[p0:p0 + chunk.shape[0]] = _score(
             filtered.view(chunk.shape[0], n * npx, c), image_offsets, px_comps, weights,
-            comp_offsets, delta)
+            comp_offsets, delta, values)
     return out
 
 
@@ -310,7 +434,7 @@ def plan_packs(keys, pixels, points, n_pairs, src_cn):
     return packs
 
 
-def sweep_packed(src, joint, sizes, dedup, pairs, delta=0.1, grey_as_bgr=False):
+def sweep_packed(src, joint, sizes, dedup, pairs, delta=0.1, grey_as_bgr=False, values=None):
     """The bilateral sweep on one pack: images of sizes[i] = (h_i, w_i) packed one after another in
     the CUDA uint8 tensors src / joint [total pixels, C], dedup = dedup_points_ragged of their
     comparisons.  One ragged filter call and one WHDR call: float64 [P, n]."""
@@ -320,10 +444,10 @@ def sweep_packed(src, joint, sizes, dedup, pairs, delta=0.1, grey_as_bgr=False):
         return np.zeros((np.asarray(pairs).reshape(-1, 2).shape[0], len(sizes)), dtype=np.float64)
     samples = ops.joint_bilateral_points_ragged_u8(joint, src, pts, point_offsets, pairs, d=-1,
                                                    grey_as_bgr=grey_as_bgr, sizes=sizes)
-    return whdr_points_u8(samples, point_offsets, comps, weights, comp_offsets, delta)
+    return _score(samples, point_offsets, comps, weights, comp_offsets, delta, values)
 
 
-def sweep_guided_packed(src, joint, sizes, dedup, pairs, delta=0.1, grey_as_bgr=False):
+def sweep_guided_packed(src, joint, sizes, dedup, pairs, delta=0.1, grey_as_bgr=False, values=None):
     """The guided sweep on one pack: one-channel images of sizes[i] = (h_i, w_i) packed one after
     another in the CUDA uint8 tensors src [total pixels, 1] / joint [total pixels, C], dedup =
     dedup_points_ragged of their comparisons.  Pairs are
@@ -358,7 +482,7 @@ def sweep_guided_packed(src, joint, sizes, dedup, pairs, delta=0.1, grey_as_bgr=
             chunk = eps[e0:e0 + per]
             filtered = ops.guided_filter_ragged_sweep_u8(joint, src, radius, chunk,
                                                          grey_as_bgr=grey_as_bgr, sizes=sizes)
-            res = whdr_points_u8(filtered, image_offsets, px_comps, weights, comp_offsets, delta)
+            res = _score(filtered, image_offsets, px_comps, weights, comp_offsets, delta, values)
             for j, e in enumerate(chunk):
                 out[rows[e]] = res[j]
     return out
@@ -412,7 +536,7 @@ def _pixel_comps(dedup, pixels):
     return px
 
 
-def _chain_guided(src, sizes, dedup, pairs, iterations, delta, one_pass):
+def _chain_guided(src, sizes, dedup, pairs, iterations, delta, one_pass, values=None):
     """The guided chain on images that lie one after another in `src` (a packed list [total pixels,
     C], or a batch [N,H,W,C] with sizes = N x (H, W)): float64 [K, P, n].  Pairs are grouped by radius
     and equal (radius, eps) pairs computed once, as in sweep_guided_packed;
@@ -439,14 +563,15 @@ def _chain_guided(src, sizes, dedup, pairs, iterations, delta, one_pass):
             for k in range(iterations):
                 filtered = _empty((len(chunk),) + shape, src)
                 cur = [one_pass(cur[j], radius, e, filtered[j]) for j, e in enumerate(chunk)]
-                res = whdr_points_u8(filtered.view(len(chunk), -1, shape[-1]), image_offsets,
-                                     px_comps, weights, comp_offsets, delta)
+                res = _score(filtered.view(len(chunk), -1, shape[-1]), image_offsets, px_comps,
+                             weights, comp_offsets, delta, values)
                 for j, e in enumerate(chunk):
                     out[k, rows[e]] = res[j]
     return out
 
 
-def _chain_bilateral(src, sizes, dedup, pairs, iterations, delta, full_pass, point_pass):
+def _chain_bilateral(src, sizes, dedup, pairs, iterations, delta, full_pass, point_pass,
+                     values=None):
     """The bilateral chain on images that lie one after another in `src` (as in _chain_guided):
     float64 [K, P, n].  full_pass(cur, sigma_color, sigma_space, out) filters cur into out and returns
     the result; point_pass(cur, sigma_color, sigma_space) evaluates one more pass at the deduplicated
@@ -471,15 +596,16 @@ def _chain_bilateral(src, sizes, dedup, pairs, iterations, delta, full_pass, poi
         cur = [src] * len(group)
         for k in range(iterations - 1):
             cur = [full_pass(cur[g], sc, ss, bufs[g, k % 2]) for g, (sc, ss) in enumerate(group)]
-            out[k, rows] = whdr_points_u8(_sample(cur, index), point_offsets, comps, weights,
-                                          comp_offsets, delta)
+            out[k, rows] = _score(_sample(cur, index), point_offsets, comps, weights, comp_offsets,
+                                  delta, values)
         last = _cat(point_pass(cur[g], sc, ss) for g, (sc, ss) in enumerate(group))
-        out[iterations - 1, rows] = whdr_points_u8(last, point_offsets, comps, weights, comp_offsets,
-                                                   delta)
+        out[iterations - 1, rows] = _score(last, point_offsets, comps, weights, comp_offsets, delta,
+                                           values)
     return out
 
 
-def chain_packed(src, joint, sizes, dedup, pairs, iterations, delta=0.1, grey_as_bgr=False):
+def chain_packed(src, joint, sizes, dedup, pairs, iterations, delta=0.1, grey_as_bgr=False,
+                 values=None):
     """sweep_packed for a chain of `iterations` >= 2 passes with the joint held fixed: float64
     [K, P, n], slice k the WHDR after pass k + 1.  Per pair K - 1 full ragged passes
     (ops.joint_bilateral_ragged_u8, the uint8 result of one the src of the next) and one point pass
@@ -491,10 +617,12 @@ def chain_packed(src, joint, sizes, dedup, pairs, iterations, delta=0.1, grey_as
         lambda cur, sc, ss, out: ops.joint_bilateral_ragged_u8(
             joint, cur, -1, sc, ss, grey_as_bgr=grey_as_bgr, sizes=sizes, out=out)[0],
         lambda cur, sc, ss: ops.joint_bilateral_points_ragged_u8(
-            joint, cur, dedup[0], dedup[1], [(sc, ss)], d=-1, grey_as_bgr=grey_as_bgr, sizes=sizes))
+            joint, cur, dedup[0], dedup[1], [(sc, ss)], d=-1, grey_as_bgr=grey_as_bgr, sizes=sizes),
+        values=values)
 
 
-def chain_guided_packed(src, joint, sizes, dedup, pairs, iterations, delta=0.1, grey_as_bgr=False):
+def chain_guided_packed(src, joint, sizes, dedup, pairs, iterations, delta=0.1, grey_as_bgr=False,
+                        values=None):
     """sweep_guided_packed for a chain of `iterations` >= 2 passes with the guide held fixed: float64
     [K, P, n], slice k the WHDR after pass k + 1.  Per distinct (radius, eps) one
     ops.guided_filter_ragged_u8 call per pass, the packed result of one the src of the next."""
@@ -503,10 +631,12 @@ def chain_guided_packed(src, joint, sizes, dedup, pairs, iterations, delta=0.1, 
     return _chain_guided(
         src, sizes, dedup, pairs, iterations, delta,
         lambda cur, radius, eps, out: ops.guided_filter_ragged_u8(
-            joint, cur, radius, eps, iterations=1, grey_as_bgr=grey_as_bgr, sizes=sizes, out=out)[0])
+            joint, cur, radius, eps, iterations=1, grey_as_bgr=grey_as_bgr, sizes=sizes, out=out)[0],
+        values=values)
 
 
-def _chain_batch(filter_type, src, joint, comparisons_px, pairs, iterations, delta, grey_as_bgr):
+def _chain_batch(filter_type, src, joint, comparisons_px, pairs, iterations, delta, grey_as_bgr,
+                 values=None):
     """The chain on one device batch of equal-size images, through the uniform ops: float64
     [K, P, N]."""
     from . import ops
@@ -520,11 +650,13 @@ def _chain_batch(filter_type, src, joint, comparisons_px, pairs, iterations, del
                                                             grey_as_bgr=grey_as_bgr),
             lambda cur, sc, ss: ops.joint_bilateral_points_u8(joint, cur, dedup[0], dedup[1],
                                                               [(sc, ss)], d=-1,
-                                                              grey_as_bgr=grey_as_bgr))
+                                                              grey_as_bgr=grey_as_bgr),
+            values=values)
     return _chain_guided(
         src, sizes, dedup, pairs, iterations, delta,
         lambda cur, radius, eps, out: ops.guided_filter_u8(joint, cur, radius, eps, out=out,
-                                                           grey_as_bgr=grey_as_bgr))
+                                                           grey_as_bgr=grey_as_bgr),
+        values=values)
 
 
 def _as3(image):
@@ -552,7 +684,7 @@ def _stack(images):
 
 
 def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_as_bgr=False,
-          iterations=1):
+          iterations=1, values=None):
     """WHDR of filter(joint, src) for every (sigma_color, sigma_space) pair: float64 [P, N] on the
     host, row p = pair p, column i = image i in the caller's order.
 
@@ -582,7 +714,11 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
                    (ops.guided_filter_ragged_sweep_u8 per pack and radius; equal pairs are computed
                    once; the same bytes).  Any other list, and any other pair, batches the images of equal
                    shapes wherever they stand in the list.
-    Each result equals whdr_batch on the filtered bytes as float32 / 255 (planar), bit for bit."""
+    Each result equals whdr_batch on the filtered bytes as float32 / 255 (planar), bit for bit.
+
+    values: a value table (value_table: "linear", "srgb" or a float32[256] array).  The filters see the
+    bytes as ever; every pass is then scored by whdr_points_values_u8, each filtered byte counting as
+    values[byte] - a stored result that is sRGB-coded.  None scores through whdr_points_u8."""
     from . import filter_reflectance as fr
     from .batch import group_by_shape
     import torch
@@ -595,6 +731,8 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
     if iterations < 1:
         raise ValueError("iterations must be >= 1")
     chain = iterations > 1
+    # the linear path makes its calls without the keyword
+    coded = {} if values is None else {"values": value_table(values)}
     if torch.is_tensor(src):
         if not torch.is_tensor(joint) or src.dim() != 4:
             raise ValueError("src and joint must both be CUDA batches [N,H,W,C] or both lists")
@@ -603,8 +741,8 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
         _ffi.require_gpu()
         if chain:
             return _chain_batch(filter_type, src, joint, comparisons_px, pairs, iterations, delta,
-                                grey_as_bgr)
-        return _sweep_batch(filter_type, src, joint, comparisons_px, pairs, delta, grey_as_bgr)
+                                grey_as_bgr, **coded)
+        return _sweep_batch(filter_type, src, joint, comparisons_px, pairs, delta, grey_as_bgr, **coded)
     src, joint = list(src), list(joint)
     if len(src) != len(joint) or len(src) != len(comparisons_px):
         raise ValueError("src, joint and comparisons_px must have one entry per image")
@@ -637,8 +775,8 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
             j_p = s_p if all(joint[i] is src[i] for i in pack) else \
                 _pack_list([joint[i] for i in pack], torch)
             out[:, :, pack] = chain_packed(s_p, j_p, psizes, pdedup, pairs, iterations, delta,
-                                           grey_as_bgr) if chain else \
-                sweep_packed(s_p, j_p, psizes, pdedup, pairs, delta, grey_as_bgr)[None]
+                                           grey_as_bgr, **coded) if chain else \
+                sweep_packed(s_p, j_p, psizes, pdedup, pairs, delta, grey_as_bgr, **coded)[None]
         return out if chain else out[0]
     # guided, a one-channel device list of more than one shape (the conditions of
     # filter_reflectance.apply_filter_list's ragged route): the pairs whose radius the ragged guided
@@ -661,8 +799,9 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
             psizes = [sizes[i] for i in pack]
             out[(slice(None),) + np.ix_(rows, pack)] = \
                 chain_guided_packed(s_p, j_p, psizes, pdedup, pairs[rows], iterations, delta,
-                                    grey_as_bgr) if chain else \
-                sweep_guided_packed(s_p, j_p, psizes, pdedup, pairs[rows], delta, grey_as_bgr)[None]
+                                    grey_as_bgr, **coded) if chain else \
+                sweep_guided_packed(s_p, j_p, psizes, pdedup, pairs[rows], delta, grey_as_bgr,
+                                    **coded)[None]
         rest = [p for p in range(pairs.shape[0]) if p not in rows]
         if not rest:
             return out if chain else out[0]
@@ -679,6 +818,47 @@ def sweep(filter_type, src, joint, comparisons_px, sigma_pairs, delta=0.1, grey_
         run_comps = [comparisons_px[i] for i in run]
         out[(slice(None),) + np.ix_(rest, run)] = \
             _chain_batch(filter_type, s_b, j_b, run_comps, pairs[rest], iterations, delta,
-                         grey_as_bgr) if chain else \
-            _sweep_batch(filter_type, s_b, j_b, run_comps, pairs[rest], delta, grey_as_bgr)[None]
+                         grey_as_bgr, **coded) if chain else \
+            _sweep_batch(filter_type, s_b, j_b, run_comps, pairs[rest], delta, grey_as_bgr,
+                         **coded)[None]
     return out if chain else out[0]
+
+
+def score_list(images, comparisons_px, coding="linear", delta=0.1):
+    """WHDR of stored uint8 results as they are, no filter applied: float64 [N] on the host, the
+    baseline row of a sweep.  images: N uint8 images (CUDA tensors or numpy arrays, [H,W] or [H,W,C]
+    with C of 1 or 3, taken as given) that may differ in size; comparisons_px: N arrays [n_i,6] in
+    pixel coordinates.  coding: what a byte stands for (value_table).  Points are deduplicated and
+    checked with each image's own size and the images packed by channel count as `sweep` packs a
+    list; a pack is scored with its packed pixels as the point lists.  An image without judgements
+    scores 0.0.  Each value equals host `whdr` on the float32 image values[bytes] (planar)."""
+    import torch
+    values = None if isinstance(coding, str) and coding == "linear" else value_table(coding)
+    images = list(images)
+    if len(images) != len(comparisons_px):
+        raise ValueError("images and comparisons_px must have one entry per image")
+    shapes = [tuple(im.shape) for im in images]
+    for i, (im, shape) in enumerate(zip(images, shapes)):
+        is_u8 = im.dtype == torch.uint8 if torch.is_tensor(im) else np.asarray(im).dtype == np.uint8
+        if not is_u8 or len(shape) not in (2, 3):
+            raise ValueError("image %d is not a uint8 image [H,W] or [H,W,C]" % i)
+        if (shape + (1,))[2] not in (1, 3):
+            raise Exception("Expecting 1 or 3 channels to compute lightness!")
+    dedup = [dedup_points([comp], shape[0], shape[1]) for comp, shape in zip(comparisons_px, shapes)]
+    out = np.zeros(len(images), dtype=np.float64)
+    if not images:
+        return out
+    _ffi.require_gpu()
+    keys = [(shape + (1,))[2] for shape in shapes]
+    sizes = [shape[:2] for shape in shapes]
+    for pack in plan_packs(keys, [h * w for h, w in sizes], [int(d[1][-1]) for d in dedup], 1,
+                           lambda k: k):
+        pdedup = join_dedup([dedup[i] for i in pack])
+        if pdedup[2].shape[0] == 0:
+            continue
+        psizes = [sizes[i] for i in pack]
+        packed = _pack_list([images[i] for i in pack], torch)
+        image_offsets, pixels = _point_pixels(pdedup, psizes)
+        out[pack] = _score(packed.view(1, -1, packed.shape[-1]), image_offsets,
+                           _pixel_comps(pdedup, pixels), pdedup[3], pdedup[4], delta, values)[0]
+    return out
