@@ -1,5 +1,6 @@
 // rf_gf_fused.hpp -- fused stage 2 of the guided filter (box means of the alpha/beta planes) for
-// any radius, gfx950.  Included by rf_gf.hip (shared helpers) and by the rf_gf_fused_*.hip units
+// any radius, gfx950.  Included by rf_gf.hip and rf_gf_f32.hip (shared helpers, through
+// rf_gf_algebra.hpp / rf_gf_twokernel.hpp) and by the rf_gf_fused_*.o units (rf_gf_fused_inst.hip)
 // that instantiate the kernels per radius.
 //
 // Contract (opencv/modules/imgproc/src/smooth.cpp boxFilter on CV_32F planes, called 12 times by
@@ -48,7 +49,7 @@ constexpr int kGsFloatsPublic = 9;  // floats per pixel of the guide record kept
 // because M < 2^(Emax - 126) and e = Emin - 150.
 //
 // For such rows stage 2 needs no row walk: stage 1 leaves the sum of every aligned 16-column block
-// (xf, see rf_gf.hip), and the column walk rebuilds the row sum at its block's first column 16 b as
+// (xf, see GfExactOut in rf_gf_stage1.hpp), and the column walk rebuilds the row sum at its block's first column 16 b as
 //     prefix of block b + q up to column 16 b + R   (= F[b + q] - the c0' entering operands behind it)
 //   + F[b - q] + ... + F[b + q - 1]                  (block indices reflected like columns)
 //   + suffix of block b - q - 1 from column 16 b - R (= its first c0 leaving operands)

@@ -3,8 +3,8 @@
 // or - with -DRF_GF_LARGE - for r = kGfFusedSmallMax + 1 + RF_GF_PART, + RF_GF_PARTS, ... <=
 // kGfFusedMaxRadius (rf_gf_fused_L<part>.o: the large radii, whose unrolled bodies take a third of
 // the compile time at -O1 and lose nothing - their registers are spoken for either way).  The
-// Makefile compiles this file once per part so that the per-radius kernels build in parallel; rf_gf.hip
-// asks the parts for a radius's launcher (gf_fused_launcher).
+// Makefile compiles this file once per part so that the per-radius kernels build in parallel;
+// gf_fused_launcher (rf_gf.hip) asks the parts for a radius's launcher.
 #include "rf_gf_fused.hpp"
 
 #ifndef RF_GF_PART

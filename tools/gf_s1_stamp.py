@@ -31,9 +31,10 @@ def build():
     flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-gpu-rdc",
              "-fno-slp-vectorize", "-DRF_GF_S1_STAMP=1", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-c", os.path.join(CSRC, "rf_gf.hip"), "-o", obj])
-    objs = [os.path.join(CSRC, o) for o in ["rf_api.o", "rf_jbf.o", "rf_jbf_tables.o", "rf_jbf_f32.o", "rf_cnn.o",
+    objs = [os.path.join(CSRC, o) for o in ["rf_api.o", "rf_jbf.o", "rf_jbf_greymap.o", "rf_jbf_tables.o",
+                                              "rf_jbf_f32.o", "rf_gf_f32.o", "rf_gf_side.o", "rf_cnn.o",
                                               "rf_colorize.o", "rf_whdr.o"]
-            + ["rf_gf_fused_%d.o" % k for k in range(8)]]
+            + ["rf_gf_fused_%d.o" % k for k in range(8)] + ["rf_gf_fused_L%d.o" % k for k in range(4)]]
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, obj] + objs)
     os.remove(obj)
     print("built", LIB)

@@ -47,8 +47,9 @@ flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=o
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 flags += os.environ.get("RF_STAMP_DEFS", "").split()   # experiment switches of rf_gf_fused.hpp
 subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-c", path, "-o", obj])
-objs = [os.path.join(CSRC, o) for o in ("rf_api.o", "rf_jbf.o", "rf_jbf_tables.o", "rf_jbf_f32.o",
-                                        "rf_gf.o", "rf_cnn.o", "rf_colorize.o", "rf_whdr.o")]
+objs = [os.path.join(CSRC, o) for o in ("rf_api.o", "rf_jbf.o", "rf_jbf_greymap.o", "rf_jbf_tables.o", "rf_jbf_f32.o",
+                                        "rf_gf.o", "rf_gf_f32.o", "rf_gf_side.o", "rf_cnn.o", "rf_colorize.o",
+                                        "rf_whdr.o")]
 out = os.path.join(ROOT, "reflectance_filtering_amd",
                    "librf_hip.so.stamp" + os.environ.get("RF_STAMP_SUFFIX", ""))
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out,
