@@ -43,6 +43,26 @@
  *     rf_jbf_u8, packed-weight slots of the CNN: 16 each) may be used from more streams than are kept:
  *     a further stream is served by a recycled idle entry or by a route that needs none.
  *
+ * Graphs (held for every entry by tests/test_gpu_capture_contract.py: one call captured on a side stream in
+ * the default capture mode, after a warm eager call on that stream, and replayed over changed inputs and a
+ * dirty workspace):
+ *   - on a stream that is being captured into a graph every entry does one of two things.  Capturable:
+ *     rf_jbf_u8, rf_gf_u8, rf_gf_ex_u8, rf_gf_f32, rf_colorize_srgb_u8, rf_whdr_f32, rf_whdr_points_u8,
+ *     rf_cnn_pack_weights and the two rf_cnn_reflectance_packed entries - the call returns RF_OK and none
+ *     of its work runs before a replay.  Refusing: every entry that
+ *     says "SYNCHRONISES THE STREAM", on every route it has, and the raw-weight rf_cnn_reflectance_u8 and
+ *     rf_cnn_reflectance_f32 - the call returns RF_E_UNSUPPORTED before anything is enqueued or written, the
+ *     message names the entry and the capture, and the capture stays valid and the stream usable;
+ *   - a replay reads its buffers - inputs and workspace - as they are at replay time, not as they were at
+ *     the capture; it initialises whatever it reads of the workspace, like an eager call, and writes nothing
+ *     but the call's outputs and its workspace.  The graph holds the addresses of the call's buffers: they
+ *     stay allocated while it can be replayed;
+ *   - a graph also holds addresses of what the library keeps (parameter tables, the vote bytes of its
+ *     capture stream): destroy every graph that captured a library call before rf_shutdown, and those that
+ *     captured rf_jbf_u8 before rf_jbf_release_scratch; replays of graphs that captured rf_jbf_u8 on one
+ *     stream are serialised.  After either call everything is rebuilt on demand, by every
+ *     entry.
+ *
  * Sizes (held by tests/test_gpu_size_contract.py, whose buffers pass 2^31 and 2^32 bytes, and by
  * tests/test_launch_limits_abi.py.  Within 32 GiB per call, one-channel 8-bit buffers pass pixel index 2^32
  * too - those of the colourise entries 2^31, those of rf_gf_ragged_u8 2^30 - and float buffers element
@@ -110,8 +130,10 @@ extern "C" {
 int rf_version(void);
 const char *rf_last_error(void);
 /* Frees what the library holds: the per-device parameter tables (colour LUTs, tap tables), the
-   packed-weight slots of rf_cnn_reflectance_u8 and the guided filter's side streams.  Call it with
-   no library work in flight. */
+   packed-weight slots of rf_cnn_reflectance_u8 and rf_cnn_reflectance_f32, the guided filter's side
+   streams and the scratch of rf_jbf_release_scratch.  Call it with no library work in flight and no
+   captured graph of a library call left to replay ("Graphs" above); every entry rebuilds what it
+   needs at its next call. */
 int rf_shutdown(void);
 /* Frees the scratch rf_jbf_u8 keeps from call to call (one vote byte per 64x64 tile of its largest
    launch, per device and stream, for at most 16 streams).  Call it with no rf_jbf_u8 work in flight
@@ -177,7 +199,7 @@ int rf_jbf_ragged_u8(const uint8_t *joint, const uint8_t *src, uint8_t *dst, int
  *   src    n*h*w*src_cn   device, src_cn in {1,3}
  *   dst    n*h*w*src_cn   device; may alias src
  *   radius 0..4096 (int(sigma_spatial) is a free parameter of the reference's tool): radii up to
- *   120 run the 8-bit kernels (exact uint32 window sums); larger ones run the float kernels of
+ *   128 run the 8-bit kernels (exact uint32 window sums); larger ones run the float kernels of
  *   rf_gf_f32 on float copies of the images kept in the workspace, each pass rounded to uint8 like
  *   convertTo(CV_8U) - the same bytes (on 8-bit data the float path's double window sums are the
  *   same exact integers).  rf_gf_workspace_bytes sizes the workspace for the radius it is given.
@@ -268,6 +290,9 @@ int rf_gf_ragged_u8(const uint8_t *guide, const uint8_t *src, uint8_t *dst, int 
  *   weights    4513 float32 on the device:
  *              W0[32][3] b0[32] | 4 x (W[32][32] b[32]) | wf[160] bf[1]
  *   srgb_lut   256 float32 on the device: linear value of each sRGB byte
+ * The call packs the weights into a slot the library keeps per (device, stream), so it is refused
+ * (RF_E_UNSUPPORTED) on a stream that is being captured into a graph, before anything is enqueued:
+ * graphs use the pair below.
  */
 #define RF_CNN_NPARAMS 4513
 #define RF_CNN_NPACKED 4673 /* floats of rf_cnn_pack_weights' output */
@@ -411,7 +436,9 @@ int rf_colorize_ragged_r8_srgb_u8(const uint8_t *bgr, const uint8_t *r8, uint8_t
  * the cv2.ximgproc semantics).  Same layouts as the 8-bit entry points with float pixels.
  *   rf_jbf_f32: jointBilateralFilter_32f - colour weight interpolated in a table of 4096 bins per
  *     joint channel over the joint's value range, built on the host with libm's exp: the range
- *     comes back to the host, so THIS ENTRY POINT SYNCHRONISES THE STREAM.  A constant joint
+ *     comes back to the host, so THIS ENTRY POINT SYNCHRONISES THE STREAM, and rf_jbf_f32 is refused
+ *     (RF_E_UNSUPPORTED) on a stream that is being captured into a graph, before its tables are
+ *     looked up and before anything is enqueued (rf_gf_f32 below can be captured).  A constant joint
  *     image returns RF_E_UNSUPPORTED (OpenCV switches to a Gaussian blur there), and so does
  *     BORDER_CONSTANT (its zero padding indexes OpenCV's table out of bounds).
  *   rf_gf_f32: guidedFilter on float guide/src, float result (no rounding), `iterations` chained.

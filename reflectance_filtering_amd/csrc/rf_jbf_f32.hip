@@ -322,6 +322,10 @@ extern "C" int rf_jbf_f32(const float *joint, const float *src, float *dst, int 
     if (radius > kJbfMaxRadius)
         return fail(RF_E_UNSUPPORTED, "rf_jbf_f32: radius %d too large", radius);
     hipStream_t stream = (hipStream_t)stream_;
+    // (before the tables and the first copy: a refused call leaves the capture as it found it)
+    if (stream_is_capturing(stream))
+        return fail(RF_E_UNSUPPORTED, "rf_jbf_f32: synchronises its stream and cannot be captured "
+                                      "into a graph");
     JbfTables t;  // tap offsets and spatial weights are those of the 8-bit path
     TablesHold hold{t};
     int rc = get_tables(radius, joint_cn, sigma_color, sigma_space, stream, &t);

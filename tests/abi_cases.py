@@ -1,6 +1,7 @@
-"""The per-entry cases of the C ABI (include/reflectance_filtering.h), built once and run by two modules:
+"""The per-entry cases of the C ABI (include/reflectance_filtering.h), built once and run by three modules:
 tests/test_gpu_buffer_contract.py places a case's buffers at odd addresses inside a guarded arena,
-tests/test_gpu_stream_contract.py runs it on a busy side stream.
+tests/test_gpu_stream_contract.py runs it on a busy side stream, tests/test_gpu_capture_contract.py
+captures it into a graph (or sees it refused) and runs it across rf_shutdown().
 
 A Case holds the buffers of one call with their host data, the call itself and the oracle check of its
 outputs.  An input that holds pixel values, float values or weights also carries a `decoy`: another valid
@@ -626,28 +627,34 @@ def _sizes_arrays(sizes=MIXED):
     return _i32([s[0] for s in sizes]), _i32([s[1] for s in sizes])
 
 
-def jbf_ragged_u8(env, sigma_space=22.0, sizes=MIXED, skind="grey3", first=0):
-    """sigma_space 22: radius 33, the tile classes; 36: radius 54, the slab launch."""
+def jbf_ragged_u8(env, sigma_space=22.0, sizes=MIXED, skind="grey3", first=0, flags=0):
+    """sigma_space 22: radius 33, the tile classes; 36: radius 54, the slab launch; flags
+    RF_JBF_FORCE_GENERIC: the fallback route, rf_jbf_u8 once per image."""
     rf, co, torch = env
     lib = rf._ffi.load_library()
     joint, src = _packed("colour", sizes, first), _packed(skind, sizes, first)
     scn = src.shape[1]
     hs, wd = _sizes_arrays(sizes)
     n, d, sc, ss = len(sizes), -1, 20.0, sigma_space
-    need = lib.rf_jbf_ragged_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, 3, scn, d, ss, 0)
-    if int(np.rint(ss * 1.5)) <= 52:
-        assert need > 0 and rf._ffi.jbf_ragged_plan(sizes, 3, scn, d, sc, ss) is not None
+    need = lib.rf_jbf_ragged_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, 3, scn, d, ss, flags)
+    assert need > 0
+    tiled = rf._ffi.jbf_ragged_plan(sizes, 3, scn, d, sc, ss, flags)
+    slabs = rf._ffi.jbf_ragged_slab_plan(sizes, 3, scn, d, sc, ss, flags)
+    if flags & rf._ffi.JBF_FORCE_GENERIC:
+        assert tiled is None and slabs is None, "the plan no longer puts this list on the fallback route"
+    elif int(np.rint(ss * 1.5)) <= 52:
+        assert tiled is not None
     else:
-        assert need > 0 and rf._ffi.jbf_ragged_slab_plan(sizes, 3, scn, d, sc, ss) is not None
+        assert slabs is not None
 
     def sized(k):
         hk, wk = np.tile(hs, k), np.tile(wd, k)
-        ws = lib.rf_jbf_ragged_workspace_bytes(k * n, hk.ctypes.data, wk.ctypes.data, 3, scn, d, ss, 0)
+        ws = lib.rf_jbf_ragged_workspace_bytes(k * n, hk.ctypes.data, wk.ctypes.data, 3, scn, d, ss, flags)
         assert ws > 0
 
         def call(lib, p, stream):
             return lib.rf_jbf_ragged_u8(p["joint"], p["src"], p["dst"], k * n, hk.ctypes.data, wk.ctypes.data, 3, scn,
-                                        d, sc, ss, 4, 0, p["ws"], ws, stream)
+                                        d, sc, ss, 4, flags, p["ws"], ws, stream)
         return call, ws
     call = sized(1)[0]
 
@@ -663,26 +670,28 @@ def jbf_ragged_u8(env, sigma_space=22.0, sizes=MIXED, skind="grey3", first=0):
                 call, {"dst": (np.uint8, src.shape)}, check, entries=("rf_jbf_ragged_u8",), sync=True, sized=sized)
 
 
-def gf_ragged_u8(env, sizes=MIXED, grey_guide=False, first=0):
-    """grey_guide: a one-channel guide under RF_GF_GREY_AS_BGR."""
+def gf_ragged_u8(env, sizes=MIXED, grey_guide=False, first=0, skind="grey1", radius=9):
+    """grey_guide: a one-channel guide under RF_GF_GREY_AS_BGR; skind "grey3" (a 3-channel src) or radius
+    0: the fallback route, rf_gf_ex_u8 once per image."""
     rf, co, torch = env
     lib = rf._ffi.load_library()
-    guide, src = _packed("joint1" if grey_guide else "colour", sizes, first), _packed("grey1", sizes, first)
-    gcn, flags = guide.shape[1], (rf._ffi.GF_GREY_AS_BGR if grey_guide else 0)
+    guide, src = _packed("joint1" if grey_guide else "colour", sizes, first), _packed(skind, sizes, first)
+    gcn, scn, flags = guide.shape[1], src.shape[1], (rf._ffi.GF_GREY_AS_BGR if grey_guide else 0)
     hs, wd = _sizes_arrays(sizes)
-    n, radius, eps, iterations = len(sizes), 9, 3.0, 2
-    need = lib.rf_gf_ragged_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, gcn, 1, radius, flags)
+    n, eps, iterations = len(sizes), 3.0, 2
+    need = lib.rf_gf_ragged_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, gcn, scn, radius, flags)
     assert need > 0
     if not grey_guide:
-        assert rf._ffi.gf_ragged_plan(sizes, 3, 1, radius) is not None
+        on_route = rf._ffi.gf_ragged_plan(sizes, 3, scn, radius) is not None
+        assert on_route == (scn == 1 and 1 <= radius <= 128), "the plan names another route for this list"
 
     def sized(k):
         hk, wk = np.tile(hs, k), np.tile(wd, k)
-        ws = lib.rf_gf_ragged_workspace_bytes(k * n, hk.ctypes.data, wk.ctypes.data, gcn, 1, radius, flags)
+        ws = lib.rf_gf_ragged_workspace_bytes(k * n, hk.ctypes.data, wk.ctypes.data, gcn, scn, radius, flags)
         assert ws > 0
 
         def call(lib, p, stream):
-            return lib.rf_gf_ragged_u8(p["guide"], p["src"], p["dst"], k * n, hk.ctypes.data, wk.ctypes.data, gcn, 1,
+            return lib.rf_gf_ragged_u8(p["guide"], p["src"], p["dst"], k * n, hk.ctypes.data, wk.ctypes.data, gcn, scn,
                                        radius, eps, iterations, flags, p["ws"], ws, stream)
         return call, ws
     call = sized(1)[0]
