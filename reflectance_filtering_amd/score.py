@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""WHDR of stored decompositions as they are, and of their filtered forms, on one device.
+"""WHDR of stored decompositions as they are, and of their filtered forms: on one device, or under
+torchrun one process per GPU, each on a contiguous slice of the photos (sweep.run_sharded).
 
     python -m reflectance_filtering_amd.score --inputs 'iiw/*.png' --results '{dir}/zoran/{stem}.png' \\
         --coding srgb --out score.json [--per_image score.npz]
@@ -22,11 +23,17 @@ unfiltered row and the filtered ones agree in kind.
 The JSON holds `coding`, `delta`, `images`, `images_with_judgements`, `results` and `source`
 (`mean_whdr` over the images with judgements); with a filter also the keys sweep.py writes for the
 same run (`src_files` is the --results pattern, `guidance` sweep.py's name: `cnn` for self).  The npz holds `source` [N], `has_judgements` and `files`, with a filter `whdr` and `pairs`.
+
+--split and --split_scheme score one of the reference's IIW splits (sweep.py: the position is taken
+over all photos --inputs names; the JSON gains `split`, `files` hold the selected photos).  Under
+RANK / WORLD_SIZE / LOCAL_RANK every rank loads, scores and filters its slice; rank 0 gathers `source`,
+`has_judgements` and `whdr` and writes the files of one process (sweep.py; --io_threads, --group_timeout).
 """
 from __future__ import division, print_function
 
 import argparse
 import json
+import os
 import sys
 
 import numpy as np
@@ -40,7 +47,7 @@ FILTER_ONLY = ("guidance", "guidance_files", "iterations")
 
 
 def build_parser():
-    p = argparse.ArgumentParser(description="WHDR of stored decompositions (one device).")
+    p = argparse.ArgumentParser(description="WHDR of stored decompositions (under torchrun one process per GPU).")
     p.add_argument("--inputs", nargs="+", required=True,
                    help="photos (files or glob patterns), IIW <stem>.json beside each")
     p.add_argument("--results", required=True, metavar="PATTERN",
@@ -62,6 +69,8 @@ def build_parser():
                    help="guide with the image this pattern names per photo (overrides --guidance)")
     f.add_argument("--iterations", type=sweep._positive_int, default=None, metavar="K",
                    help="apply the filter K times with the guidance held fixed; every pass is scored")
+    sweep.add_split_options(p)
+    sweep.add_rank_options(p)
     return p
 
 
@@ -83,6 +92,8 @@ def parse_args(argv):
     if args.filtered:
         args.guidance = args.guidance or "self"
         args.iterations = args.iterations or 1
+    sweep.fill_defaults(args)
+    sweep.check_split(parser, args.split, args.split_scheme)
     return args
 
 
@@ -101,24 +112,53 @@ def main(argv=None):
     photos = expand_inputs(args.inputs)
     if not photos:
         raise SystemExit("no input photos")
-    images, sources, _, judgements, grey = sweep.load(photos, args.results, None, args.png_decoder,
-                                                      photo_pixels=False)
-    comps = [whdr.to_pixels(j, *sweep._size(img)) for j, img in zip(judgements, images)]
-    has = np.array([c.shape[0] > 0 for c in comps], dtype=bool)
-    source = score_sources(sources, grey, comps, args.coding, args.delta)
+    selected, split = sweep.select_split(photos, args.split, args.split_scheme)
+    if not selected:
+        raise SystemExit("no input photos in split %s" % args.split)
+    guidance = "cnn" if args.guidance == "self" else args.guidance
+
+    def work(part):
+        """A rank's slice: the stored files as they are and, with a filter, sweep.run over them."""
+        if not part:
+            out = {"source": np.zeros(0, dtype=np.float64), "has": np.zeros(0, dtype=bool)}
+            if args.filtered:
+                pairs, per_image, _ = sweep.empty_result(args.sigma_color, args.sigma_spatial,
+                                                         args.iterations)
+                out.update(whdr=per_image, pairs=pairs)
+            return out
+        images, sources, _, judgements, grey = sweep.load(part, args.results, None, args.png_decoder,
+                                                          photo_pixels=False)
+        comps = [whdr.to_pixels(j, *sweep._size(img)) for j, img in zip(judgements, images)]
+        out = {"source": score_sources(sources, grey, comps, args.coding, args.delta),
+               "has": np.array([c.shape[0] > 0 for c in comps], dtype=bool)}
+        if args.filtered:
+            pairs, per_image, _ = sweep.run(part, args.filter_type, args.sigma_color,
+                                            args.sigma_spatial, guidance, args.delta,
+                                            src_files=args.results, guidance_files=args.guidance_files,
+                                            iterations=args.iterations, png_decoder=args.png_decoder,
+                                            src_coding=args.coding)
+            out.update(whdr=per_image, pairs=pairs)
+        return out
+
+    rank = int(os.environ.get("RANK", "0"))
+    try:
+        rank, merged = sweep.run_sharded(selected, work, args.io_threads, args.group_timeout)
+    except sweep.ShardError as error:
+        return sweep.fail(rank, error)
+    finally:
+        sweep.leave_group()
+    if rank:
+        return 0
+    source, has = merged["source"], merged["has"]
     result = {
-        "coding": args.coding, "delta": args.delta, "images": len(photos),
+        "coding": args.coding, "delta": args.delta, "images": len(selected),
         "images_with_judgements": int(has.sum()), "results": args.results,
         "source": {"mean_whdr": float(source[has].mean()) if has.any() else 0.0},
     }
-    saved = {"source": source, "has_judgements": has, "files": np.array(photos)}
+    saved = {"source": source, "has_judgements": has, "files": np.array(selected)}
     line = "source: mean WHDR %.6f over %d image(s)" % (result["source"]["mean_whdr"], int(has.sum()))
     if args.filtered:
-        guidance = "cnn" if args.guidance == "self" else args.guidance
-        pairs, per_image, _ = sweep.run(photos, args.filter_type, args.sigma_color, args.sigma_spatial,
-                                        guidance, args.delta, src_files=args.results,
-                                        guidance_files=args.guidance_files, iterations=args.iterations,
-                                        png_decoder=args.png_decoder, src_coding=args.coding)
+        pairs, per_image = merged["pairs"], merged["whdr"]
         filtered, best = sweep.report(args.filter_type, guidance, args.delta, args.sigma_color,
                                       args.sigma_spatial, pairs, per_image, has, args.iterations,
                                       args.results, args.guidance_files)
@@ -126,6 +166,8 @@ def main(argv=None):
         result = filtered
         saved.update(whdr=per_image, pairs=pairs)
         line += "\n" + best
+    if split:
+        result["split"] = split
     with open(args.out, "w") as fh:
         json.dump(result, fh, indent=1)
     if args.per_image:

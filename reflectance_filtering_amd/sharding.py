@@ -3,8 +3,9 @@
 Every image is filtered independently, so multi-GPU operation is pure data
 parallelism: one process per GPU, each takes a contiguous slice of the batch, and there is no
 data-path collective at all (no RCCL traffic over xGMI).  torch.distributed is used only for
-the host-side barrier and for gathering per-rank (pixels, seconds) when measuring - two scalars -
-and does that over gloo: no RCCL communicator is brought up unless one is asked for
+the host-side barrier, for gathering per-rank (pixels, seconds) when measuring - two scalars - and
+for the one gather of host results that ends a sharded sweep (gather_results), and does that over
+gloo: no RCCL communicator is brought up unless one is asked for
 (``init_distributed(backend="nccl")`` or ``RF_DIST_BACKEND=nccl``; SURVEY.md 5: "do not add RCCL").
 """
 
@@ -24,9 +25,11 @@ def shard_sizes(n_items, world_size):
             for r in range(world_size)]
 
 
-def init_distributed(backend=None):
+def init_distributed(backend=None, timeout=None):
     """Join the torchrun rendezvous if one is described by the environment.
-    Returns (rank, world_size, local_rank)."""
+    Returns (rank, world_size, local_rank).  timeout: seconds a rank waits for its peers, at the
+    rendezvous and in every collective of the group, before it raises (None: torch's default of half
+    an hour for gloo)."""
     import os
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -40,7 +43,11 @@ def init_distributed(backend=None):
                 backend = os.environ.get("RF_DIST_BACKEND")
             if backend is None:
                 backend = "gloo"  # host-side barrier + two scalar reductions: nothing for xGMI to carry
-            dist.init_process_group(backend=backend, rank=rank, world_size=world)
+            extra = {}
+            if timeout is not None:
+                import datetime
+                extra["timeout"] = datetime.timedelta(seconds=float(timeout))
+            dist.init_process_group(backend=backend, rank=rank, world_size=world, **extra)
     return rank, world, local
 
 
@@ -80,3 +87,34 @@ def gather_scalars(local_value, world_size, device=None):
     out = [torch.zeros_like(mine) for _ in range(world_size)]
     dist.all_gather(out, mine)
     return [float(t.item()) for t in out]
+
+
+def io_threads(cpus, local_world=1, override=None):
+    """Loader threads of one rank: `override` where given, else its share of the `cpus` in the
+    affinity mask among the `local_world` ranks of the node, at least 1 and at most 16."""
+    if override is not None:
+        if int(override) < 1:
+            raise ValueError("io_threads must be at least 1")
+        return int(override)
+    return max(1, min(16, int(cpus) // max(1, int(local_world))))
+
+
+def gather_results(payload, world_size, timeout=None):
+    """Every rank's `payload` (any picklable host object: arrays, an error message), in rank order,
+    on every rank: the one collective of a sharded sweep.  The objects travel over gloo - a gloo
+    subgroup where the default group is RCCL, whose collectives take device tensors - and reach every
+    rank, not rank 0 alone, so that all ranks learn of a failed peer in the same call and end alike.
+    timeout: seconds, for the subgroup (the default group keeps the one it was made with)."""
+    if world_size == 1:
+        return [payload]
+    import torch.distributed as dist
+    group = None
+    if dist.get_backend() != "gloo":
+        extra = {}
+        if timeout is not None:
+            import datetime
+            extra["timeout"] = datetime.timedelta(seconds=float(timeout))
+        group = dist.new_group(backend="gloo", **extra)
+    out = [None] * world_size
+    dist.all_gather_object(out, payload, group=group)
+    return out

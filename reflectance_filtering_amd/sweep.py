@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """WHDR parameter sweep of the reflectance filters: the loop the reference tool's docstring
 describes ("Go through color and spatial parameters and evaluate filter",
-the reference's filter_reflectance.py:1) over IIW photos and their judgements, on one device.
+the reference's filter_reflectance.py:1) over IIW photos and their judgements: on one device, or
+under torchrun one process per GPU, each on a contiguous slice of the photos (below).
 
     python -m reflectance_filtering_amd.sweep --inputs 'iiw/*.png' --filter_type bilateral \\
         --sigma_color 10,15,20,25 --sigma_spatial 16,22,28 --out sweep.json [--per_image sweep.npz]
@@ -29,6 +30,23 @@ are read on batch.IO_THREADS threads; --png_decoder device leaves only inflate t
 
 run(..., src_coding="srgb") scores stored sources that are sRGB-coded (whdr.value_table); its command
 line, with the unfiltered row beside the sweep, is reflectance_filtering_amd.score.
+
+    ... --inputs 'iiw/*.png' --split val --report_split test [--split_scheme train_val_test]
+
+--split evaluates one of the reference's IIW splits (whdr.iiw_split: the position of a photo in the
+list of all stems --inputs names, sorted as strings - pass the whole dataset); the JSON gains `split`,
+the npz `files` hold the selected photos in the order of the stems.  --report_split NAME then runs the
+best pair of the grid (of the last pass of a chain) on the photos of split NAME: the JSON gains
+`report`, a second line is printed.  Without --split the files are those of before.
+
+    python -m torch.distributed.run --nproc-per-node 8 -m reflectance_filtering_amd.sweep ...
+
+Under RANK / WORLD_SIZE / LOCAL_RANK every rank runs run() on its contiguous slice of the selected
+photos on device LOCAL_RANK modulo the device count (run_sharded); one gather of host arrays over gloo
+ends the run, rank 0 alone summarises, writes and prints, the files are those of one process.  A rank
+whose work raises still reaches the gather: every rank exits non-zero, rank 0 says which rank failed,
+nothing is written.  --io_threads N sets the loader threads of a rank (default: its share of the CPUs
+among the ranks of its node, at most 16), --group_timeout how long a rank waits for its peers.
 """
 from __future__ import division, print_function
 
@@ -287,8 +305,151 @@ def run(photos, filter_type, sigma_color, sigma_spatial, guidance="cnn", delta=0
     return pairs, (per_image if iterations > 1 else per_image[0]), has
 
 
+def empty_result(sigma_color, sigma_spatial, iterations=1):
+    """What run() would return for no photos (it is not called for them: no device work): the pairs,
+    per_image [P, 0] or [K, P, 0], has [0].  The slice of a rank when there are more ranks than
+    photos."""
+    pairs = grid_pairs(sigma_color, sigma_spatial)
+    shape = (pairs.shape[0], 0) if int(iterations) == 1 else (int(iterations), pairs.shape[0], 0)
+    return pairs, np.zeros(shape, dtype=np.float64), np.zeros(0, dtype=bool)
+
+
+# ---- IIW splits -----------------------------------------------------------------------------------------
+
+SPLITS = ("all", "train", "val", "test")
+SPLIT_SCHEMES = ("train_test", "train_val_test", "big_train_mini_val")     # whdr.SPLIT_SCHEMES
+
+
+def stem_of(photo):
+    """`dir/10-x.png` -> `10-x`: what the reference sorts before it splits."""
+    return os.path.splitext(os.path.basename(photo))[0]
+
+
+def select_split(photos, name, scheme):
+    """The photos of split `name` under `scheme` (whdr.iiw_split over the stems of all `photos`, so
+    the list is the whole dataset), in the order of the stems, and what the JSON records about it;
+    "all" gives the list as it is and None.  Two photos with one stem are refused by both names."""
+    from . import whdr
+    photos = list(photos)
+    if name == "all":
+        return photos, None
+    seen = {}
+    for photo in photos:
+        other = seen.setdefault(stem_of(photo), photo)
+        if other is not photo:
+            raise ValueError("{} and {} have the same stem {!r}: its position in the split is "
+                             "ambiguous".format(other, photo, stem_of(photo)))
+    index = whdr.iiw_split([stem_of(photo) for photo in photos], scheme)[name]
+    info = {"name": name, "scheme": scheme, "of": len(photos), "images": len(index)}
+    return [photos[i] for i in index], info
+
+
+# Options a command line of before does not know: they are absent from the parsed namespace unless
+# given (argparse.SUPPRESS; the namespace of such a command line is the one of before), and
+# fill_defaults puts these values in.
+DATASET_DEFAULTS = {"split": "all", "split_scheme": "train_val_test", "report_split": None,
+                    "io_threads": None, "group_timeout": 600.0}
+
+
+def add_split_options(parser):
+    parser.add_argument("--split", choices=SPLITS, default=argparse.SUPPRESS,
+                        help="evaluate only this IIW split (default: all); the position of a photo is "
+                             "taken over all photos --inputs names (sorted by stem), so pass the whole "
+                             "dataset")
+    parser.add_argument("--split_scheme", choices=SPLIT_SCHEMES, default=argparse.SUPPRESS,
+                        help="train_test: 80/20 (every fifth photo is test, no val); train_val_test "
+                             "(the default): 70/10/20; big_train_mini_val: 79/1/20")
+
+
+def fill_defaults(args):
+    for name, value in DATASET_DEFAULTS.items():
+        if not hasattr(args, name):
+            setattr(args, name, value)
+    return args
+
+
+def check_split(parser, name, scheme, option="--split"):
+    if name == "val" and scheme == "train_test":
+        parser.error("%s val: --split_scheme train_test has no val split" % option)
+
+
+# ---- one process per GPU --------------------------------------------------------------------------------
+
+# seconds a rank waits for its peers (torch's own default is half an hour)
+GROUP_TIMEOUT = DATASET_DEFAULTS["group_timeout"]
+SHARED = ("pairs",)         # results every rank computes alike; the others are per photo, last axis
+
+
+class ShardError(RuntimeError):
+    """The work of one or more ranks raised: `failed` holds (rank, message) pairs."""
+
+    def __init__(self, failed):
+        RuntimeError.__init__(self, "; ".join("rank %d failed: %s" % f for f in failed))
+        self.failed = failed
+
+
+def add_rank_options(parser):
+    parser.add_argument("--io_threads", type=_positive_int, default=argparse.SUPPRESS, metavar="N",
+                        help="loader threads of each rank (default: up to 16, under torchrun this "
+                             "rank's share of the CPUs among the ranks of its node)")
+    parser.add_argument("--group_timeout", type=float, default=argparse.SUPPRESS, metavar="SECONDS",
+                        help="how long a rank waits for its peers before it gives up (default: %g)"
+                             % GROUP_TIMEOUT)
+
+
+def _cpus():
+    return len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+
+
+def run_sharded(photos, work, io_threads=None, timeout=GROUP_TIMEOUT):
+    """`work` over `photos`, one contiguous slice (sharding.shard_range) per rank of the torchrun
+    environment (RANK / WORLD_SIZE / LOCAL_RANK): returns (rank, merged).  work(slice) returns a
+    dictionary of host arrays whose last axis is the photo axis (those named in SHARED are equal on
+    every rank and taken from rank 0); it is called for an empty slice too.  merged holds the arrays
+    joined in rank order, which is list order, on every rank.  A rank uses device LOCAL_RANK modulo
+    the device count and its share of the loader threads (sharding.io_threads; io_threads overrides).
+    The results travel in one gather of host data (sharding.gather_results).  A rank whose work
+    raises takes its message to that gather instead, and every rank raises ShardError.  With one
+    rank work(photos) is called as it is: no group, no device choice, today's loader threads."""
+    from . import sharding
+    photos = list(photos)
+    rank, world, local = sharding.init_distributed(timeout=timeout)
+    if io_threads is not None or world > 1:
+        from . import batch
+        local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
+        batch.IO_THREADS = sharding.io_threads(_cpus(), local_world if world > 1 else 1, io_threads)
+    if world == 1:
+        return rank, work(photos)
+    import torch
+    if torch.cuda.is_available():
+        torch.cuda.set_device(local % torch.cuda.device_count())
+    lo, hi = sharding.shard_range(len(photos), world, rank)
+    try:
+        payload = (None, work(photos[lo:hi]))
+    except Exception as exc:    # the gather below is reached whatever happened: no peer waits
+        payload = ("%s: %s" % (type(exc).__name__, exc), None)
+    if rank:
+        print("rank %d: %d photo(s)" % (rank, hi - lo), file=sys.stderr)
+    gathered = sharding.gather_results(payload, world, timeout)
+    failed = [(r, error) for r, (error, _) in enumerate(gathered) if error is not None]
+    if failed:
+        raise ShardError(failed)
+    parts = [part for _, part in gathered]
+    merged = {key: (parts[0][key] if key in SHARED else
+                    np.concatenate([part[key] for part in parts], axis=-1)) for key in parts[0]}
+    return rank, merged
+
+
+def leave_group():
+    """End of a tool under torchrun: the process group is taken down, if there is one."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        dist.destroy_process_group()
+
+
 def build_parser():
-    p = argparse.ArgumentParser(description="WHDR over a grid of filter parameters (one device).")
+    p = argparse.ArgumentParser(description="WHDR over a grid of filter parameters (under torchrun "
+                                            "one process per GPU, each on a slice of the photos).")
     p.add_argument("--inputs", nargs="+", required=True,
                    help="photos (files or glob patterns), IIW <stem>.json beside each")
     p.add_argument("--filter_type", choices=FILTER_TYPES, default="bilateral")
@@ -307,12 +468,32 @@ def build_parser():
                    help="apply the filter K times with the guidance held fixed; every pass is scored")
     p.add_argument("--png_decoder", choices=PNG_DECODERS, default="host",
                    help="device: the threads inflate, the device reconstructs the PNG rows")
+    add_split_options(p)
+    p.add_argument("--report_split", choices=SPLITS[1:], default=argparse.SUPPRESS, metavar="NAME",
+                   help="the paper's protocol in one run: the grid runs on --split, its best pair "
+                        "(of the last pass of a chain) then on the photos of split NAME")
+    add_rank_options(p)
     return p
 
 
+def parse_args(argv):
+    """The options, with the split's checked against each other."""
+    parser = build_parser()
+    args = fill_defaults(parser.parse_args(argv))
+    check_split(parser, args.split, args.split_scheme)
+    if args.report_split:
+        check_split(parser, args.report_split, args.split_scheme, "--report_split")
+        if args.split == "all":
+            parser.error("--report_split needs a --split to choose the pair on: all holds every split")
+        if args.report_split == args.split:
+            parser.error("--report_split %s is the split the pair is chosen on" % args.split)
+    return parser, args
+
+
 def report(filter_type, guidance, delta, sigma_color, sigma_spatial, pairs, per_image, has,
-           iterations=1, src_files=None, guidance_files=None):
-    """What the tool writes about a run(): the JSON dictionary and the line it prints."""
+           iterations=1, src_files=None, guidance_files=None, split=None):
+    """What the tool writes about a run(): the JSON dictionary and the line it prints.  split: what
+    select_split recorded (None: no `split` key)."""
     def best_of(mean, best):
         return {"sigma_color": float(pairs[best, 0]), "sigma_spatial": float(pairs[best, 1]),
                 "mean_whdr": float(mean[best])}
@@ -335,29 +516,95 @@ def report(filter_type, guidance, delta, sigma_color, sigma_spatial, pairs, per_
         result["src_files"] = src_files
     if guidance_files:
         result["guidance_files"] = guidance_files
+    if split:
+        result["split"] = split
     line = ("best: sigma_color %g sigma_spatial %g mean WHDR %.6f over %d image(s)"
             % (pairs[best, 0], pairs[best, 1], mean[best], int(has.sum())))
     return result, line
 
 
+def report_held_out(name, sigma_color, sigma_spatial, per_image, has, iterations=1):
+    """What --report_split adds about the run of the chosen pair on split `name` (per_image [1, N]
+    or [K, 1, N]): the `report` entry of the JSON and the line printed for it."""
+    pair = grid_pairs([sigma_color], [sigma_spatial])
+    passes = [summarise(pair, m, has)[0] for m in (per_image if iterations > 1 else [per_image])]
+    entry = {"split": name, "sigma_color": float(sigma_color), "sigma_spatial": float(sigma_spatial),
+             "mean_whdr": float(passes[-1][0]), "images": len(has),
+             "images_with_judgements": int(has.sum())}
+    if iterations > 1:
+        entry["passes"] = [{"pass": k + 1, "mean_whdr": float(m[0])} for k, m in enumerate(passes)]
+    line = ("%s: sigma_color %g sigma_spatial %g mean WHDR %.6f over %d image(s)"
+            % (name, sigma_color, sigma_spatial, entry["mean_whdr"], int(has.sum())))
+    return entry, line
+
+
+def refuse(parser, rank, message):
+    """parser.error on rank 0; the other ranks end with its status and leave the words to it."""
+    if rank:
+        raise SystemExit(2)
+    parser.error(message)
+
+
+def fail(rank, error):
+    """The end of a tool whose ranks raised (ShardError): rank 0 says which, every rank returns 1."""
+    if rank == 0:
+        for r, message in error.failed:
+            print("rank %d failed: %s" % (r, message), file=sys.stderr)
+        print("no output written", file=sys.stderr)
+    return 1
+
+
 def main(argv=None):
-    args = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    parser, args = parse_args(sys.argv[1:] if argv is None else argv)
     from .batch import expand_inputs
     photos = expand_inputs(args.inputs)
     if not photos:
         raise SystemExit("no input photos")
-    pairs, per_image, has = run(photos, args.filter_type, args.sigma_color, args.sigma_spatial,
-                                args.guidance, args.delta, src_files=args.src_files,
-                                guidance_files=args.guidance_files, iterations=args.iterations,
-                                png_decoder=args.png_decoder)
-    result, line = report(args.filter_type, args.guidance, args.delta, args.sigma_color,
-                          args.sigma_spatial, pairs, per_image, has, args.iterations, args.src_files,
-                          args.guidance_files)
+    selected, split = select_split(photos, args.split, args.split_scheme)
+    if not selected:
+        raise SystemExit("no input photos in split %s" % args.split)
+
+    def work_on(sigma_color, sigma_spatial):
+        def work(part):
+            pairs, per_image, has = (run(part, args.filter_type, sigma_color, sigma_spatial,
+                                         args.guidance, args.delta, src_files=args.src_files,
+                                         guidance_files=args.guidance_files,
+                                         iterations=args.iterations, png_decoder=args.png_decoder)
+                                     if part else empty_result(sigma_color, sigma_spatial, args.iterations))
+            return {"pairs": pairs, "whdr": per_image, "has": has}
+        return work
+
+    rank = int(os.environ.get("RANK", "0"))
+    try:
+        rank, merged = run_sharded(selected, work_on(args.sigma_color, args.sigma_spatial),
+                                   args.io_threads, args.group_timeout)
+        pairs, per_image, has = merged["pairs"], merged["whdr"], merged["has"]
+        result, line = report(args.filter_type, args.guidance, args.delta, args.sigma_color,
+                              args.sigma_spatial, pairs, per_image, has, args.iterations,
+                              args.src_files, args.guidance_files, split)
+        if args.report_split:
+            if not has.any():
+                refuse(parser, rank, "--report_split: no image of split %s has judgements to choose "
+                                     "a pair on" % args.split)
+            held, _ = select_split(photos, args.report_split, args.split_scheme)
+            if not held:
+                refuse(parser, rank, "--report_split: no photo in split %s" % args.report_split)
+            c, s = result["best"]["sigma_color"], result["best"]["sigma_spatial"]
+            _, other = run_sharded(held, work_on([c], [s]), args.io_threads, args.group_timeout)
+            result["report"], second = report_held_out(args.report_split, c, s, other["whdr"],
+                                                       other["has"], args.iterations)
+            line += "\n" + second
+    except ShardError as error:
+        return fail(rank, error)
+    finally:
+        leave_group()
+    if rank:
+        return 0
     with open(args.out, "w") as fh:
         json.dump(result, fh, indent=1)
     if args.per_image:
         np.savez(args.per_image, whdr=per_image, pairs=pairs, has_judgements=has,
-                 files=np.array(photos))
+                 files=np.array(selected))
     print(line)
     return 0
 

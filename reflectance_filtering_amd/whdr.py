@@ -51,6 +51,42 @@ def to_pixels(comparisons, height, width):
     return px
 
 
+SPLIT_SCHEMES = ("train_test", "train_val_test", "big_train_mini_val")
+_VAL_PERIOD = {"train_val_test": 10, "big_train_mini_val": 100}
+
+
+def iiw_split(stems, scheme="train_val_test"):
+    """The reference's IIW splits (training/createNumpyArrayWithComparisonsForIIW.py:689-728
+    narihiraSplitIntoTwoLists, narihiraSplitIntoThreeLists, splitIntoBigTrainMiniVal, over the list
+    sorted at :745): {split name: indices into `stems`}, every list in the sorted order, so
+    [stems[i] for i in result[name]] is the list the reference's function returns.  The stems (file
+    names without directory and extension) are sorted with Python's plain string order; position k
+    is `test` if k % 5 == 0, else `val` if k % 10 == 6 (train_val_test) or k % 100 == 6
+    (big_train_mini_val), else `train`; train_test has no `val`.  The order is that of the stems,
+    not of the file names (`10-x.png` sorts before `10.png`, the stem `10-x` after `10`).  Two
+    equal stems make the positions ambiguous and are refused."""
+    if scheme not in SPLIT_SCHEMES:
+        raise ValueError("scheme must be one of %s" % ", ".join(SPLIT_SCHEMES))
+    stems = [str(s) for s in stems]
+    order = sorted(range(len(stems)), key=lambda i: stems[i])
+    for a, b in zip(order, order[1:]):
+        if stems[a] == stems[b]:
+            raise ValueError("duplicate stem %r (items %d and %d): its position in the split is "
+                             "ambiguous" % (stems[a], a, b))
+    period = _VAL_PERIOD.get(scheme)
+    split = {"train": [], "test": []}
+    if period:
+        split["val"] = []
+    for k, i in enumerate(order):
+        if k % 5 == 0:
+            split["test"].append(i)
+        elif period and k % period == 6:
+            split["val"].append(i)
+        else:
+            split["train"].append(i)
+    return split
+
+
 def _point_lightness(reflectance, ys, xs):
     """Lightness of the pixels (ys[i], xs[i]) of a [c,h,w] image, one gather for all points:
     the channel mean (3 channels, in the image's dtype like np.mean of one pixel) or the value
