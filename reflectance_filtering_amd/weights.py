@@ -144,3 +144,61 @@ def load_weights(caffemodel=None):
     if flat.dtype != np.float32 or flat.shape != (N_PARAMS,):
         raise ValueError("corrupt weight file %s" % _DATA)
     return flat
+
+
+def _put_varint(value):
+    out = bytearray()
+    while True:
+        b = value & 0x7F
+        value >>= 7
+        if value:
+            out.append(b | 0x80)
+        else:
+            out.append(b)
+            return bytes(out)
+
+
+def _put_bytes(field, payload):
+    """One length-delimited field (wire type 2)."""
+    return _put_varint(field << 3 | 2) + _put_varint(len(payload)) + payload
+
+
+def _put_blob(arr):
+    """BlobProto: shape = field 7 {dim = field 1, packed}, data = field 5, packed floats."""
+    dims = b"".join(_put_varint(d) for d in arr.shape)
+    return _put_bytes(7, _put_bytes(1, dims)) + _put_bytes(5, arr.astype("<f4").tobytes())
+
+
+def unflatten(flat):
+    """The 4,513-float vector -> {layer name: [weights, bias]} in Caffe's blob shapes (the inverse
+    of flatten)."""
+    flat = np.asarray(flat)
+    if flat.dtype != np.float32 or flat.shape != (N_PARAMS,):
+        raise ValueError("expected %d float32 parameters" % N_PARAMS)
+    layers = {}
+    pos = 0
+    for name in CONV_LAYERS:
+        blobs = []
+        for shape in _EXPECTED_SHAPES[name]:
+            size = int(np.prod(shape))
+            blobs.append(flat[pos:pos + size].reshape(shape).copy())
+            pos += size
+        layers[name] = blobs
+    assert pos == N_PARAMS
+    return layers
+
+
+def write_caffemodel(path, flat):
+    """Write the 4,513 float32 parameters as a binary NetParameter: the six convolution layers by
+    their names in network_definition.prototxt (NetParameter.layer = field 100; LayerParameter.name
+    = 1, .type = 2, .blobs = 7), each with its weight and bias blob and their shapes.
+    read_caffemodel reads the file back to the same bits, so it can be passed wherever the package
+    takes ``caffemodel=``."""
+    body = _put_bytes(1, b"reflectance_filtering_amd")
+    for name, blobs in unflatten(flat).items():
+        layer = _put_bytes(1, name.encode("utf-8")) + _put_bytes(2, b"Convolution")
+        for blob in blobs:
+            layer += _put_bytes(7, _put_blob(blob))
+        body += _put_bytes(100, layer)
+    with open(path, "wb") as fh:
+        fh.write(body)
