@@ -10,6 +10,13 @@
  * Return codes are numerically those of reflectance_filtering.h (RF_OK 0, RF_E_BADARG -1,
  * RF_E_UNSUPPORTED -2, RF_E_HIP -4); every refusal is decided on the host before any device work
  * and leaves its text in rf_train_last_error() (thread-local).
+ *
+ * tests/test_gpu_train_contract.py holds both device entries to these sentences with the runners of the
+ * main library's four contract modules (cases: tests/train_cases.py): every buffer at odd residues
+ * inside a guarded arena over a dirty workspace, behind a delay on a busy non-blocking side stream
+ * (the call returns while the work in front of it is pending), captured once into a graph and replayed
+ * on true inputs and on decoys - also after rf_shutdown() of the main library -, and over buffers
+ * past byte 2^32 and at the largest admitted launch.
  */
 #ifndef REFLECTANCE_FILTERING_TRAIN_H
 #define REFLECTANCE_FILTERING_TRAIN_H

@@ -19,6 +19,8 @@ takes `first` (the images behind the usual ones: another period of the same kind
 `sizes`, and a Case carries `sized(k)`: the same call over k periods, a period being the case's own
 images (n of them for a uniform entry, the whole list for a ragged one), with the workspace it needs.
 Buffers named in PER_CALL do not grow with the periods.
+
+tests/train_cases.py builds the cases of librf_train_hip.so in the same format.
 """
 import zlib
 
@@ -29,7 +31,7 @@ from tests import synth
 
 S1, S2, S3 = (2, 67, 131), (3, 5, 7), (1, 1, 1)
 MIXED = ((67, 131), (5, 7), (5, 7), (67, 131), (5, 7))     # the ragged entries' list
-INDEX_LIKE = ("points", "offsets", "point_offsets", "comps", "comp_offsets")
+INDEX_LIKE = ("points", "offsets", "point_offsets", "comps", "comp_offsets", "inc_offsets", "inc")
 PER_CALL = ("weights", "lut", "steps", "packed", "ws")      # one per call, however many images it has
 
 

@@ -20,7 +20,8 @@ is 26,331 or 8,777 bytes, both odd, so the second image of a batch is at an odd 
 S2 = 3 x 5 x 7 (smaller than every tile and window; 105 bytes), S3 = 1 x 1 x 1.
 
 The cases themselves (buffers, host data, the call, the oracle check) are built by tests/abi_cases.py,
-which tests/test_gpu_stream_contract.py runs as well.
+which tests/test_gpu_stream_contract.py runs as well.  tests/test_gpu_train_contract.py runs _contract on the
+two entries of librf_train_hip.so (cases: tests/train_cases.py).
 """
 import ctypes
 import itertools
@@ -55,9 +56,12 @@ def _residues(bufs, layout):
     return out
 
 
-def _run(env, case, layout, fill):
+def _run(env, case, layout, fill, lib=None, last_error=None):
+    """lib, last_error: the library the case calls and the getter of its error text (default: librf_hip.so and
+    its rf_last_error; tests/test_gpu_train_contract.py passes librf_train_hip.so)."""
     rf, co, torch = env
-    lib = rf._ffi.load_library()
+    lib = rf._ffi.load_library() if lib is None else lib
+    last_error = lib.rf_last_error if last_error is None else last_error
     ar = A.Arena(torch, "cuda", A.arena_bytes([b.nbytes for b in case.bufs]), fill)
     regs = {}
     for b, res in zip(case.bufs, _residues(case.bufs, layout)):
@@ -75,7 +79,7 @@ def _run(env, case, layout, fill):
     else:
         rc = case.call(lib, ptrs, stream)
     torch.cuda.synchronize()
-    assert rc == rf._ffi.RF_OK, (layout, fill, rc, lib.rf_last_error())
+    assert rc == rf._ffi.RF_OK, (layout, fill, rc, last_error())
     try:
         ar.assert_only_changed([regs[b.name] for b in case.bufs if b.role in ("out", "ws")])
     except AssertionError as err:
@@ -84,10 +88,10 @@ def _run(env, case, layout, fill):
     return C.typed_outputs(case, raw)
 
 
-def _contract(env, case):
+def _contract(env, case, lib=None, last_error=None):
     base = None
     for layout, fill in PAIRS:
-        outs = _run(env, case, layout, fill)
+        outs = _run(env, case, layout, fill, lib, last_error)
         if case.after is not None:
             case.after()
         if base is None:

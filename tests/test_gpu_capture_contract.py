@@ -30,6 +30,9 @@ against the oracle; rf_shutdown(); the same call; rf_jbf_release_scratch(); the 
 Then one sequence across entries: rf_shutdown(), five cases, rf_shutdown(), the five in reverse.  The
 module ends with rf_shutdown(): what it built leaves with it, and the first use of a parameter set in a
 later module is a first use.
+
+Bench and _capture also serve tests/test_gpu_train_contract.py: both entries of librf_train_hip.so are
+capturable, and their graphs are replayed once more after rf_shutdown() of this library.
 """
 import gc
 
@@ -119,7 +122,7 @@ class Bench(Flight):
     def eager(self, stream, what):
         rc, _ = self.enqueue(stream, NoDelay(), 0)
         stream.synchronize()
-        assert rc == self.env[0]._ffi.RF_OK, (what, rc, self.lib.rf_last_error())
+        assert rc == self.env[0]._ffi.RF_OK, (what, rc, self.last_error())
         self.verify(what=what)
 
 
@@ -172,7 +175,7 @@ def _capture(env, ctx, bench):
     try:
         with torch.cuda.graph(graph, stream=S):
             rc = bench._call(S)
-            msg = ctx.lib.rf_last_error() if rc != rf._ffi.RF_OK else b""
+            msg = bench.last_error() if rc != rf._ffi.RF_OK else b""
     except RuntimeError as err:
         ended = err
     torch.cuda.synchronize()

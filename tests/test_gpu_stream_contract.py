@@ -30,6 +30,9 @@ The module tests itself as well (test_the_runner_notices_work_on_another_stream)
 entry handed another stream - an idle one, which runs ahead, and a held-up one, which runs behind - must
 fail the oracle check.  One finding of the module is kept as a test of its own: a call that finds its
 parameter tables cached does not free the table set an earlier call evicted (hipFree waits for the device).
+
+Flight and Delay also serve tests/test_gpu_train_contract.py, which holds the two entries of
+librf_train_hip.so (include/reflectance_filtering_train.h) to points 1 and 2.
 """
 import ctypes
 import math
@@ -178,11 +181,13 @@ def _ptr(stream):
 class Flight(object):
     """One case with buffers of its own: an arena (every base a multiple of 256, filled with 0xA5) that
     holds the decoys, the true inputs and the decoys again as separate device tensors, and `slots` sets
-    of keep-buffers for the outputs."""
+    of keep-buffers for the outputs.  lib is the library the case calls, last_error the getter of its error
+    text (default: lib.rf_last_error; tests/test_gpu_train_contract.py passes librf_train_hip.so's)."""
 
-    def __init__(self, env, lib, case, slots=1):
+    def __init__(self, env, lib, case, slots=1, last_error=None):
         rf, co, torch = env
         self.env, self.lib, self.case, self.torch = env, lib, case, torch
+        self.last_error = lib.rf_last_error if last_error is None else last_error
         self.ar = A.Arena(torch, "cuda", A.arena_bytes([b.nbytes for b in case.bufs]), 0xA5)
         self.regs, self.true, self.decoy = {}, {}, {}
         for b in case.bufs:
@@ -232,7 +237,7 @@ class Flight(object):
                 if name not in self.decoy:                # (an output that is an input too holds its decoy)
                     self.ar.bytes(self.regs[name]).fill_(0xA5)
             stream.synchronize()
-        assert rc == self.env[0]._ffi.RF_OK, (rc, self.lib.rf_last_error())
+        assert rc == self.env[0]._ffi.RF_OK, (rc, self.last_error())
         return seconds
 
     def enqueue(self, stream, delay, reps, slot=0, call_on=None):

@@ -1,5 +1,9 @@
 """Training ops library on the device: the hinge entry against the float64 restatement, the backward
-entry against torch CPU float64 autograd, and five full-batch SGD steps end to end."""
+entry against torch CPU float64 autograd, five full-batch SGD steps end to end, and what the header
+states of the backward kernel and of the trainer beyond that: a point with grad_r = 0 adds nothing, the
+sigmoid derivative near saturation, weights unrelated to the shipped ones, a run inside the packed set,
+minibatch SGD across an epoch boundary, Adam.  tests/test_gpu_train_contract.py holds the two entries to
+the buffer, stream, capture and size contracts."""
 import ctypes
 import os
 
@@ -19,9 +23,9 @@ BLOCKS = (("W0", 0, 96), ("b0", 96, 128), ("W1", 128, 1152), ("b1", 1152, 1184),
 
 # ---- plain-torch statements (the oracles) ----------------------------------------------------------
 
-def net(x_bgr, w):
-    """The network on [P,3] B,G,R inputs with the flat parameter vector w: r [P] and the 160
-    pre-activations [P,160]."""
+def net_z(x_bgr, w):
+    """The network on [P,3] B,G,R inputs with the flat parameter vector w up to the sigmoid: z [P] and the
+    160 pre-activations [P,160]."""
     h = x_bgr.flip(1)
     pre, acts = [], []
     h = h @ w[0:96].view(32, 3).t() + w[96:128]
@@ -35,7 +39,13 @@ def net(x_bgr, w):
         h = torch.relu(h)
         acts.append(h)
     z = torch.cat(acts, 1) @ w[4352:4512] + w[4512]
-    return torch.sigmoid(z), torch.cat(pre, 1)
+    return z, torch.cat(pre, 1)
+
+
+def net(x_bgr, w):
+    """r [P] and the 160 pre-activations [P,160]."""
+    z, pre = net_z(x_bgr, w)
+    return torch.sigmoid(z), pre
 
 
 def hinge_torch(r, po, cp, wt, co, delta, margin):
@@ -158,10 +168,10 @@ def test_hinge_entry_empty_and_weightless_images(built):
 
 # ---- backward entry -------------------------------------------------------------------------------------
 
-def backward_case(npoints, seed):
-    from reflectance_filtering_amd import image_utils as iu, weights as wmod
-    rng = np.random.RandomState(seed)
-    w = wmod.load_weights() * (1 + 0.05 * rng.standard_normal(NP)).astype(np.float32)
+def draw_inputs(rng, w, npoints):
+    """[npoints,3] inputs, half uniform and half from the sRGB table, none with a pre-activation within 1e-4
+    of a ReLU kink under the weights w (float64); at most 2 % of the points (one at least) are redrawn."""
+    from reflectance_filtering_amd import image_utils as iu
     lut = iu.srgb_byte_lut()
     w64 = torch.from_numpy(w.astype(np.float64))
 
@@ -179,7 +189,15 @@ def backward_case(npoints, seed):
             break
         redrawn += int(close.sum())
         x[close] = draw(int(close.sum()))
-    assert not close.any() and redrawn <= max(1, 0.02 * npoints)
+    assert not close.any() and redrawn <= max(1, 0.02 * npoints), (redrawn, npoints)
+    return x
+
+
+def backward_case(npoints, seed):
+    from reflectance_filtering_amd import weights as wmod
+    rng = np.random.RandomState(seed)
+    w = wmod.load_weights() * (1 + 0.05 * rng.standard_normal(NP)).astype(np.float32)
+    x = draw_inputs(rng, w, npoints)
     grad_r = rng.standard_normal(npoints).astype(np.float32)
     grad_r[rng.rand(npoints) < 0.5] = 0
     return x, w, grad_r
@@ -265,24 +283,45 @@ def end_to_end_inputs():
     return images, comps
 
 
-def trajectory(x, arrays, w0, dtype):
-    """STEPS full-batch steps of Caffe's SGD with momentum in plain torch on the CPU: the weights
-    after the last step and the loss before every step and after the last."""
+def trajectory(x, arrays, w0, dtype, steps=STEPS, batch_size=None, seed=0, solver="sgd", lr=LR,
+               adam_eps=None, momentum2=0.999):
+    """`steps` steps of Caffe's SGD with momentum (or of its Adam) in plain torch on the CPU: the weights
+    after the last step, the loss before every step and after the last, and the first step's gradient.
+    batch_size None: full batches.  Otherwise a minibatch is a run of batch_size consecutive images
+    (train.batch_runs) and every epoch takes the runs in the order RandomState(seed + epoch).permutation
+    gives - train.fit's rule, restated here."""
+    from reflectance_filtering_amd import train
     po, cp, wt, co = arrays
+    n = len(co) - 1
+    runs = train.batch_runs(n, n if batch_size is None else batch_size, full_batch=batch_size is None)
     w = torch.from_numpy(w0.astype(dtype))
-    v = torch.zeros_like(w)
+    v, v2 = torch.zeros_like(w), torch.zeros_like(w)
     xt = torch.from_numpy(x.astype(dtype))
-    losses = []
-    for step in range(STEPS + 1):
+    losses, queue, epoch, first_grad = [], [], 0, None
+    for step in range(steps + 1):
+        if not queue:
+            queue = [runs[i] for i in np.random.RandomState(seed + epoch).permutation(len(runs))]
+            epoch += 1
+        first, count = queue.pop(0)
         wt_ = w.clone().requires_grad_(True)
-        loss = hinge_torch(net(xt, wt_)[0], po, cp, wt, co, DELTA, MARGIN)
+        loss = hinge_torch(net(xt, wt_)[0], po[first:first + count + 1], cp, wt, co[first:first + count + 1],
+                           DELTA, MARGIN)
         losses.append(loss.item())
-        if step == STEPS:
+        if step == steps:
             break
         loss.backward()
-        v = MOMENTUM * v + LR * wt_.grad
-        w = w - v
-    return w.numpy().astype(np.float64), losses
+        g = wt_.grad
+        first_grad = g.numpy().astype(np.float64) if first_grad is None else first_grad
+        if solver == "sgd":
+            v = MOMENTUM * v + lr * g
+            w = w - v
+        else:
+            t = step + 1
+            v = MOMENTUM * v + (1 - MOMENTUM) * g
+            v2 = momentum2 * v2 + (1 - momentum2) * g * g
+            rate = lr * np.sqrt(1 - momentum2 ** t) / (1 - MOMENTUM ** t)
+            w = w - rate * v / (v2.sqrt() + adam_eps)
+    return w.numpy().astype(np.float64), losses, first_grad
 
 
 def test_five_full_batch_sgd_steps_end_to_end(built, tmp_path):
@@ -294,8 +333,8 @@ def test_five_full_batch_sgd_steps_end_to_end(built, tmp_path):
     arrays = (packed.point_offsets, packed.comps, packed.weights, packed.comp_offsets)
     x = packed.x.cpu().numpy()
     w0 = wmod.load_weights()
-    want, want_losses = trajectory(x, arrays, w0, np.float64)
-    f32, _ = trajectory(x, arrays, w0, np.float32)
+    want, want_losses, _ = trajectory(x, arrays, w0, np.float64)
+    f32, _, _ = trajectory(x, arrays, w0, np.float32)
     assert want_losses[-1] < want_losses[0]
     final, history = train.fit(packed, w0, iterations=STEPS, base_lr=LR, solver="sgd",
                                momentum=MOMENTUM, full_batch=True, delta=DELTA, margin=MARGIN,
@@ -317,3 +356,243 @@ def test_five_full_batch_sgd_steps_end_to_end(built, tmp_path):
     _, shipped8 = rf.get_reflectance_batch(batch)
     _, trained8 = rf.get_reflectance_batch(batch, weights=wmod.load_weights(path))
     assert not torch.equal(shipped8, trained8)
+
+
+# ---- what the header states of the backward kernel and of the trainer, and nothing else checks -------------------
+
+def block_distances(got, want, f32):
+    """Per parameter block: (name, device distance, float32 distance), both relative to the block's largest
+    |oracle| element."""
+    out = []
+    for name, a, b in BLOCKS:
+        scale = np.abs(want[a:b]).max()
+        d32 = np.abs(f32[a:b] - want[a:b]).max() / scale if scale else 0.0
+        dev = np.abs(got[a:b] - want[a:b]).max() / scale if scale else np.abs(got[a:b]).max()
+        out.append((name, dev, d32))
+    return out
+
+
+def test_a_point_with_zero_grad_r_adds_exactly_nothing(built):
+    """P = 130 with one live point - at lane 0, 1, 31, 32 (the second half of a matrix step), 63, at 64 (lane 0
+    of the second pass) and at the last point - gives, as values (-0 equals +0), the call with P = 1 on that
+    point alone: the kernel's tail handling (dead lanes run with grad_r = 0) rests on it."""
+    from reflectance_filtering_amd import _ffi_train
+    lib = _ffi_train.load_library()
+    x, w, _ = backward_case(130, 135)       # (the first seed from 100 + 130 % 97 on that meets the redraw cap)
+    values = np.random.RandomState(8).standard_normal(130).astype(np.float32)
+    differ = []
+    for at in (0, 1, 31, 32, 63, 64, 129):
+        grad_r = np.zeros(130, np.float32)
+        grad_r[at] = values[at]
+        assert grad_r[at] != 0
+        among = run_backward(lib, x, w, grad_r)
+        alone = run_backward(lib, x[at:at + 1], w, grad_r[at:at + 1])
+        assert np.isfinite(alone).all() and np.abs(alone).max() > 0
+        bad = np.flatnonzero(~(among == alone))
+        print("live point %3d: %d of %d gradient elements differ from the call on the point alone"
+              % (at, bad.size, NP))
+        if bad.size:
+            differ.append((at, bad.size, int(bad[0]), float(among[bad[0]]), float(alone[bad[0]])))
+    assert not differ, differ
+
+
+def chain_z(x, w):
+    """z of a float32 CPU forward pass in the order the header gives for the kernels: every dot product an FMA
+    chain, k ascending from 0, then + bias; z the chain over the 160 post-ReLU activations in channel order, then
+    + bf.  (An FMA is formed in float64 - the product of two floats is exact there - and rounded to float32.)"""
+    f32 = np.float32
+
+    def fma(a, b, c):
+        return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(f32)
+
+    def layer(mat, bias, h):
+        acc = np.zeros((h.shape[0], mat.shape[0]), f32)
+        for k in range(mat.shape[1]):
+            acc = fma(mat[None, :, k], h[:, k:k + 1], acc)
+        return np.maximum(acc + bias[None, :], f32(0))
+    x, w = np.asarray(x, f32), np.asarray(w, f32)
+    h = layer(w[0:96].reshape(32, 3), w[96:128], x[:, ::-1])
+    acts = [h]
+    for l in range(4):
+        base = 128 + l * 1056
+        h = layer(w[base:base + 1024].reshape(32, 32), w[base + 1024:base + 1056], h)
+        acts.append(h)
+    acts = np.concatenate(acts, 1)
+    z = np.zeros(x.shape[0], f32)
+    for c in range(160):
+        z = fma(w[4352 + c], acts[:, c], z)
+    return z + w[4512]
+
+
+def saturated_case(low, high, seed):
+    """130 points under the shipped weights with bf shifted so that every z lies in [low, high] (float64 and
+    float32 CPU forward alike): (x, w)."""
+    from reflectance_filtering_amd import weights as wmod
+    rng = np.random.RandomState(seed)
+    w = wmod.load_weights().astype(np.float32).copy()
+    x = draw_inputs(rng, w, 1040)
+    z = net_z(torch.from_numpy(x.astype(np.float64)), torch.from_numpy(w.astype(np.float64)))[0].numpy()
+    shift = 0.5 * (low + high) - np.median(z)
+    w[4512] = np.float32(w[4512] + shift)
+    z64 = net_z(torch.from_numpy(x.astype(np.float64)), torch.from_numpy(w.astype(np.float64)))[0].numpy()
+    z32 = chain_z(x, w)
+    keep = np.flatnonzero((np.minimum(z64, z32) >= low + 0.25) & (np.maximum(z64, z32) <= high - 0.25))
+    assert keep.size >= 130, keep.size
+    return np.ascontiguousarray(x[keep[:130]]), w
+
+
+@pytest.mark.parametrize("low,high", [(8.0, 12.0), (-12.0, -8.0)], ids=["r-near-1", "r-near-0"])
+def test_sigmoid_derivative_near_saturation(built, low, high):
+    """The kernel forms sigma'(z) = r (1 - r) in double from its float32 z and rounds dz once (the header).  The
+    oracle is float64 autograd with its z moved onto the float32 z of a float32 CPU forward pass in the
+    kernels' chain order (chain_z), so that what is compared is the derivative at the z the forward chains
+    give and not the rounding of z itself (at |z| = 10 an ulp of z is 1e-6 of sigma', ten times the
+    yardstick); the yardstick is float32 autograd up to z with dz formed in float64 from that z and rounded once.  Plain
+    float32 autograd (1 - r in float32) is printed beside it: near r = 1 it is far outside 4 x the yardstick,
+    so a kernel that fell back to float32 there would fail."""
+    from reflectance_filtering_amd import _ffi_train
+    lib = _ffi_train.load_library()
+    x, w = saturated_case(low, high, 31)
+    grad_r = np.random.RandomState(32).standard_normal(130).astype(np.float32)
+    x32, w32 = torch.from_numpy(x), torch.from_numpy(w)
+    z32 = torch.from_numpy(chain_z(x, w))
+    assert float(z32.min()) >= low and float(z32.max()) <= high
+    print("z in [%g, %g]: the chain-ordered float32 z is within %.3g of torch's float32 z"
+          % (low, high, float((z32 - net_z(x32, w32)[0]).abs().max())))
+    gr64 = torch.from_numpy(grad_r.astype(np.float64))
+    # the oracle
+    w64 = torch.from_numpy(w.astype(np.float64)).requires_grad_(True)
+    z64 = net_z(x32.double(), w64)[0]
+    (torch.sigmoid(z64 + (z32.double() - z64).detach()) * gr64).sum().backward()
+    want = w64.grad.numpy()
+    # the yardstick
+    wy = w32.clone().requires_grad_(True)
+    zy = net_z(x32, wy)[0]
+    ry = torch.sigmoid(z32.double())
+    zy.backward((gr64 * (ry * (1 - ry))).float())
+    yard = wy.grad.numpy().astype(np.float64)
+    plain = autograd(x, w, grad_r, np.float32)
+    got = run_backward(lib, x, w, grad_r).astype(np.float64)
+    misses = []
+    for (name, dev, d32), (_, dplain, _) in zip(block_distances(got, want, yard), block_distances(plain, want, yard)):
+        print("z in [%g, %g] %s: yardstick %.3g, device %.3g, plain float32 autograd %.3g" % (low, high, name, d32,
+                                                                                             dev, dplain))
+        misses += [(name, dev, d32)] if dev > 4 * d32 else []
+    assert not misses, misses
+
+
+def test_backward_entry_with_gaussian_weights(built):
+    """Weights unrelated to the shipped ones: every entry N(0, 1 / fan_in), so the fuse weights have both signs
+    and about half of every layer's channels are off at a point.  With 160 such channels a point lies within
+    1e-4 of a kink far more often than under the shipped weights, and the redraw cap (one point of 65) holds
+    for about one seed in three; the seed is the first from 41 on at which the inputs meet it."""
+    from reflectance_filtering_amd import _ffi_train
+    lib = _ffi_train.load_library()
+    rng = np.random.RandomState(43)
+    w = np.zeros(NP, np.float32)
+    w[0:128] = rng.standard_normal(128) / np.sqrt(3)
+    for l in range(4):
+        w[128 + l * 1056:128 + (l + 1) * 1056] = rng.standard_normal(1056) / np.sqrt(32)
+    w[4352:4513] = rng.standard_normal(161) / np.sqrt(160)
+    assert (w[4352:4512] > 0).sum() >= 40 and (w[4352:4512] < 0).sum() >= 40
+    x = draw_inputs(rng, w, 65)
+    grad_r = rng.standard_normal(65).astype(np.float32)
+    grad_r[rng.rand(65) < 0.5] = 0
+    want, f32 = autograd(x, w, grad_r, np.float64), autograd(x, w, grad_r, np.float32)
+    got = run_backward(lib, x, w, grad_r).astype(np.float64)
+    misses = []
+    for name, dev, d32 in block_distances(got, want, f32):
+        print("gaussian weights %s: float32 autograd %.3g, device %.3g" % (name, d32, dev))
+        misses += [(name, dev, d32)] if dev > 4 * d32 else []
+    assert not misses, misses
+
+
+def packed_inputs():
+    from reflectance_filtering_amd import train
+    images, comps = end_to_end_inputs()
+    packed = train.pack(images, comps, order_seed=5)
+    arrays = (packed.point_offsets, packed.comps, packed.weights, packed.comp_offsets)
+    return packed, arrays, packed.x.cpu().numpy()
+
+
+def test_loss_and_grad_on_a_run_inside_the_packed_set(built):
+    """first = 2, count = 3 of the six images: x + 12 p0 and grad_r + 4 p0 reach the kernel, bases that are no
+    multiple of 256 bytes.  Against hinge_torch / net in float64 at 4 x the float32 distance: the gradient per
+    parameter block, the per-image losses relative to the largest."""
+    from reflectance_filtering_amd import train, weights as wmod
+    packed, (po, cp, wt, co), x = packed_inputs()
+    first, count = 2, 3
+    assert (12 * int(po[first])) % 256 and (4 * int(po[first])) % 256
+    w0 = wmod.load_weights()
+
+    def oracle(dtype):
+        w = torch.from_numpy(w0.astype(dtype)).requires_grad_(True)
+        r = net(torch.from_numpy(x.astype(dtype)), w)[0]
+        per = [hinge_torch(r, po[i:i + 2], cp, wt, co[i:i + 2], DELTA, MARGIN) for i in range(first, first + count)]
+        (sum(per) / count).backward()
+        return np.array([p.item() for p in per], np.float64), w.grad.numpy().astype(np.float64)
+    want_l, want_g = oracle(np.float64)
+    f32_l, f32_g = oracle(np.float32)
+    loss, per_image, grad = train.loss_and_grad(w0, packed, first, count, DELTA, MARGIN)
+    got = grad.cpu().numpy().astype(np.float64)
+    d32 = np.abs(f32_l - want_l).max() / want_l.max()
+    dev = np.abs(per_image - want_l).max() / want_l.max()
+    print("run [2, 5): per-image losses float32 %.3g, device %.3g; mean %.9g against %.9g"
+          % (d32, dev, loss, want_l.mean()))
+    assert per_image.shape == (count,) and dev <= 4 * d32
+    assert loss == float(per_image.mean())              # (documented as exactly that mean)
+    misses = []
+    for name, dev, d32 in block_distances(got, want_g, f32_g):
+        print("run [2, 5) %s: float32 %.3g, device %.3g" % (name, d32, dev))
+        misses += [(name, dev, d32)] if dev > 4 * d32 else []
+    assert not misses, misses
+
+
+def test_minibatch_sgd_across_an_epoch_boundary(built):
+    """batch_size 2 on the six images: three runs an epoch, five steps, so the second epoch's reshuffle is
+    taken.  The oracle restates the order (trajectory).  The float32 distance is about one float32 ulp of a
+    weight of magnitude 1 over the largest weight change: it is the rounding of the float32 weights themselves,
+    which the device's trajectory shares, and no measure of the device's gradient accuracy (the backward tests
+    are); what the bound catches is a wrong batch order or update rule, whose errors are far larger."""
+    from reflectance_filtering_amd import train, weights as wmod
+    packed, arrays, x = packed_inputs()
+    w0 = wmod.load_weights()
+    orders = [np.random.RandomState(1 + e).permutation(3).tolist() for e in range(2)]
+    assert orders[0] != orders[1], orders                 # the reshuffle can be told from a repeat
+    want, want_losses, _ = trajectory(x, arrays, w0, np.float64, steps=5, batch_size=2, seed=1)
+    f32, _, _ = trajectory(x, arrays, w0, np.float32, steps=5, batch_size=2, seed=1)
+    final, _ = train.fit(packed, w0, iterations=5, batch_size=2, base_lr=LR, solver="sgd", momentum=MOMENTUM,
+                         delta=DELTA, margin=MARGIN, seed=1)
+    scale = np.abs(want - w0).max()
+    d32, dev = np.abs(f32 - want).max() / scale, np.abs(final - want).max() / scale
+    print("minibatch SGD: oracle batch losses %s; float32 trajectory %.3g, device %.3g of the largest weight "
+          "change %.3g" % (want_losses, d32, dev, scale))
+    assert dev <= 4 * d32
+
+
+ADAM_EPS_FACTOR = 1e-3      # adam_eps over the largest |gradient| element of the float64 oracle at step 0
+
+
+def test_adam_minibatch_steps(built):
+    """Three Adam steps on the same minibatches.  adam_eps is ADAM_EPS_FACTOR x the largest |gradient| element
+    of the float64 oracle at step 0, so that elements whose gradient is rounding noise are not amplified
+    (m / (sqrt(v) + eps) is +-1 for any gradient well above eps, however small).  As in the SGD test the
+    float32 distance is mostly the rounding of the float32 weights and moments themselves: the bound catches a
+    wrong update rule or batch order, not a small gradient error."""
+    from reflectance_filtering_amd import train, weights as wmod
+    packed, arrays, x = packed_inputs()
+    w0 = wmod.load_weights()
+    _, _, g0 = trajectory(x, arrays, w0, np.float64, steps=1, batch_size=2, seed=1)
+    eps = ADAM_EPS_FACTOR * np.abs(g0).max()
+    want, want_losses, _ = trajectory(x, arrays, w0, np.float64, steps=3, batch_size=2, seed=1, solver="adam",
+                                      lr=1e-3, adam_eps=eps)
+    f32, _, _ = trajectory(x, arrays, w0, np.float32, steps=3, batch_size=2, seed=1, solver="adam", lr=1e-3,
+                           adam_eps=eps)
+    final, _ = train.fit(packed, w0, iterations=3, batch_size=2, base_lr=1e-3, solver="adam", momentum=MOMENTUM,
+                         momentum2=0.999, adam_eps=eps, delta=DELTA, margin=MARGIN, seed=1)
+    scale = np.abs(want - w0).max()
+    d32, dev = np.abs(f32 - want).max() / scale, np.abs(final - want).max() / scale
+    print("Adam: adam_eps %.3g; oracle batch losses %s; float32 trajectory %.3g, device %.3g of the largest weight "
+          "change %.3g" % (eps, want_losses, d32, dev, scale))
+    assert d32 <= 1e-3, "the float32 trajectory is %.3g of the largest weight change: the case measures noise" % d32
+    assert dev <= 4 * d32

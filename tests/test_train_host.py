@@ -308,3 +308,127 @@ def test_cli_runs_with_stubs(tmp_path, monkeypatch, capsys):
     assert "val hinge 0.750000 whdr 0.5000" in capsys.readouterr().out
     with pytest.raises(SystemExit):
         train.main(["--inputs", str(tmp_path / "none*.png")])
+
+
+# ---- the cases of the contract module (tests/train_cases.py, tests/test_gpu_train_contract.py) ------------
+
+def _train_env():
+    import torch
+
+    import reflectance_filtering_amd as rf
+    return rf, None, torch
+
+
+def test_contract_cases_build_and_the_oracle_on_their_decoys_fails_their_check(built):
+    """Building a case needs the plan and the workspace query only.  Per case: the entries it names, the
+    buffer roles, a decoy that differs for every value input and none for the index-like ones, the case's
+    check passing on the oracle's own result (as float32 where the device writes float32) and FAILING on the
+    oracle's result for the decoys - otherwise a replay on decoys would prove nothing."""
+    from tests import abi_cases as C
+    from tests import train_cases as T
+    env = _train_env()
+    assert {"inc_offsets", "inc"} <= set(C.INDEX_LIKE)
+    assert sorted(T.CASES) == ["backward-P32833", "backward-P65", "hinge-fixture", "hinge-run",
+                               "hinge-wide-margin"]
+    per, most, _ = env[0]._ffi_train.cnn_points_plan(2 ** 31 - 1)
+    assert T.plan_p32833(env[0]) == (most + 1) * per + 1 == 32833
+    for name in sorted(T.CASES):
+        entries, build, opts = T.CASES[name]
+        case = build(env)               # (the backward builder asserts the redraw cap of 2 % at its size)
+        assert case.entries == entries and not case.sync and not opts, name
+        values = []
+        for b in case.bufs:
+            if b.data is None:
+                assert b.role in ("out", "ws"), (name, b.name)
+            elif b.name in C.INDEX_LIKE:
+                assert b.decoy is None and b.data.dtype == np.int32, (name, b.name)
+            else:
+                assert b.decoy is not None and not np.array_equal(b.decoy, b.data), (name, b.name)
+                assert np.isfinite(b.decoy.astype(np.float64)).all(), (name, b.name)
+                assert np.array_equal(np.sort(b.decoy, axis=None), np.sort(b.data, axis=None)) \
+                    or np.array_equal(b.decoy, b.data * b.data.dtype.type(0.5)), (name, b.name)
+                values.append(b.name)
+        assert values == (["r", "weights"] if name.startswith("hinge") else ["x", "weights", "grad_r"]), name
+        true = dict((b.name, b.data) for b in case.bufs if b.data is not None)
+        decoys = dict((b.name, b.decoy if b.decoy is not None else b.data) for b in case.bufs
+                      if b.data is not None)
+        as_written = {"loss_out": np.float64, "grad_r": np.float32, "grad_w": np.float32}
+        right = dict((k, v.astype(as_written[k])) for k, v in case.oracle_on(true).items())
+        case.check(right)
+        wrong = dict((k, v.astype(as_written[k])) for k, v in case.oracle_on(decoys).items())
+        with pytest.raises(AssertionError):
+            case.check(wrong)
+        if name.startswith("hinge"):        # ... and the weights' decoy alone: no uniform scale, which cancels
+            only_w = dict(true, weights=decoys["weights"])
+            with pytest.raises(AssertionError):
+                case.check(dict((k, v.astype(as_written[k])) for k, v in case.oracle_on(only_w).items()))
+            scaled = dict(true, weights=true["weights"] * 0.5)
+            case.check(dict((k, v.astype(as_written[k])) for k, v in case.oracle_on(scaled).items()))
+    fix = T._fixture(1)
+    assert (fix["delta"], fix["margin"]) == (0.12, 0.08) and T._fixture(2)["margin"] > T._fixture(2)["delta"]
+    po, cp, wt, co = fix["arrays"]
+    assert np.diff(co).tolist() == [5, 300, 1181] and np.diff(po).max() > 256
+
+
+def test_hinge_run_case_reports_a_write_outside_the_run(built):
+    """The callable `outputs` of hinge-run: grad_r in front of the run holds one fill byte throughout."""
+    from tests import abi_cases as C
+    from tests import train_cases as T
+    case = T.CASES["hinge-run"][1](_train_env())
+    sizes = dict((b.name, b.nbytes) for b in case.bufs)
+    for fill in (0xA5, 0x00, 0xFF):
+        raw = {"loss_out": np.full(sizes["loss_out"], fill, np.uint8),
+               "grad_r": np.full(sizes["grad_r"], fill, np.uint8)}
+        outs = C.typed_outputs(case, raw)
+        assert outs["loss_out"].shape == (2,) and 4 * outs["grad_r"].size < sizes["grad_r"]
+        raw["grad_r"][5] ^= 0x10
+        with pytest.raises(AssertionError, match="outside the points"):
+            C.typed_outputs(case, raw)
+
+
+def test_every_train_entry_that_takes_a_stream_is_capturable_and_a_case_reaches_it():
+    """The class list of tests/test_gpu_train_contract.py against include/reflectance_filtering_train.h, in
+    the style of tests/test_capture_cases.py: the library has no refusing class."""
+    from tests import test_gpu_train_contract as tc
+    from tests import train_cases as T
+    from tests.test_stream_cases import _entries_with_a_stream
+    with open(os.path.join(ROOT, "include", "reflectance_filtering_train.h")) as fh:
+        text = fh.read()
+    names = _entries_with_a_stream(text)
+    assert names == ["rf_train_cnn_points_backward_f32", "rf_train_whdr_hinge_points_f32"]
+    assert sorted(tc.CAPTURABLE) == names and len(set(tc.CAPTURABLE)) == len(tc.CAPTURABLE)
+    assert tc.REFUSING == () and tc.SYNCHRONISING == ()
+    reached = set(e for entries, _, _ in T.CASES.values() for e in entries)
+    assert reached == set(names)
+    for test in (tc.test_buffer_contract, tc.test_entry_on_a_busy_side_stream,
+                 tc.test_case_is_captured_and_replays_also_after_rf_shutdown):
+        marks = [m for m in test.pytestmark if m.name == "parametrize"]
+        assert len(marks) == 1 and list(marks[0].args[1]) == sorted(T.CASES), test.__name__
+    preamble = text[:text.index("#ifndef")]
+    for words in ("synchronises nothing", "ordered like any kernel launch", "safe to capture into a graph",
+                  "does not concern", "tests/test_gpu_train_contract.py"):
+        assert words in re.sub(r"\s*\n\s*\*\s*", " ", preamble), words
+    assert "does not depend on what the workspace held" in re.sub(r"\s*\n\s*\*\s*", " ", text)
+
+
+def test_contract_cases_sit_at_the_residues_the_documents_name(built):
+    """float32 and int32 buffers at 4 and 12, float64 buffers at 8 and 24, the workspace at 16, in every layout but
+    L0 (tests/test_gpu_buffer_contract._residues): the sentence of the header preamble, of DESIGN.md and of
+    tests/test_gpu_train_contract.py."""
+    from tests import train_cases as T
+    from tests.test_gpu_buffer_contract import PAIRS, _residues
+    env = _train_env()
+    for name in sorted(T.CASES):
+        case = T.CASES[name][1](env)
+        assert set(_residues(case.bufs, "L0")) == {0}
+        for layout in sorted(set(l for l, _ in PAIRS) - {"L0"}):
+            by_elem = {}
+            for b, res in zip(case.bufs, _residues(case.bufs, layout)):
+                assert res % b.elem == 0, (name, b.name)
+                by_elem.setdefault("ws" if b.role == "ws" else b.elem, set()).add(res)
+            assert by_elem.pop(4) == {4, 12}, (name, layout)
+            if name.startswith("hinge"):
+                assert by_elem.pop(8) == {8, 24}, (name, layout)
+            else:
+                assert by_elem.pop("ws") == {16}, (name, layout)
+            assert not by_elem, (name, layout, by_elem)
