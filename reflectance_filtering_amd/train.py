@@ -14,6 +14,11 @@ step:
     python -m reflectance_filtering_amd.train --inputs 'iiw/*.png' --split train --report_split val \
         --iterations 2000 --batch_size 10 --base_lr 1e-3 --out weights.caffemodel --log train.json
 
+`--comparisons augmented` trains on the transitive hull of every photo's judgements (augment.py, the
+reference's --comparisonsType augmented) and, like the reference's layer, evaluates a random
+`--max_evaluated` (1,500) of an image's comparisons per step; the true WHDR is still that of the
+original judgements.
+
 Single process, single GPU.  There is no CPU fallback.
 """
 from __future__ import division, print_function
@@ -30,12 +35,15 @@ from . import whdr as whdr_mod
 
 SOLVERS = ("sgd", "adam")
 DENSE_COMPARISONS = 300     # whdr_hinge_loss_layer.py:136: above this an image is "densely annotated"
+MAX_EVALUATED_COMPARISONS = 1500    # whdr_hinge_loss_layer.py: a random subsample above this many
+COMPARISON_TYPES = ("comparisons", "augmented")
 
 
 def select_comparisons(comparisons, ratio=1.0, eval_dense=True):
     """The reference's choice of an image's evaluated comparisons (whdr_hinge_loss_layer.py:135-140):
     one comparison for an image with more than 300 when eval_dense is false, then the first
-    ceil(ratio * count).  Its random subsample above 1,500 comparisons is not mirrored."""
+    ceil(ratio * count).  Its random subsample above 1,500 comparisons is drawn per step
+    (subsample_weights)."""
     if not 0 < ratio <= 1:
         raise ValueError("ratio must be in (0, 1]")
     comparisons = np.asarray(comparisons, dtype=np.float64).reshape(-1, 6)
@@ -104,13 +112,19 @@ def _inputs_at(image, xs, ys, lut):
     raise ValueError("an image must be uint8 (sRGB) or float32 (linear)")
 
 
-def pack(images, comparisons_px, order_seed=None, ratio=1.0, eval_dense=True, device=None):
+def pack(images, comparisons_px, order_seed=None, ratio=1.0, eval_dense=True, device=None,
+         hinge_comparisons_px=None):
     """The training set on the device.  images: [H,W,3] BGR arrays, uint8 sRGB or float32 linear, of
     any sizes; comparisons_px: per image float [m,6] judgements in pixel coordinates
     (whdr.to_pixels).  The image order is shuffled once (order_seed; None keeps it), the
     comparisons are selected (select_comparisons), de-duplicated (whdr.dedup_points) and given
     incidence lists, and the network inputs at the points are gathered into one [total,3] buffer:
-    they never change during training."""
+    they never change during training.
+    hinge_comparisons_px: a second comparison set per image (the augmented one), same format.  When
+    given, the hinge arrays (comps, weights, comp_offsets, the incidence lists) come from IT, selected
+    as the reference applies ratio / eval_dense to its `augmented` blob, the true WHDR of evaluate()
+    comes from ALL of comparisons_px (whdr_comps, whdr_weights, whdr_comp_offsets), and the points are
+    the de-duplicated union of both sets.  Without it nothing changes: whdr_* are the hinge arrays."""
     torch = _ffi.require_gpu()
     from . import image_utils as iu
     if len(images) != len(comparisons_px):
@@ -121,7 +135,27 @@ def pack(images, comparisons_px, order_seed=None, ratio=1.0, eval_dense=True, de
     images = [images[i] for i in order]
     comps_px = [select_comparisons(comparisons_px[i], ratio, eval_dense) for i in order]
     sizes = [tuple(int(v) for v in im.shape[:2]) for im in images]
-    points, point_offsets, comps, weights, comp_offsets = whdr_mod.dedup_points_ragged(comps_px, sizes)
+    if hinge_comparisons_px is None:
+        points, point_offsets, comps, weights, comp_offsets = whdr_mod.dedup_points_ragged(comps_px, sizes)
+        whdr_px, whdr_arrays = comps_px, (comps, weights, comp_offsets)
+    else:
+        if len(hinge_comparisons_px) != n:
+            raise ValueError("one second comparison array per image")
+        whdr_px = [np.asarray(comparisons_px[i], dtype=np.float64).reshape(-1, 6) for i in order]
+        comps_px = [select_comparisons(hinge_comparisons_px[i], ratio, eval_dense) for i in order]
+        points, point_offsets, both, both_w, both_off = whdr_mod.dedup_points_ragged(
+            [np.concatenate([h, o], axis=0) for h, o in zip(comps_px, whdr_px)], sizes)
+        parts = [[], []]        # per image the first rows are the hinge set, the rest the judgements
+        for i in range(n):
+            cut = both_off[i] + comps_px[i].shape[0]
+            parts[0].append(slice(both_off[i], cut))
+            parts[1].append(slice(cut, both_off[i + 1]))
+        split = []
+        for rows in parts:
+            offsets = np.concatenate([[0], np.cumsum([r.stop - r.start for r in rows])]).astype(np.int32)
+            split.append((np.concatenate([both[r] for r in rows] + [both[:0]], axis=0),
+                          np.concatenate([both_w[r] for r in rows] + [both_w[:0]], axis=0), offsets))
+        (comps, weights, comp_offsets), whdr_arrays = split
     if (comps.shape[0] and ((comps[:, 2] < 0) | (comps[:, 2] > 2)).any()):
         raise ValueError("darker is neither 0 (=E), 1, 2")
     inc_offsets, inc = point_incidence(point_offsets, comps, comp_offsets)
@@ -134,7 +168,8 @@ def pack(images, comparisons_px, order_seed=None, ratio=1.0, eval_dense=True, de
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     packed = Packed()
     packed.n, packed.total, packed.order, packed.sizes = n, int(points.shape[0]), order, sizes
-    packed.comparisons_px = comps_px
+    packed.comparisons_px, packed.whdr_comparisons_px = comps_px, whdr_px
+    packed.whdr_comps, packed.whdr_weights, packed.whdr_comp_offsets = whdr_arrays
     packed.points, packed.point_offsets, packed.comps = points, point_offsets, comps
     packed.weights, packed.comp_offsets = weights, comp_offsets
     packed.inc_offsets, packed.inc = inc_offsets, inc
@@ -179,16 +214,39 @@ def forward(weights, packed, first, count):
     return packed.r[p0:p1]
 
 
-def hinge(packed, first, count, delta, margin):
+def subsample_weights(packed, first, count, max_evaluated, generator):
+    """The reference layer's random subsample (whdr_hinge_loss_layer.py, MAX_EVALUATED_COMPARISONS): a
+    copy of the packed weights (CUDA float64 [m]) in which every image of [first, first + count) with
+    more than max_evaluated hinge comparisons keeps max_evaluated of them, chosen without replacement
+    by `generator` (a torch generator on the device), and the rest have weight 0 - exact zeros in the
+    entry's loss, weight sum and gradient, which leaves the reference's arithmetic on the chosen ones.
+    None where nothing is to be dropped (max_evaluated 0 = all): no draw is made then."""
+    torch = _ffi.require_gpu()
+    _run(packed, first, count)
+    if not max_evaluated:
+        return None
+    sizes = np.diff(packed.comp_offsets[first:first + count + 1].astype(np.int64))
+    if not (sizes > max_evaluated).any():
+        return None
+    weights = packed.d_weights.clone()
+    for i in np.nonzero(sizes > max_evaluated)[0]:
+        k0 = int(packed.comp_offsets[first + i])
+        order = torch.randperm(int(sizes[i]), generator=generator, device=weights.device)
+        weights[k0 + order[int(max_evaluated):]] = 0
+    return weights
+
+
+def hinge(packed, first, count, delta, margin, weights=None):
     """rf_train_whdr_hinge_points_f32 on packed.r for images [first, first + count): the per-image
-    losses (CUDA float64 [count]); d mean-loss / d r is left in packed.grad_r."""
+    losses (CUDA float64 [count]); d mean-loss / d r is left in packed.grad_r.  weights: this call's
+    weight array (subsample_weights) in place of the packed one."""
     torch = _ffi.require_gpu()
     lib = _ffi_train.load_library()
     _run(packed, first, count)
     losses = torch.zeros(max(count, 1), dtype=torch.float64, device=packed.x.device)
     rc = lib.rf_train_whdr_hinge_points_f32(
         packed.r.data_ptr(), packed.d_point_offsets.data_ptr() + 4 * first,
-        packed.d_comps.data_ptr(), packed.d_weights.data_ptr(),
+        packed.d_comps.data_ptr(), (packed.d_weights if weights is None else weights).data_ptr(),
         packed.d_comp_offsets.data_ptr() + 4 * first, packed.d_inc_offsets.data_ptr(),
         packed.d_inc.data_ptr(), int(count), float(delta), float(margin), losses.data_ptr(),
         packed.grad_r.data_ptr(), _ffi.current_stream_ptr(torch))
@@ -220,13 +278,13 @@ def backward(weights, packed, first, count):
     return grad_w
 
 
-def loss_and_grad(weights, packed, first, count, delta=0.1, margin=0.0):
+def loss_and_grad(weights, packed, first, count, delta=0.1, margin=0.0, hinge_weights=None):
     """(loss, per-image losses float64 [count] (host), grad_w CUDA float32 [4513]) of the mean hinge
     loss over the packed images [first, first + count) - a minibatch is a run of consecutive images
     and needs no repacking.  The loss is that of exactly the reflectance `decompose` would output
-    for these weights."""
+    for these weights.  hinge_weights: the comparison weights of this step (subsample_weights)."""
     forward(weights, packed, first, count)
-    losses = hinge(packed, first, count, delta, margin)
+    losses = hinge(packed, first, count, delta, margin, hinge_weights)
     grad_w = backward(weights, packed, first, count)
     per_image = losses.cpu().numpy()
     return (float(per_image.mean()) if count else 0.0), per_image, grad_w
@@ -234,17 +292,18 @@ def loss_and_grad(weights, packed, first, count, delta=0.1, margin=0.0):
 
 def whdr_at_points(packed, delta=0.1):
     """The true WHDR of packed.r per packed image (host, whdr.whdr: each image's points as a
-    one-row image, its comparisons re-addressed into it), float64 [n]."""
+    one-row image, its comparisons re-addressed into it), float64 [n].  The comparisons are the
+    packed judgements: the hinge set itself unless pack() was given a second set."""
     r = packed.r.cpu().numpy()
     out = np.zeros(packed.n, dtype=np.float64)
     for i in range(packed.n):
         p0, p1 = packed.point_offsets[i], packed.point_offsets[i + 1]
-        k0, k1 = packed.comp_offsets[i], packed.comp_offsets[i + 1]
+        k0, k1 = packed.whdr_comp_offsets[i], packed.whdr_comp_offsets[i + 1]
         if k1 == k0:
             continue
         rows = np.zeros((k1 - k0, 6), dtype=np.float64)
-        rows[:, 0], rows[:, 2] = packed.comps[k0:k1, 0], packed.comps[k0:k1, 1]
-        rows[:, 4], rows[:, 5] = packed.comps[k0:k1, 2], packed.weights[k0:k1]
+        rows[:, 0], rows[:, 2] = packed.whdr_comps[k0:k1, 0], packed.whdr_comps[k0:k1, 1]
+        rows[:, 4], rows[:, 5] = packed.whdr_comps[k0:k1, 2], packed.whdr_weights[k0:k1]
         out[i] = whdr_mod.whdr(r[p0:p1].reshape(1, 1, -1), rows, delta)
     return out
 
@@ -267,12 +326,14 @@ def batch_runs(n, batch_size, full_batch=False):
 
 def fit(packed, weights=None, iterations=100, batch_size=10, base_lr=1e-3, solver="sgd",
         momentum=0.9, momentum2=0.999, adam_eps=1e-8, full_batch=False, delta=0.1, margin=0.0,
-        seed=0, report_every=0, held_out=None, log=None):
+        seed=0, report_every=0, held_out=None, log=None, max_evaluated=0):
     """Train for `iterations` steps.  Minibatches are runs of `batch_size` consecutive images of the
     packed order, and the order of the batches is reshuffled every epoch from `seed`; full_batch
     takes all images every step.  solver: "sgd" (v = momentum v + lr g; w -= v, Caffe's SGD) or
     "adam" (Caffe's Adam).  Every report_every steps (and after the last) the mean hinge loss and
-    true WHDR of the whole training set and of `held_out` (another pack()) are recorded.
+    true WHDR of the whole training set and of `held_out` (another pack()) are recorded, over all
+    their comparisons.  max_evaluated > 0: every step evaluates a random max_evaluated of the hinge
+    comparisons of an image that has more (subsample_weights, drawn on the device from `seed`).
     Returns (weights float32 [4513] (host), history: list of dicts)."""
     torch = _ffi.require_gpu()
     from . import weights as wmod
@@ -287,6 +348,8 @@ def fit(packed, weights=None, iterations=100, batch_size=10, base_lr=1e-3, solve
     m1, m2 = torch.zeros_like(w), torch.zeros_like(w)
     runs = batch_runs(packed.n, batch_size, full_batch)
     history, queue, epoch = [], [], 0
+    chooser = torch.Generator(device=dev)
+    chooser.manual_seed(int(seed))
 
     def record(step, batch_loss):
         entry = {"iteration": step, "batch_loss": batch_loss, "train": evaluate(w, packed, delta, margin)}
@@ -304,7 +367,8 @@ def fit(packed, weights=None, iterations=100, batch_size=10, base_lr=1e-3, solve
             queue = [runs[i] for i in np.random.RandomState(seed + epoch).permutation(len(runs))]
             epoch += 1
         first, count = queue.pop(0)
-        batch_loss, _, grad = loss_and_grad(w, packed, first, count, delta, margin)
+        batch_loss, _, grad = loss_and_grad(w, packed, first, count, delta, margin,
+                                            subsample_weights(packed, first, count, max_evaluated, chooser))
         if solver == "sgd":
             m1.mul_(momentum).add_(grad, alpha=base_lr)
             w.sub_(m1)
@@ -336,6 +400,13 @@ def _non_negative(text):
     return value
 
 
+def _count(text):
+    value = int(text)
+    if value < 0:
+        raise argparse.ArgumentTypeError("must be >= 0")
+    return value
+
+
 def build_parser():
     from . import sweep
     p = argparse.ArgumentParser(description="Fine-tune the 1x1 reflectance CNN on the WHDR hinge loss "
@@ -352,6 +423,10 @@ def build_parser():
     p.add_argument("--ratio", type=float, default=1.0, help="evaluate the first ceil(ratio * m) comparisons")
     p.add_argument("--eval_dense", type=int, choices=(0, 1), default=1,
                    help="0: one comparison for images with more than %d" % DENSE_COMPARISONS)
+    p.add_argument("--comparisons", choices=COMPARISON_TYPES, default="comparisons",
+                   help="augmented: the hinge loss takes the transitive hull of each photo's judgements")
+    p.add_argument("--max_evaluated", type=_count, default=MAX_EVALUATED_COMPARISONS, metavar="K",
+                   help="per step a random K of an image's comparisons when it has more (0 = all)")
     p.add_argument("--solver", choices=SOLVERS, default="sgd")
     p.add_argument("--base_lr", type=_positive(float), default=1e-3)
     p.add_argument("--momentum", type=_non_negative, default=0.9)
@@ -386,7 +461,13 @@ def load_packed(photos, args, order_seed):
     from . import sweep
     images, _, _, judgements, _ = sweep.load(photos)
     comps = [whdr_mod.to_pixels(j, im.shape[0], im.shape[1]) for j, im in zip(judgements, images)]
-    return pack(images, comps, order_seed, args.ratio, bool(args.eval_dense))
+    if args.comparisons != "augmented":
+        return pack(images, comps, order_seed, args.ratio, bool(args.eval_dense))
+    from . import augment
+    lists, points = augment.augment_files([sweep.judgements_for(f) for f in photos], seed=args.seed)
+    hull = [whdr_mod.to_pixels(augment.to_rows(a, p), im.shape[0], im.shape[1])
+            for a, p, im in zip(lists, points, images)]
+    return pack(images, comps, order_seed, args.ratio, bool(args.eval_dense), hinge_comparisons_px=hull)
 
 
 def main(argv=None):
@@ -421,10 +502,11 @@ def main(argv=None):
                          base_lr=args.base_lr, solver=args.solver, momentum=args.momentum,
                          full_batch=args.full_batch, delta=args.delta, margin=args.margin,
                          seed=args.seed, report_every=args.report_every, held_out=held_packed,
-                         log=say)
+                         log=say, max_evaluated=args.max_evaluated)
     wmod.write_caffemodel(args.out, final)
     result = {"delta": args.delta, "margin": args.margin, "ratio": args.ratio,
-              "eval_dense": args.eval_dense, "solver": args.solver, "base_lr": args.base_lr,
+              "eval_dense": args.eval_dense, "comparisons_type": args.comparisons,
+              "max_evaluated": args.max_evaluated, "solver": args.solver, "base_lr": args.base_lr,
               "momentum": args.momentum, "iterations": args.iterations,
               "batch_size": args.batch_size, "full_batch": bool(args.full_batch), "seed": args.seed,
               "images": packed.n, "points": packed.total, "comparisons": int(packed.comps.shape[0]),
