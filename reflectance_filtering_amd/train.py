@@ -19,6 +19,15 @@ reference's --comparisonsType augmented) and, like the reference's layer, evalua
 `--max_evaluated` (1,500) of an image's comparisons per step; the true WHDR is still that of the
 original judgements.
 
+`--RS_est_mode rRelMean` (or rRelMax, rRelY, rRelNorm) trains the network's output as the factor of
+image / norm(image), the reference's colour modes, with both of its boundary losses (reflectance and
+shading inside [0, 1]).  Those are means over EVERY pixel, so the step is dense:
+
+    e      = ops.cnn_reflectance_f32 over all pixels of the minibatch (pack_dense)
+    L      = rf_recover_forward_f32 at the judgement points -> the hinge entry as above
+    grad_e = rf_recover_boundary_backward_f32 over all pixels, then rf_recover_hinge_scatter_f32
+    grad_w = rf_train_cnn_points_backward_f32 over all pixels
+
 Single process, single GPU.  There is no CPU fallback.
 """
 from __future__ import division, print_function
@@ -30,13 +39,22 @@ import sys
 
 import numpy as np
 
-from . import _ffi, _ffi_train
+from . import _ffi, _ffi_recover, _ffi_train
 from . import whdr as whdr_mod
 
 SOLVERS = ("sgd", "adam")
 DENSE_COMPARISONS = 300     # whdr_hinge_loss_layer.py:136: above this an image is "densely annotated"
 MAX_EVALUATED_COMPARISONS = 1500    # whdr_hinge_loss_layer.py: a random subsample above this many
 COMPARISON_TYPES = ("comparisons", "augmented")
+RS_MODES = ("rDirectly", "rRelMean", "rRelMax", "rRelY", "rRelNorm")    # networks.py: the one-channel r modes
+BOUNDARY_PENALTIES = ("L1", "L2")
+
+
+def rs_norm(rs_mode):
+    """The norm code of the recover entries for an rRel* mode, None for rDirectly."""
+    if rs_mode not in RS_MODES:
+        raise ValueError("rs_mode must be one of %s" % ", ".join(RS_MODES))
+    return None if rs_mode == "rDirectly" else _ffi_recover.NORMS[rs_mode[4:]]
 
 
 def select_comparisons(comparisons, ratio=1.0, eval_dense=True):
@@ -186,6 +204,51 @@ def pack(images, comparisons_px, order_seed=None, ratio=1.0, eval_dense=True, de
     return packed
 
 
+def check_distinct_pixels(point_pixel):
+    """rf_recover_hinge_scatter_f32 adds into grad_e at the listed pixels without atomics: two equal
+    indices would race, so a list with a repeated pixel is refused here."""
+    point_pixel = np.asarray(point_pixel, dtype=np.int64).ravel()
+    if np.unique(point_pixel).size != point_pixel.size:
+        raise ValueError("the packed points are not pairwise distinct pixels")
+    return point_pixel
+
+
+def pack_dense(images, comparisons_px, order_seed=None, ratio=1.0, eval_dense=True, device=None,
+               hinge_comparisons_px=None):
+    """pack() for the dense modes (rRel*): the same Packed plus
+        x_dense        CUDA float32 [T,3] (B, G, R): every pixel of every image in packed order,
+                       row-major, through the same sRGB table as x
+        pixel_offsets  int64 [n+1] (host): image i owns the pixels [pixel_offsets[i], pixel_offsets[i+1])
+        point_pixel    int64 [total] (host; d_point_pixel on the device): the absolute dense index of
+                       every packed point, so that x_dense[point_pixel] is x bit for bit
+    Memory: 12 bytes per pixel stay on the device for the whole training, about 2 MB per IIW photo
+    (341 x 512), 2 GB for a thousand; a step adds 8 bytes per pixel of its minibatch (e and grad_e)."""
+    torch = _ffi.require_gpu()
+    from . import image_utils as iu
+    packed = pack(images, comparisons_px, order_seed, ratio, eval_dense, device, hinge_comparisons_px)
+    images = [images[i] for i in packed.order]
+    dev = packed.x.device
+    areas = [h * w for h, w in packed.sizes]
+    pixel_offsets = np.concatenate([[0], np.cumsum(areas)]).astype(np.int64)
+    image_of = np.repeat(np.arange(packed.n), np.diff(packed.point_offsets))
+    widths = np.array([w for _, w in packed.sizes] + [0], dtype=np.int64)[image_of]
+    points = packed.points.astype(np.int64).reshape(-1, 2)
+    point_pixel = check_distinct_pixels(pixel_offsets[image_of] + points[:, 1] * widths + points[:, 0])
+    lut = iu.srgb_byte_lut()
+    x_dense = torch.empty((max(int(pixel_offsets[-1]), 1), 3), dtype=torch.float32, device=dev)
+    for i, image in enumerate(images):      # one image on the host at a time
+        if areas[i]:
+            h, w = packed.sizes[i]
+            ys, xs = np.divmod(np.arange(areas[i]), w)
+            x_dense[pixel_offsets[i]:pixel_offsets[i + 1]] = torch.from_numpy(
+                np.ascontiguousarray(_inputs_at(image, xs, ys, lut))).to(dev)
+    packed.x_dense, packed.pixel_offsets, packed.point_pixel = x_dense, pixel_offsets, point_pixel
+    packed.pixels = int(pixel_offsets[-1])
+    packed.d_point_pixel = _device_array(torch, dev, point_pixel)
+    packed.recover_workspace = None
+    return packed
+
+
 def _host_weights(weights):
     if hasattr(weights, "is_cuda"):
         weights = weights.detach().cpu().numpy()
@@ -257,9 +320,15 @@ def hinge(packed, first, count, delta, margin, weights=None):
 def backward(weights, packed, first, count):
     """rf_train_cnn_points_backward_f32 with packed.grad_r at the points of images [first, first +
     count): grad_w, CUDA float32 [4513]."""
+    p0, p1 = _run(packed, first, count)
+    return _backward_at(weights, packed, packed.x[p0:p1], packed.grad_r[p0:p1])
+
+
+def _backward_at(weights, packed, x, grad):
+    """The backward entry over the rows of x [P,3] with d loss / d output in grad [P]."""
     torch = _ffi.require_gpu()
     lib = _ffi_train.load_library()
-    p0, p1 = _run(packed, first, count)
+    p0, p1 = 0, int(grad.shape[0])
     dev = packed.x.device
     grad_w = torch.zeros(_ffi.CNN_NPARAMS, dtype=torch.float32, device=dev)
     if p1 == p0:
@@ -271,18 +340,124 @@ def backward(weights, packed, first, count):
     if packed.workspace is None or packed.workspace.numel() < need:
         packed.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
     rc = lib.rf_train_cnn_points_backward_f32(
-        packed.x.data_ptr() + 12 * p0, weights.data_ptr(), packed.grad_r.data_ptr() + 4 * p0,
-        p1 - p0, grad_w.data_ptr(), packed.workspace.data_ptr(), packed.workspace.numel(),
-        _ffi.current_stream_ptr(torch))
+        x.data_ptr(), weights.data_ptr(), grad.data_ptr(), p1 - p0, grad_w.data_ptr(),
+        packed.workspace.data_ptr(), packed.workspace.numel(), _ffi.current_stream_ptr(torch))
     _ffi_train.check(rc, "rf_train_cnn_points_backward_f32")
     return grad_w
 
 
-def loss_and_grad(weights, packed, first, count, delta=0.1, margin=0.0, hinge_weights=None):
+def _dense_run(packed, first, count):
+    if not hasattr(packed, "x_dense"):
+        raise ValueError("the rRel* modes need every pixel: pack with pack_dense()")
+    _run(packed, first, count)
+    return int(packed.pixel_offsets[first]), int(packed.pixel_offsets[first + count])
+
+
+def forward_dense(weights, packed, first, count):
+    """The network's output e at every pixel of images [first, first + count): (x of the run [Q,3],
+    e CUDA float32 [Q]), by the forward pass every other part of the package runs."""
+    from . import ops
+    q0, q1 = _dense_run(packed, first, count)
+    x = packed.x_dense[q0:q1]
+    e, _ = ops.cnn_reflectance_f32(x.view(1, 1, q1 - q0, 3), layout="nhwc_bgr",
+                                   weights=_host_weights(weights), want_u8=False)
+    return x, e.view(-1)
+
+
+def recover_points(x, e, pixel, norm, lightness):
+    """rf_recover_forward_f32: the recovered lightness at the listed pixels (CUDA int64, or None =
+    all rows of x in order) of x [P,3] / e [P], written into `lightness`."""
+    torch = _ffi.require_gpu()
+    lib = _ffi_recover.load_library()
+    listed = int(e.shape[0] if pixel is None else pixel.shape[0])
+    rc = lib.rf_recover_forward_f32(x.data_ptr(), e.data_ptr(), int(e.shape[0]),
+                                    None if pixel is None else pixel.data_ptr(), listed, int(norm),
+                                    lightness.data_ptr(), None, None, _ffi.current_stream_ptr(torch))
+    _ffi_recover.check(rc, "rf_recover_forward_f32")
+    return lightness
+
+
+def boundary(packed, x, e, norm, penalty, scale_reflectance, scale_shading):
+    """rf_recover_boundary_backward_f32 over all rows of x / e: (the unscaled means of the reflectance
+    and the shading boundary loss, CUDA float64 [2]; grad_e CUDA float32 [Q], the scaled losses'
+    gradient)."""
+    torch = _ffi.require_gpu()
+    lib = _ffi_recover.load_library()
+    npixels, dev = int(e.shape[0]), x.device
+    means = torch.zeros(2, dtype=torch.float64, device=dev)
+    grad_e = torch.empty(max(npixels, 1), dtype=torch.float32, device=dev)
+    need = _ffi_recover.boundary_workspace_bytes(npixels)
+    if packed.recover_workspace is None or packed.recover_workspace.numel() < need:
+        packed.recover_workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    rc = lib.rf_recover_boundary_backward_f32(
+        x.data_ptr(), e.data_ptr(), npixels, int(norm), _ffi_recover.PENALTIES[penalty],
+        float(scale_reflectance), float(scale_shading), means.data_ptr(), grad_e.data_ptr(),
+        packed.recover_workspace.data_ptr(), packed.recover_workspace.numel(),
+        _ffi.current_stream_ptr(torch))
+    _ffi_recover.check(rc, "rf_recover_boundary_backward_f32")
+    return means, grad_e[:npixels]
+
+
+def hinge_scatter(x, e, grad_l, pixel, norm, scale, grad_e):
+    """rf_recover_hinge_scatter_f32: scale * d hinge / d e added into grad_e at the listed pixels."""
+    torch = _ffi.require_gpu()
+    lib = _ffi_recover.load_library()
+    rc = lib.rf_recover_hinge_scatter_f32(x.data_ptr(), e.data_ptr(), grad_l.data_ptr(),
+                                          pixel.data_ptr(), int(pixel.shape[0]), int(e.shape[0]),
+                                          int(norm), float(scale), grad_e.data_ptr(),
+                                          _ffi.current_stream_ptr(torch))
+    _ffi_recover.check(rc, "rf_recover_hinge_scatter_f32")
+    return grad_e
+
+
+def _loss_and_grad_dense(weights, packed, first, count, delta, margin, hinge_weights, norm,
+                         loss_scale_whdr, loss_scale_boundaries, boundary_penalty):
+    if boundary_penalty not in BOUNDARY_PENALTIES:
+        raise ValueError("boundary_penalty must be L1 or L2")
+    p0, p1 = _run(packed, first, count)
+    q0, q1 = _dense_run(packed, first, count)
+    if q1 == q0:        # no pixels: nothing to average over
+        torch = _ffi.require_gpu()
+        parts = {"hinge": 0.0, "boundary_reflectance": 0.0, "boundary_shading": 0.0}
+        return 0.0, np.zeros(count), torch.zeros(_ffi.CNN_NPARAMS, dtype=torch.float32,
+                                                 device=packed.x.device), parts
+    x, e = forward_dense(weights, packed, first, count)
+    pixel = (packed.d_point_pixel[p0:p1] - int(packed.pixel_offsets[first])).contiguous()
+    if p1 > p0:
+        recover_points(x, e, pixel, norm, packed.r[p0:p1])
+    losses = hinge(packed, first, count, delta, margin, hinge_weights)
+    means, grad_e = boundary(packed, x, e, norm, boundary_penalty, loss_scale_boundaries,
+                             loss_scale_boundaries)
+    if p1 > p0:
+        hinge_scatter(x, e, packed.grad_r[p0:p1], pixel, norm, loss_scale_whdr, grad_e)
+    grad_w = _backward_at(weights, packed, x, grad_e)
+    per_image = losses.cpu().numpy()
+    b_refl, b_shad = (float(v) for v in means.cpu().numpy())
+    parts = {"hinge": float(per_image.mean()) if count else 0.0, "boundary_reflectance": b_refl,
+             "boundary_shading": b_shad}
+    loss = loss_scale_whdr * parts["hinge"] + loss_scale_boundaries * (b_refl + b_shad)
+    return loss, per_image, grad_w, parts
+
+
+def loss_and_grad(weights, packed, first, count, delta=0.1, margin=0.0, hinge_weights=None,
+                  rs_mode="rDirectly", loss_scale_whdr=1.0, loss_scale_boundaries=0.1,
+                  boundary_penalty="L1"):
     """(loss, per-image losses float64 [count] (host), grad_w CUDA float32 [4513]) of the mean hinge
     loss over the packed images [first, first + count) - a minibatch is a run of consecutive images
     and needs no repacking.  The loss is that of exactly the reflectance `decompose` would output
-    for these weights.  hinge_weights: the comparison weights of this step (subsample_weights)."""
+    for these weights.  hinge_weights: the comparison weights of this step (subsample_weights).
+    rs_mode rRelMean / rRelMax / rRelY / rRelNorm (packed by pack_dense): the network's output is the
+    factor of image / norm(image); the hinge loss reads the recovered lightness, both boundary losses
+    (boundary_penalty L1 or L2) are means over every pixel of the run (count = the run's pixels, the
+    reference's N H W for images of one size), and the result has a fourth element:
+    loss = loss_scale_whdr * hinge + loss_scale_boundaries * (boundary_reflectance +
+    boundary_shading), grad_w its gradient, and {"hinge", "boundary_reflectance",
+    "boundary_shading"} the three unscaled parts.  In rDirectly the three scales are not used."""
+    norm = rs_norm(rs_mode)
+    if norm is not None:
+        return _loss_and_grad_dense(weights, packed, first, count, delta, margin, hinge_weights, norm,
+                                    float(loss_scale_whdr), float(loss_scale_boundaries),
+                                    boundary_penalty)
     forward(weights, packed, first, count)
     losses = hinge(packed, first, count, delta, margin, hinge_weights)
     grad_w = backward(weights, packed, first, count)
@@ -308,13 +483,32 @@ def whdr_at_points(packed, delta=0.1):
     return out
 
 
-def evaluate(weights, packed, delta=0.1, margin=0.0):
-    """{"hinge": mean hinge loss, "whdr": mean true WHDR (threshold delta)} over all packed images."""
+def evaluate(weights, packed, delta=0.1, margin=0.0, rs_mode="rDirectly"):
+    """{"hinge": mean hinge loss, "whdr": mean true WHDR (threshold delta)} over all packed images.
+    In an rRel* mode both are those of the recovered lightness; only the points are evaluated."""
+    norm = rs_norm(rs_mode)
     if packed.n == 0:
         return {"hinge": 0.0, "whdr": 0.0}
     forward(weights, packed, 0, packed.n)
+    if norm is not None and packed.total:
+        recover_points(packed.x, packed.r[:packed.total].clone(), None, norm, packed.r)
     losses = hinge(packed, 0, packed.n, delta, margin).cpu().numpy()
     return {"hinge": float(losses.mean()), "whdr": float(whdr_at_points(packed, delta).mean())}
+
+
+def boundary_means(weights, packed, rs_mode, boundary_penalty="L1", batch_size=10):
+    """{"boundary_reflectance", "boundary_shading"}: both boundary means over every pixel of the
+    packed set (pack_dense), taken in runs of batch_size images and weighted by their pixels."""
+    norm = rs_norm(rs_mode)
+    if norm is None:
+        raise ValueError("rDirectly has no boundary loss")
+    sums = np.zeros(2)
+    for first, count in batch_runs(packed.n, batch_size):
+        x, e = forward_dense(weights, packed, first, count)
+        means, _ = boundary(packed, x, e, norm, boundary_penalty, 0.0, 0.0)
+        sums += means.cpu().numpy() * int(e.shape[0])
+    total = max(int(packed.pixels), 1)
+    return {"boundary_reflectance": float(sums[0] / total), "boundary_shading": float(sums[1] / total)}
 
 
 def batch_runs(n, batch_size, full_batch=False):
@@ -326,7 +520,8 @@ def batch_runs(n, batch_size, full_batch=False):
 
 def fit(packed, weights=None, iterations=100, batch_size=10, base_lr=1e-3, solver="sgd",
         momentum=0.9, momentum2=0.999, adam_eps=1e-8, full_batch=False, delta=0.1, margin=0.0,
-        seed=0, report_every=0, held_out=None, log=None, max_evaluated=0):
+        seed=0, report_every=0, held_out=None, log=None, max_evaluated=0, rs_mode="rDirectly",
+        loss_scale_whdr=1.0, loss_scale_boundaries=0.1, boundary_penalty="L1"):
     """Train for `iterations` steps.  Minibatches are runs of `batch_size` consecutive images of the
     packed order, and the order of the batches is reshuffled every epoch from `seed`; full_batch
     takes all images every step.  solver: "sgd" (v = momentum v + lr g; w -= v, Caffe's SGD) or
@@ -334,6 +529,9 @@ def fit(packed, weights=None, iterations=100, batch_size=10, base_lr=1e-3, solve
     true WHDR of the whole training set and of `held_out` (another pack()) are recorded, over all
     their comparisons.  max_evaluated > 0: every step evaluates a random max_evaluated of the hinge
     comparisons of an image that has more (subsample_weights, drawn on the device from `seed`).
+    rs_mode and the three options behind it: loss_and_grad; in an rRel* mode `packed` comes from
+    pack_dense, every report adds both boundary means over the training set to its "train" entry
+    (held_out needs its points only) and "batch_parts" holds the step's three unscaled parts.
     Returns (weights float32 [4513] (host), history: list of dicts)."""
     torch = _ffi.require_gpu()
     from . import weights as wmod
@@ -343,6 +541,10 @@ def fit(packed, weights=None, iterations=100, batch_size=10, base_lr=1e-3, solve
         raise ValueError("no images to train on")
     if iterations < 0 or batch_size < 1:
         raise ValueError("iterations must be >= 0 and batch_size >= 1")
+    dense = rs_norm(rs_mode) is not None
+    if dense:
+        _dense_run(packed, 0, packed.n)
+    mode = {"rs_mode": rs_mode} if dense else {}
     dev = packed.x.device
     w = torch.from_numpy(_host_weights(wmod.load_weights() if weights is None else weights).copy()).to(dev)
     m1, m2 = torch.zeros_like(w), torch.zeros_like(w)
@@ -352,23 +554,34 @@ def fit(packed, weights=None, iterations=100, batch_size=10, base_lr=1e-3, solve
     chooser.manual_seed(int(seed))
 
     def record(step, batch_loss):
-        entry = {"iteration": step, "batch_loss": batch_loss, "train": evaluate(w, packed, delta, margin)}
+        entry = {"iteration": step, "batch_loss": batch_loss,
+                 "train": evaluate(w, packed, delta, margin, **mode)}
+        if dense:
+            entry["batch_parts"] = batch_parts
+            entry["train"].update(boundary_means(w, packed, rs_mode, boundary_penalty, batch_size))
         if held_out is not None:
-            entry["held_out"] = evaluate(w, held_out, delta, margin)
+            entry["held_out"] = evaluate(w, held_out, delta, margin, **mode)
         history.append(entry)
         if log is not None:
             log(entry)
 
+    batch_loss = batch_parts = None
+    mode_options = dict(rs_mode=rs_mode, loss_scale_whdr=loss_scale_whdr,
+                        loss_scale_boundaries=loss_scale_boundaries,
+                        boundary_penalty=boundary_penalty)
     if report_every:
         record(0, None)
-    batch_loss = None
     for step in range(1, iterations + 1):
         if not queue:
             queue = [runs[i] for i in np.random.RandomState(seed + epoch).permutation(len(runs))]
             epoch += 1
         first, count = queue.pop(0)
-        batch_loss, _, grad = loss_and_grad(w, packed, first, count, delta, margin,
-                                            subsample_weights(packed, first, count, max_evaluated, chooser))
+        step_weights = subsample_weights(packed, first, count, max_evaluated, chooser)
+        if dense:
+            batch_loss, _, grad, batch_parts = loss_and_grad(w, packed, first, count, delta, margin,
+                                                             step_weights, **mode_options)
+        else:
+            batch_loss, _, grad = loss_and_grad(w, packed, first, count, delta, margin, step_weights)
         if solver == "sgd":
             m1.mul_(momentum).add_(grad, alpha=base_lr)
             w.sub_(m1)
@@ -427,6 +640,16 @@ def build_parser():
                    help="augmented: the hinge loss takes the transitive hull of each photo's judgements")
     p.add_argument("--max_evaluated", type=_count, default=MAX_EVALUATED_COMPARISONS, metavar="K",
                    help="per step a random K of an image's comparisons when it has more (0 = all)")
+    p.add_argument("--RS_est_mode", choices=RS_MODES, default="rDirectly",
+                   help="rDirectly: the output is the reflectance intensity; rRelMean / rRelMax / rRelY / "
+                        "rRelNorm: it is the factor of image / norm(image) (colour reflectance and shading; "
+                        "dense steps).  The reference trainer's own default is rRelMax")
+    p.add_argument("--loss_scale_whdr", type=_non_negative, default=1.0,
+                   help="weight of the hinge loss outside rDirectly (the reference's default: 10)")
+    p.add_argument("--loss_scale_boundaries01", type=_non_negative, default=0.1,
+                   help="weight of both boundary losses outside rDirectly (the reference's default: 0.1)")
+    p.add_argument("--boundary_penalty", choices=BOUNDARY_PENALTIES, default="L1",
+                   help="penalty on reflectance and shading outside [0, 1] (outside rDirectly)")
     p.add_argument("--solver", choices=SOLVERS, default="sgd")
     p.add_argument("--base_lr", type=_positive(float), default=1e-3)
     p.add_argument("--momentum", type=_non_negative, default=0.9)
@@ -456,18 +679,20 @@ def parse_args(argv):
     return parser, args
 
 
-def load_packed(photos, args, order_seed):
-    """pack() of photos read by sweep.load (host decode), judgements scaled to each photo's size."""
+def load_packed(photos, args, order_seed, dense=False):
+    """pack() - pack_dense() when dense - of photos read by sweep.load (host decode), judgements
+    scaled to each photo's size."""
     from . import sweep
+    packer = pack_dense if dense else pack
     images, _, _, judgements, _ = sweep.load(photos)
     comps = [whdr_mod.to_pixels(j, im.shape[0], im.shape[1]) for j, im in zip(judgements, images)]
     if args.comparisons != "augmented":
-        return pack(images, comps, order_seed, args.ratio, bool(args.eval_dense))
+        return packer(images, comps, order_seed, args.ratio, bool(args.eval_dense))
     from . import augment
     lists, points = augment.augment_files([sweep.judgements_for(f) for f in photos], seed=args.seed)
     hull = [whdr_mod.to_pixels(augment.to_rows(a, p), im.shape[0], im.shape[1])
             for a, p, im in zip(lists, points, images)]
-    return pack(images, comps, order_seed, args.ratio, bool(args.eval_dense), hinge_comparisons_px=hull)
+    return packer(images, comps, order_seed, args.ratio, bool(args.eval_dense), hinge_comparisons_px=hull)
 
 
 def main(argv=None):
@@ -487,12 +712,19 @@ def main(argv=None):
         if not held:
             parser.error("--report_split: no photo in split %s" % args.report_split)
     init = wmod.load_weights(args.init)
-    packed = load_packed(selected, args, args.seed)
+    dense = args.RS_est_mode != "rDirectly"
+    mode = dict(rs_mode=args.RS_est_mode, loss_scale_whdr=args.loss_scale_whdr,
+                loss_scale_boundaries=args.loss_scale_boundaries01,
+                boundary_penalty=args.boundary_penalty) if dense else {}
+    packed = load_packed(selected, args, args.seed, dense)
     held_packed = load_packed(held, args, None) if held else None
 
     def say(entry):
         line = "iteration %d: train hinge %.6f whdr %.4f" % (
             entry["iteration"], entry["train"]["hinge"], entry["train"]["whdr"])
+        if "boundary_shading" in entry["train"]:
+            line += " boundaries %.6g %.6g" % (entry["train"]["boundary_reflectance"],
+                                               entry["train"]["boundary_shading"])
         if "held_out" in entry:
             line += "; %s hinge %.6f whdr %.4f" % (args.report_split, entry["held_out"]["hinge"],
                                                    entry["held_out"]["whdr"])
@@ -502,7 +734,7 @@ def main(argv=None):
                          base_lr=args.base_lr, solver=args.solver, momentum=args.momentum,
                          full_batch=args.full_batch, delta=args.delta, margin=args.margin,
                          seed=args.seed, report_every=args.report_every, held_out=held_packed,
-                         log=say, max_evaluated=args.max_evaluated)
+                         log=say, max_evaluated=args.max_evaluated, **mode)
     wmod.write_caffemodel(args.out, final)
     result = {"delta": args.delta, "margin": args.margin, "ratio": args.ratio,
               "eval_dense": args.eval_dense, "comparisons_type": args.comparisons,
@@ -511,6 +743,10 @@ def main(argv=None):
               "batch_size": args.batch_size, "full_batch": bool(args.full_batch), "seed": args.seed,
               "images": packed.n, "points": packed.total, "comparisons": int(packed.comps.shape[0]),
               "init": args.init, "out": args.out, "history": history}
+    if dense:
+        result.update({"RS_est_mode": args.RS_est_mode, "loss_scale_whdr": args.loss_scale_whdr,
+                       "loss_scale_boundaries01": args.loss_scale_boundaries01,
+                       "boundary_penalty": args.boundary_penalty, "pixels": packed.pixels})
     if split:
         result["split"] = split
     if args.report_split:
